@@ -27,6 +27,13 @@ line as `full`) and to stderr.  `roofline` times the dominant kernel with HIP ev
 SAME source data, copied back from HBM; `parity_check` renders one call of the benched launch shape on a fresh context
 and compares chosen blocks of it, bit for bit, with the oracle; `other_configs` carries configs 1, 3, 4 and 5 (one
 shard) in short form; `realtime_us_per_callback` is the one-block-per-call latency of the headline graph.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it builds the graph in one context, runs W
+untimed steps, times K steps and prints the line (`value`, `ms_per_step`, ...); `roofline`, `cpu_baseline`, `parity_check`,
+`other_configs` and the rest of the above are then null or absent.  `--full` adds all of them, and times the default single-GPU
+line in five fresh contexts.  `--dump-outputs DIR` writes the mix bus of the last timed step to DIR/mix_bus.npy (float32, frames x 2;
+with N > 1 ranks rank 0 writes the reduced bus of the whole graph);
+the sources and the graph are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -908,6 +915,7 @@ def run_workload(env, args, wl, V, B, K, F, steps, warmup, full=True, parity_mul
     for _ in range(steps):
         step()
     dt_enqueue = time.perf_counter() - t0  # the host's share: message calls + launches of all the steps (the device runs behind them)
+    last_slot = slot[0] - 1  # the bus slot of the last timed step (finish_reductions may move the counter past a partly filled buffer)
     finish_reductions()  # every bus of the timed region is fully reduced before the clock stops
     sync()
     if dist is not None:
@@ -927,6 +935,18 @@ def run_workload(env, args, wl, V, B, K, F, steps, warmup, full=True, parity_mul
                 reducer.close(dist)
             cx.close()
             raise ExchangeFailed("; ".join("rank %d: %s" % (r, e) for r, e in enumerate(errs) if e))
+    outputs = None
+    if full and rank == 0 and args.dump_outputs:
+        # --dump-outputs: what the caller of the timed path received from its last step, copied off before any pass below renders
+        # into the same buffers.  N > 1: the REDUCED mix bus, which the exchange and ordered_abi modes write into a buffer of their
+        # own (every reducer's wait(i) returns it; finish_reductions has waited for all of them)
+        if args.host_buffers:
+            bus = host_out.copy()
+        else:
+            b_last, r_last = (last_slot // R) % 2, last_slot % R
+            red = reducer.wait(b_last) if reducer is not None else outs[b_last]
+            bus = red[r_last * step_elems:(r_last + 1) * step_elems].cpu().numpy()
+        outputs = {"mix_bus": bus.reshape(K * B, 2)}
 
     roofline = None
     if timing:
@@ -1106,6 +1126,8 @@ def run_workload(env, args, wl, V, B, K, F, steps, warmup, full=True, parity_mul
         }
         if own is not None:
             res["parity_check_timed_context"] = own
+        if outputs is not None:
+            res["outputs"] = outputs
     if reducer is not None and hasattr(reducer, "close"):
         if res is not None:  # how far the ranks ran apart: the longest rank 0's reduce kernels waited for each rank's arrival
             res["config"]["bus_exchange_max_wait_us"] = reducer.x.wait_stats() if hasattr(reducer, "x") else None
@@ -1449,6 +1471,25 @@ def write_full(line, world):
     return path
 
 
+DUMP_BYTES_MAX = 64 * 10 ** 6 - 4096  # --dump-outputs: the arrays' bytes; with their .npy headers at most 64 MB in all
+
+
+def write_outputs(path, outputs):
+    """--dump-outputs: one float32 <name>.npy per array.  An array over the cap keeps a fixed, seeded sample of its rows, and
+    <name>_rows.npy (float64) says which rows those are."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in sorted(outputs.items()):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > DUMP_BYTES_MAX:
+            keep = DUMP_BYTES_MAX // (a.nbytes // a.shape[0] + 8)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 
 # ------------------------------------------------------------------------------------------------ launcher
 def self_launch(args):
@@ -1501,8 +1542,16 @@ def main():
     ap.add_argument("--no-parity-check", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--no-realtime", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline's timed steps: the per-kernel event pass (roofline, step-time distribution), "
+                         "parity checks against the oracle, the CPU baseline, the realtime probe, host-buffer figures, other configs, and "
+                         "five fresh contexts for the default single-GPU line.  A plain run only sets up, warms up, times --steps steps "
+                         "in one context and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path's last step handed its caller (the interleaved mix bus, "
+                         "frames x 2, float32; with N > 1 ranks the reduced bus of the whole graph) to DIR/mix_bus.npy")
     ap.add_argument("--lean", action="store_true",
-                    help="profiling runs: the timed region only (no CPU baseline, parity check, other configs, realtime probe)")
+                    help="with --full, for profiling runs: no CPU baseline, parity check, other configs, realtime probe")
     ap.add_argument("--taps", type=int, default=65536)
     ap.add_argument("--source-format", choices=["f32", "i16"], default="f32",
                     help="cfg2/cfg5 only: planar f32 sources (the headline) or interleaved stereo i16 (4 B per voice-sample)")
@@ -1545,9 +1594,11 @@ def main():
                          "NOT a scaling figure and the line says so")
     ap.add_argument("--contexts", type=int, default=0,
                     help="time the workload in this many FRESH contexts inside the one run and report the median context (default: 5 for "
-                         "the default single-GPU line, 1 otherwise)")
-    ap.add_argument("--force-other-configs", action="store_true", help="tests: emit other_configs / bus_reduce_modes for a non-default shape too")
+                         "the default single-GPU --full line, 1 otherwise)")
+    ap.add_argument("--force-other-configs", action="store_true", help="tests, with --full: emit other_configs / bus_reduce_modes for a non-default shape too")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline's timed steps and nothing that takes runs or checks of its own
+        args.no_cpu_baseline = args.no_parity_check = args.no_other_configs = args.no_realtime = args.no_kernel_timing = True
     if args.lean:
         args.no_cpu_baseline = args.no_parity_check = args.no_other_configs = args.no_realtime = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1614,9 +1665,9 @@ def main():
         r0 = run_workload(env, args, wl, V, B, K, F, steps, args.warmup, full=False, warm_ms=args.warm_ms)
         repeats.append({"ms_per_step": r0["ms_per_step"], "kernel_us": (r0["roofline"] or {}).get("avg_launch_us")})
     # The headline kernel runs in one of two HBM placement states, fixed per context when its buffers are allocated (DESIGN.md
-    # §7): one context is a coin toss.  So the default line times the same workload in `--contexts` FRESH contexts (fresh bus /
+    # §7): one context is a coin toss.  So the default --full line times the same workload in `--contexts` FRESH contexts (fresh bus /
     # table allocations each) inside this one run and reports the MEDIAN context; all of them are in the line.
-    n_ctx = args.contexts if args.contexts else (5 if (world == 1 and default_shape and not hostonly) else 1)
+    n_ctx = args.contexts if args.contexts else (5 if (args.full and world == 1 and default_shape and not hostonly) else 1)
     ctx_runs = []
     for _ in range(max(0, n_ctx - 1)):
         r0 = run_workload(env, args, wl, V, B, K, F, steps, args.warmup, full=False, warm_ms=args.warm_ms)
@@ -1634,6 +1685,8 @@ def main():
             res["config"]["bus_reduce_fallback"] = runtime_fallback
     line = None
     contexts = None
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, res.pop("outputs"))
     if rank == 0 and ctx_runs:
         ctx_runs.append(res)
         order = sorted(range(len(ctx_runs)), key=lambda i: ctx_runs[i]["ms_per_step"])

@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 for rep in 1 2; do
   for v in default $(ls firewheel_amd/csrc/var_*.so 2>/dev/null); do
     if [ $v = default ]; then L=$GRAFT_REPO_ROOT/firewheel_amd/csrc/libfwgpu.so; else L=$GRAFT_REPO_ROOT/$v; fi
-    FWGPU_LIB=$L timeout 200 python bench.py --rs-source --steps 20 --warmup 3 --lean 2>/dev/null | python -c "
+    FWGPU_LIB=$L timeout 200 python bench.py --full --rs-source --steps 20 --warmup 3 --lean 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 r = d['roofline']

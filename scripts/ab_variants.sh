@@ -3,7 +3,7 @@
 args=$1; shift
 for rep in 1 2; do
   for v in "$@"; do
-    FWGPU_LIB=$GRAFT_REPO_ROOT/firewheel_amd/csrc/$v timeout 120 python bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-other-configs --no-realtime $args 2>/dev/null | python -c "
+    FWGPU_LIB=$PWD/firewheel_amd/csrc/$v timeout 120 python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-other-configs --no-realtime $args 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 r = d['roofline']

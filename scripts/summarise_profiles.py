@@ -49,7 +49,7 @@ if stats:
                          "(the timed region and the event pass behind it: what bench.py's avg_launch_us measures)\n"
                          % (domk.split("(")[0].replace("void ", ""), len(d), sum(d) / len(d) / 1e3, sum(last) / len(last) / 1e3, min(last) / 1e3, len(last)))
     with open(os.path.join(outdir, "%s_%s%s_kernel_stats.csv" % (tag, cfg, suffix)), "w") as f:
-        f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --workload %s --lean --steps %d --warmup 3 --warm-ms %s %s"
+        f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --full --workload %s --lean --steps %d --warmup 3 --warm-ms %s %s"
                 "   (MI355X, %s; %d voices, block %d, %d blocks per step)\n" % (cfg, steps, os.environ.get("WARM_MS", "60"), extra, tag, V, B, K))
         f.write(warm_note)
         w = csv.writer(f)

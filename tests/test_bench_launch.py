@@ -54,14 +54,15 @@ def test_gpus_2_self_launches_two_ranks_and_prints_one_line(mode):
     assert d["config"]["parallelism"].startswith("voice-shard x2")
     assert d["value"] is None and "host-only harness" in d["invalid"]  # no audio was computed: never a measurement
     assert d["ms_per_step"] > 0
+    assert d["parity_check"] is None and "other_configs" not in d  # a plain run: the timed steps only (the rest: --full)
 
 
 def test_gpus_3_default_exchange_mode_with_the_n_rank_extras():
-    """the N > 1 line as the driver will see it: the default mix-bus reduction is libfwgpu's own exchange (handles carried by
+    """the N > 1 line of a --full run: the default mix-bus reduction is libfwgpu's own exchange (handles carried by
     all_gather_object, regions "mapped" by the fake runtime), the line carries a parity_check entry (skipped on this tier: the
     harness computes no audio — but the oracle's WHOLE graph, 3 shards under one 3-port SumNode, was built and rendered), and
     next to it configs[4] with the reduction after every step and the headline under the two RCCL reductions."""
-    d = run_bench(["--gpus", "3", "--force-other-configs"])
+    d = run_bench(["--gpus", "3", "--full", "--force-other-configs"])
     assert d["n_gpus"] == 3 and d["ranks_seen"] == 3
     assert d["config"]["bus_reduce"] == "exchange" and d["config"]["bus_reduce_fallback"] is None
     pc = d["parity_check"]
@@ -75,7 +76,7 @@ def test_gpus_3_default_exchange_mode_with_the_n_rank_extras():
 
 def test_gpus_8_launched_like_the_driver_launches_it():
     """the round-end scaling run at N = 8, command for command: `python -m torch.distributed.run --nnodes=1 --nproc-per-node 8
-    --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 --steps K --warmup W` — eight ranks, the default exchange with eight
+    --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 --steps K --warmup W --full` — eight ranks, the default exchange with eight
     handles carried through the control plane, configs[4] with the reduction after every step, the RCCL modes beside it, the
     whole-graph parity plumbing for eight shards under one 8-port SumNode (skipped on this tier: the harness computes no audio)."""
     import socket
@@ -90,7 +91,7 @@ def test_gpus_8_launched_like_the_driver_launches_it():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port",
            str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--workload", "cfg2", "--voices", "64", "--block", "64", "--blocks-per-step", "4",
-           "--src-frames", "1024", "--steps", "4", "--warmup", "1", "--force-other-configs"]
+           "--src-frames", "1024", "--steps", "4", "--warmup", "1", "--full", "--force-other-configs"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [x for x in r.stdout.splitlines() if x.strip().startswith("{")]
@@ -113,6 +114,35 @@ def test_single_rank_line_has_the_contract_fields():
               "dtype", "data", "config", "roofline", "cpu_baseline", "parity_check", "rccl_ranks_seen"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["config"]["launch_plan"] == 1 and d["vs_baseline"] is None and d["dtype"] == "f32"
+
+
+def test_dump_outputs_writes_one_float32_file_of_the_bus_shape(tmp_path):
+    """--dump-outputs DIR: the file's name, dtype and shape (the interleaved mix bus of the last step's 4 blocks of 64 frames,
+    frames x 2) and the line beside it.  The host-only harness computes no audio, so the content is checked on the GPU tier
+    (tests/test_gpu_bench_dump.py, against the oracle)."""
+    import numpy as np
+
+    d = run_bench(["--dump-outputs", str(tmp_path / "out")])
+    a = np.load(str(tmp_path / "out" / "mix_bus.npy"))
+    assert a.dtype == np.float32 and a.shape == (4 * 64, 2)
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["config"]["warmup_steps_run"] == 2
+
+
+def test_dump_outputs_over_the_cap_keep_a_seeded_sample_of_rows(tmp_path, monkeypatch):
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 4096)
+    a = np.arange(4000 * 2, dtype=np.float32).reshape(4000, 2)
+    for sub in ("a", "b"):
+        bench.write_outputs(str(tmp_path / sub), {"mix_bus": a})
+    got = np.load(str(tmp_path / "a" / "mix_bus.npy"))
+    rows = np.load(str(tmp_path / "a" / "mix_bus_rows.npy"))
+    assert got.dtype == np.float32 and rows.dtype == np.float64 and got.nbytes + rows.nbytes <= 4096
+    assert np.array_equal(got, a[rows.astype(np.int64)]) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(str(tmp_path / "b" / "mix_bus_rows.npy")))  # the same rows on every run
 
 
 def test_gpus_mismatch_with_an_outer_launcher_is_refused():
