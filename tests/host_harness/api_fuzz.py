@@ -63,6 +63,18 @@ def run(seed):
                 n_in, n_out = rng.choice([(2, 2), (0, 2), (1, 1), (4, 2), (5, 2), (2, 3), (u() % 70, u() % 70)])
             npar = rng.randint(0, 5)
             par = (C.c_float * max(npar, 1))(*[rng.choice(WEIRD_F + [float(s) for s in samples[:3]]) for _ in range(max(npar, 1))])
+            if kind == 12 and rng.random() < 0.6:
+                # a valid FIR node: an impulse response of T on either side of FIR_SEG (4096), so that the launch stub's ring /
+                # partials / pool checks meet real rings across set_max_batch changes
+                T, ch = rng.choice([1, 2, 255, 4095, 4097, 9000]), rng.choice([1, 2])
+                data = (C.c_float * (T * ch))()
+                keep.append(data)
+                ir = L.fwgpu_sample_create(c, 5, ch, T, C.cast(data, C.c_void_p))
+                if ir >= 0:
+                    samples.append(ir)
+                    n_in, n_out = rng.choice(SHAPES[12])
+                    npar = 1
+                    par = (C.c_float * 1)(float(ir))
             r = L.fwgpu_add_node(c, kind, n_in, n_out, par, npar)
             if r >= 0:
                 nodes.append(r)

@@ -41,11 +41,13 @@ static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) {
 }
 extern "C" unsigned long long fwh_alloc_calls;  /* defined in launch_stubs.cpp: device / pinned allocations so far */
 extern "C" long long fwh_fail_alloc_in; /* > 0: the n-th device / pinned allocation from now fails (then disarms) */
+extern "C" void fwh_alloced(const void* p, size_t n);  /* launch_stubs.cpp: books the size of every live allocation */
 static inline hipError_t hipMalloc(void** p, size_t n) {
     fwh_alloc_calls++;
     if (fwh_fail_alloc_in > 0 && --fwh_fail_alloc_in == 0) return hipErrorOutOfMemory;
     if (n > ((size_t)1 << 32)) return hipErrorOutOfMemory;  /* the harness never needs more; keeps a bad size from eating the host */
     *p = calloc(n ? n : 1, 1);
+    if (*p) fwh_alloced(*p, n);
     return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 template <class T>
@@ -53,7 +55,7 @@ static inline hipError_t hipMalloc(T** p, size_t n) { return hipMalloc((void**)p
 extern "C" void fwh_freed(const void* p);  // launch_stubs.cpp: books the stubs keep per device buffer end with the buffer
 static inline hipError_t hipFree(void* p) { if (p) fwh_freed(p); free(p); return hipSuccess; }
 static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { return hipMalloc(p, n); }
-static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+static inline hipError_t hipHostFree(void* p) { if (p) fwh_freed(p); free(p); return hipSuccess; }
 enum { hipHostRegisterDefault = 0, hipHostRegisterMapped = 2 };
 static inline hipError_t hipHostRegister(void*, size_t, unsigned) { return hipSuccess; }
 static inline hipError_t hipHostUnregister(void*) { return hipSuccess; }

@@ -71,7 +71,20 @@ void touch(const void* p, size_t bytes) {
     g_sink = ((const volatile unsigned char*)p)[0];
     g_sink = ((const volatile unsigned char*)p)[bytes - 1];
 }
+// bytes of every live device allocation by its base address (fakehip's hipMalloc / hipFree): the extents the kernels index are
+// checked against them, not only touched (an under-sized pool of the fake runtime is a report only under ASan)
+std::mutex g_alloc_mu;
+std::map<const void*, size_t> g_alloc_bytes;
+size_t alloc_bytes(const void* base) {
+    std::lock_guard<std::mutex> lk(g_alloc_mu);
+    auto it = g_alloc_bytes.find(base);
+    return it == g_alloc_bytes.end() ? 0 : it->second;
+}
 }  // namespace
+extern "C" void fwh_alloced(const void* p, size_t n) {
+    std::lock_guard<std::mutex> lk(g_alloc_mu);
+    g_alloc_bytes[p] = n;
+}
 extern "C" const char* fwh_violation(void) { return g_violation.c_str(); }
 extern "C" void fwh_violation_reset(void) { g_violation.clear(); }
 
@@ -249,14 +262,38 @@ int launch_ir_convert(hipStream_t, const SampleDesc* samples, int sample, int, f
     touch(dst, sizeof(float) * (size_t)T);
     return 0;
 }
-int launch_fir(hipStream_t, const DevView& v, const FirRow* d_rows, int n_rows, const uint32_t* d_tile_h_off, uint32_t T, float*, size_t, int K,
-               hipEvent_t, hipEvent_t) {
+int launch_fir(hipStream_t, const DevView& v, const FirRow* d_rows, int n_rows, const uint32_t* d_tile_h_off, uint32_t T, float* d_partials,
+               size_t partial_cap_floats, int K, hipEvent_t, hipEvent_t) {
     g_launches[6]++;
     check_view_common(v, K);
     REQUIRE(n_rows >= 1 && n_rows % 32 == 0 && T >= 1, n_rows, (long)T);  // rows padded to 32-row tiles
     touch(d_rows, sizeof(FirRow) * (size_t)n_rows);
     touch(d_tile_h_off, sizeof(uint32_t) * (size_t)(n_rows / 32));
-    for (int t = 0; t < n_rows / 32; ++t) touch(v.ext + d_tile_h_off[t], sizeof(float) * (size_t)T);
+    const size_t ext_floats = alloc_bytes(v.ext) / sizeof(float);
+    REQUIRE(ext_floats > 0, (long)ext_floats);
+    for (int t = 0; t < n_rows / 32; ++t) {
+        touch(v.ext + d_tile_h_off[t], sizeof(float) * (size_t)T);
+        REQUIRE((size_t)d_tile_h_off[t] + T <= ext_floats, t, (long)d_tile_h_off[t]);  // each tile's h lies inside the pool
+    }
+    // k_fir_append / k_fir_gemm: a row's ring is 2R mirrored floats of its node's ext slice, and it must hold every block's window
+    // (T-1 history + the blocks of the batch up to that one) — an R sized for a smaller K than this launch's is silent wrong audio
+    for (int r = 0; r < n_rows; ++r) {
+        const FirRow row = d_rows[r];
+        if (row.state < 0) continue;  // padding row
+        touch(&v.states[row.state], sizeof(NodeState));
+        const NodeState& s = v.states[row.state];
+        const uint64_t R = s.loop_end;
+        REQUIRE(s.loop_start == T, r, (long)s.loop_start);
+        REQUIRE(R >= (uint64_t)T - 1 + (uint64_t)K * (uint64_t)v.frames, r, (long)R);
+        REQUIRE(s.playhead < R, r, (long)s.playhead);
+        REQUIRE(row.ch >= 0 && (uint64_t)(row.ch + 1) * 2 * R <= s.ext_len, r, (long)s.ext_len);
+        REQUIRE((size_t)s.ext_off + s.ext_len <= ext_floats, r, (long)s.ext_off);
+    }
+    // k_fir_gemm writes partials[seg][row][K * n_pad]: the launcher refuses a smaller buffer, so the planner must never size it short
+    const uint32_t W = T - 1u + (uint32_t)v.frames;
+    const size_t n_segs = (W + FIR_SEG - 1) / FIR_SEG, n_pad = (size_t)(v.frames + 255) / 256 * 256;
+    REQUIRE(n_segs * (size_t)n_rows * n_pad * (size_t)K <= partial_cap_floats, (long)partial_cap_floats, K);
+    REQUIRE(partial_cap_floats * sizeof(float) <= alloc_bytes(d_partials), (long)partial_cap_floats, (long)alloc_bytes(d_partials));
     return 0;
 }
 int launch_single_node(hipStream_t, const DevView& v, int node_idx) {
@@ -339,6 +376,10 @@ static LazyBook& lazy_book(const void* key) {
 }
 // (a freed LazyRec table takes its book along: the next context's table may get the same address)
 extern "C" void fwh_freed(const void* p) {
+    {
+        std::lock_guard<std::mutex> lk(g_alloc_mu);
+        g_alloc_bytes.erase(p);
+    }
     std::lock_guard<std::mutex> lk(g_lazy_mu);
     for (int i = 0; i < 64; ++i)
         if (g_lazy_key[i] == p) g_lazy[i] = LazyBook();

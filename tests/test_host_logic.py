@@ -345,6 +345,44 @@ def test_sample_destroy_contract_on_the_host_side():
     assert e.new_sample(PLANAR_F32, 1, np.ones(4, dtype=np.float32)) == ir + 1  # ids are never reused
 
 
+@pytest.mark.parametrize("mbf,kmax,grow,force_generic", [(256, 1, None, False), (100, 1, None, True), (256, 16, None, False),
+                                                         (64, 2, 16, False), (128, 5, 64, True), (1024, 3, 1, False)])
+def test_fir_launch_geometry_holds_for_every_row(mbf, kmax, grow, force_generic):
+    # the launch_fir stub checks what k_fir_append / k_fir_gemm / k_fir_reduce index for every real row: loop_start == T, a ring
+    # R >= T-1 + K*frames (every block's window inside it), playhead < R, the 2R mirrored ring inside the node's ext slice and the
+    # pool, each tile's h inside the pool, and a partials buffer of n_segs * rows * n_pad * K floats — on banks of several
+    # impulse responses and T on both sides of FIR_SEG, on both plans, before and after max_batch changes, on odd call lengths
+    e = HostOnlyEngine(max_block_frames=mbf, max_batch=kmax, force_generic=force_generic)
+    hostonly_lib().fwh_violation_reset()
+    irs = [e.new_sample(PLANAR_F32, ch, np.ones((ch, T), np.float32)) for ch, T in ((2, 1), (2, 4095), (1, 4097), (2, 9000))]
+    m = e.sum(12)
+    for v in range(12):
+        s = e.sampler(100.0)
+        f = e.fir(irs[v % 4])
+        e.connect_stereo(s, f)
+        if v == 11:  # a cascade: the second FIR node sits a level lower, its own launch on the same partials buffer
+            f2 = e.fir(irs[3])
+            e.connect_stereo(f, f2)
+            f = f2
+        e.connect_stereo(f, m, 2 * v)
+    e.connect_stereo(m, e.graph_out_node)
+    e.update()
+    assert e.cx.plan_kind() == (0 if force_generic else 3)
+    e.reset_launches()
+    for frames in (mbf, 3 * mbf + 1, 40 * mbf, 7, 17 * mbf):
+        e.process_interleaved(frames)
+    if grow:
+        e.cx.set_max_batch(grow)
+        e.update()
+        f = e.fir(irs[1])  # a node activated at the new max_batch beside the old ones
+        e.connect_stereo(e.sampler(100.0), f)
+        e.update()
+        for frames in (40 * mbf, mbf + 3, 70 * mbf):
+            e.process_interleaved(frames)
+    assert e.launches()["fir"] > 0
+    assert e.violation() == "", e.violation()
+
+
 def test_graph_edits_keep_the_plan_and_grow_buffers():
     # plug voices into spare leaf ports one at a time: every update recompiles, the fused plan stays
     e = HostOnlyEngine(max_block_frames=64, max_batch=4)

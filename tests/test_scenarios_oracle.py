@@ -190,6 +190,32 @@ def test_fir_spec_matches_f64_convolution():
     assert np.max(np.abs(y - ref) / np.maximum(bound, 1e-30)) < 16 * 2.0 ** -24
 
 
+@pytest.mark.parametrize("taps,frames,blocks", [(9000, 128, 100), (1, 256, 4), (2, 100, 5), (255, 64, 8), (3841, 256, 24),
+                                                (3842, 256, 24), (4096, 100, 60), (4097, 256, 24), (8193, 1024, 12),
+                                                (12289, 256, 60)])
+def test_fir_spec_matches_f64_convolution_in_every_segment(taps, frames, blocks):
+    # the run is longer than the impulse response, so every FIR_SEG segment of the window (and the segment boundaries
+    # W = 4096 / 4097 / one position in the last segment) multiplies data; a flat envelope makes every tap count
+    e = fwapi.OracleEngine(max_block_frames=frames)
+    h = scenarios.reverb_ir(19, taps, 1, decay=1e9)
+    ir = e.new_sample(fwapi.PLANAR_F32, 1, h)
+    n = e.fir(ir, ch=1)
+    e.update()
+    x = fwapi.xorshift_uniform(20 + taps, frames * blocks)
+    x[:29] = 0.0
+    assert x.size > taps + frames
+    y = np.concatenate([e.node_process(n, frames, [x[i:i + frames]], 1)[0][0] for i in range(0, x.size, frames)])
+    L = 1 << int(np.ceil(np.log2(x.size + taps)))
+
+    def conv64(a, b):
+        return np.fft.irfft(np.fft.rfft(a.astype(np.float64), L) * np.fft.rfft(b.astype(np.float64), L), L)[:x.size]
+
+    ref, bound = conv64(x, h[0]), conv64(np.abs(x), np.abs(h[0]))
+    assert not np.any(y[:29].view(np.uint32)), "output before the first nonzero input is not +0.0"
+    err = np.abs(y[29:].astype(np.float64) - ref[29:])
+    assert np.all(err <= 64 * 2.0 ** -24 * bound[29:] + 1e-12 * bound.max()), np.max(err / np.maximum(bound[29:], 1e-30))
+
+
 def rs_table_f64():
     """independent numpy evaluation of the SPEC filter bank: Kaiser(beta 8)-windowed sinc, cutoff 0.9"""
     P, T, fc, beta = 32, 16, 0.9, 8.0
