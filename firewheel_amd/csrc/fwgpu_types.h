@@ -143,6 +143,25 @@ struct VoiceDesc {
                                        //   the second and the third (the stages behind n_pre, in schedule order)
 };
 static_assert(sizeof(VoiceDesc) == 80, "VoiceDesc layout");
+// Plan adoption: is voice `nv` of the new plan the same chain as voice `ov` of the old one, so that its steady cache may travel
+// (k_exchange.hip.h carry_cache_voice; the host harness holds the same function to a statement of its own,
+// tests/host_harness/launch_stubs.cpp check_carry)?  The WHOLE descriptor is compared: a steady cache — "silent", the gain set, the
+// -1.0 sentinel of a stage muted between two filters — means what it means only for one arrangement of stages around the filters,
+// and a list of fields kept by hand had fallen behind the grammar (n_mid: the same nodes with a gain moved across a filter compared
+// equal).  The plan build clears a descriptor before it fills it, so unused stage slots compare equal too.
+#if defined(__HIPCC__)
+#define FW_TYPES_HD __host__ __device__
+#else
+#define FW_TYPES_HD  // (the test harnesses compile the host translation units with plain g++)
+#endif
+FW_TYPES_HD inline bool same_voice_chain(const VoiceDesc& nv, const VoiceDesc& ov) {
+    static_assert(sizeof(VoiceDesc) % sizeof(int) == 0 && alignof(VoiceDesc) == alignof(int), "VoiceDesc: ints only, no padding");
+    const int* const a = (const int*)&nv;
+    const int* const b = (const int*)&ov;
+    bool same = true;
+    for (unsigned i = 0; i < sizeof(VoiceDesc) / sizeof(int); ++i) same = same && a[i] == b[i];
+    return same;
+}
 
 // per (block, voice) record written by the control kernels, read by the leaf kernel (80 B)
 enum : uint32_t {

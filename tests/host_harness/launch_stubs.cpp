@@ -17,8 +17,10 @@ extern "C" void fwh_h2d_reset(void) {
     __atomic_store_n(&fwh_h2d_max_bytes, 0ull, __ATOMIC_RELAXED);
     __atomic_store_n(&fwh_h2d_bytes, 0ull, __ATOMIC_RELAXED);
 }
-namespace fwgpu { extern unsigned long long g_build_applies; }
+namespace fwgpu { extern unsigned long long g_build_applies, g_carried, g_not_carried; }
 extern "C" unsigned long long fwh_build_applies(void) { return fwgpu::g_build_applies; }
+extern "C" unsigned long long fwh_carried(void) { return fwgpu::g_carried; }
+extern "C" unsigned long long fwh_not_carried(void) { return fwgpu::g_not_carried; }
 extern "C" int fwh_quiet_next_call_is_due(unsigned long long now, unsigned long long start, unsigned long long period, unsigned long long dur,
                                           unsigned long long margin) {
     return fwgpu::quiet_next_call_is_due(now, start, period, dur, margin) ? 1 : 0;
@@ -44,6 +46,7 @@ extern "C" void fwh_launch_reset(void) {
 // descriptor invariants the kernels rely on are asserted.  The first violation is kept for the tests (fwh_violation).
 #include <mutex>
 #include <stdio.h>
+#include <string.h>
 
 #include <map>
 #include <string>
@@ -581,6 +584,8 @@ int launch_build_apply(hipStream_t, const BuildJob* jobs, int n_jobs) {
     }
     return 0;
 }
+unsigned long long g_carried = 0, g_not_carried = 0;  // voices of adopted plans that took / did not take their old plan's steady cache along
+static_assert(sizeof(VoiceDesc) == 20 * sizeof(int) && FW_MAX_STAGES == 6, "check_carry names VoiceDesc's fields by position");
 static int check_carry(const CarryArgs& a) {
     if (a.n_new <= 0) return 0;
     VoiceCache* new_cache = a.new_cache;
@@ -595,13 +600,37 @@ static int check_carry(const CarryArgs& a) {
     touch(new_cache, sizeof(VoiceCache) * (size_t)n_new);
     touch(new_voices, sizeof(VoiceDesc) * (size_t)n_new);
     touch(old_slot_voice, sizeof(int) * (size_t)n_old_slots);
-    for (int v = 0; v < n_new; ++v) {  // (the harness runs no kernels: what matters is that every index stays inside its table)
+    // The harness runs no kernels.  What it checks: every index stays inside its table, and — a statement of its own, stricter than
+    // any list of fields — a cache travels only between descriptors that are equal byte for byte.  A steady cache is a function of
+    // the whole chain: which stage sits on which side of which filter decides what "silent" and the gain set mean.  No field of
+    // VoiceDesc may differ legitimately (the plan build clears the struct before it fills it, unused stage slots included), so
+    // nothing is masked here.
+    for (int v = 0; v < n_new; ++v) {
         const int s = new_voices[v].sampler_state;
         if (s < 0 || s >= n_old_slots) continue;
         const int vo = old_slot_voice[s];
         if (vo < 0) continue;
         touch(old_voices + vo, sizeof(VoiceDesc));
         touch(old_cache + vo, sizeof(VoiceCache));
+        if (!same_voice_chain(new_voices[v], old_voices[vo])) {
+            g_not_carried++;
+            continue;
+        }
+        g_carried++;
+        if (memcmp(&new_voices[v], &old_voices[vo], sizeof(VoiceDesc)) != 0) {
+            static const char* const names[sizeof(VoiceDesc) / sizeof(int)] = {
+                "sampler_state", "n_stages", "stage_kind[0]", "stage_kind[1]", "stage_kind[2]", "stage_kind[3]", "stage_kind[4]",
+                "stage_state[0]", "stage_state[1]", "stage_state[2]", "stage_state[3]", "stage_state[4]", "bq_state", "dl_state", "src_kind",
+                "sp_ext_off", "n_pre", "bq2_state", "fx_order", "n_mid"};
+            int nw[sizeof(VoiceDesc) / sizeof(int)], od[sizeof(VoiceDesc) / sizeof(int)];
+            memcpy(nw, &new_voices[v], sizeof(VoiceDesc));
+            memcpy(od, &old_voices[vo], sizeof(VoiceDesc));
+            size_t f = 0;
+            while (nw[f] == od[f]) ++f;
+            char buf[160];
+            snprintf(buf, sizeof(buf), "a steady cache travels between different chains: new voice %d, old voice %d differ in %s", v, vo, names[f]);
+            violation(buf, od[f], nw[f]);
+        }
     }
     return 0;
 }

@@ -509,6 +509,57 @@ def test_control_dispatch_order_and_cache_carry_on_the_host_side():
     assert e.violation() == "", e.violation()
 
 
+def _carry_counts():
+    import ctypes as C
+
+    from fwapi import hostonly_lib
+
+    L = hostonly_lib()
+    L.fwh_carried.restype = L.fwh_not_carried.restype = C.c_ulonglong
+    return int(L.fwh_carried()), int(L.fwh_not_carried())
+
+
+# every "same nodes, other edges" row of test_gpu_rewire's catalogue: a gain stage across a filter, the filter order, two stages swapped
+SAME_NODES_OTHER_EDGES = [("BvD", "BDv"), ("BDv", "BvD"), ("vBD", "BvD"), ("BvD", "vBD"), ("BvB", "BBv"), ("BBv", "BvB"), ("DvB", "DBv"), ("DBv", "DvB"),
+                          ("BcD", "BDc"), ("BDc", "BcD"), ("BD", "DB"), ("DB", "BD"), ("BBD", "DBB"), ("DBB", "BBD"), ("vBDp", "vDBp"), ("vDBp", "vBDp"),
+                          ("vp", "pv"), ("pv", "vp"), ("cv", "vc"), ("vc", "cv")]
+
+
+@pytest.mark.parametrize("before,after", SAME_NODES_OTHER_EDGES)
+def test_a_rewired_voice_leaves_its_steady_cache_behind_and_the_others_take_theirs_along(before, after):
+    """host half (the adoption stub, tests/host_harness/launch_stubs.cpp check_carry, holds fwgpu_types.h same_voice_chain to a stricter
+    statement of its own: a cache travels only between descriptors equal byte for byte).  Voices 1, 4 and 6 of a bank of sounding voices
+    are re-plugged with the SAME nodes in another order: their caches stay behind — a steady cache describes one arrangement of stages
+    around the filters — and every untouched voice's travels: carrying them is why an edit costs the next callback microseconds.
+    (BvD -> BDv: only n_mid tells the two descriptors apart; the comparison this replaced let that cache travel.)"""
+    from fwapi import HostOnlyEngine, hostonly_lib
+    from test_gpu_rewire import build_rewire_bank, move, reshape
+
+    hostonly_lib().fwh_violation_reset()
+    e = HostOnlyEngine(max_block_frames=128, max_batch=8)
+    shapes = [before if i in (1, 4, 6) else sh for i, sh in enumerate(["vB", "", "BD", "v", "", "vp", "", "BvD", "vBD", "pv", "DBv"])]
+    voices, free = build_rewire_bank(e, shapes, radix=6, spare=1, seed=3, delays=(300, 129, 700))
+    for vc in voices:
+        e.sampler_play(vc["sampler"])
+    for _ in range(3):
+        e.process_blocks(4)
+    for i in (1, 4, 6):
+        reshape(e, voices[i], after)
+    c0, n0 = _carry_counts()
+    e.update()
+    e.process_blocks(2)
+    c1, n1 = _carry_counts()
+    assert e.violation() == "", e.violation()
+    assert (n1 - n0, c1 - c0) == (3, len(shapes) - 3), (n1 - n0, c1 - c0)
+    # a voice that moves to another mixer port with its chain as it was IS the same chain: its cache travels with everybody else's
+    move(e, voices[1], free[0])
+    e.update()
+    e.process_blocks(2)
+    c2, n2 = _carry_counts()
+    assert e.violation() == "", e.violation()
+    assert (n2 - n1, c2 - c1) == (0, len(shapes)), (n2 - n1, c2 - c1)
+
+
 def test_plan_builds_go_out_in_pieces_only_while_a_stream_is_live(monkeypatch):
     """round 3, host half (fwgpu_plan_install.cpp, quiet_window / audio_live): a build with no process call in the last 200 ms
     uploads every table whole; a build right after a process call cuts its uploads into pieces of at most FWGPU_UP_PIECE bytes

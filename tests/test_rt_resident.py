@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import scenarios
-from fwapi import LOOP_FULL, LOOP_RANGE_SECS, GpuEngine, OracleEngine
+from fwapi import LOOP_FULL, LOOP_RANGE_SECS, PLANAR_F32, GpuEngine, OracleEngine
 from test_gpu_parity import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -148,6 +148,63 @@ def test_messages_other_sizes_and_edits_end_the_kernel_and_nothing_is_lost():
     launches, doorbells = g.cx.rt_resident_stats()
     if os.environ.get("FWGPU_RT_PERSIST") != "0":
         assert launches >= 4 and doorbells >= 20, (launches, doorbells)   # ended and launched again around every event
+
+
+def test_an_in_place_rewire_between_callbacks_ends_the_kernel_and_nothing_is_lost():
+    """the callback path's share of tests/test_gpu_rewire.py, one block per call under the resident kernel: two sounding voices — one of
+    them muted and settled — get their volume and pan swapped (sampler -> pan -> volume) with the same nodes.  The kernel ends, the next
+    callback adopts the new plan, the two voices leave their steady caches behind and everybody else's travels."""
+    def run(e, rewire=True):
+        # (scenarios.build_voice_bank keeps its mixers to itself: the bank is wired here, 96 voices under three leaf sums of 32)
+        rng = np.random.default_rng(1234)
+        voices, leaves = [], []
+        for v in range(96):
+            if v % 32 == 0:
+                leaves.append(e.sum(32))
+            s, vol, pan = e.sampler(100.0), e.volume(float(rng.uniform(10, 100))), e.pan(float(rng.uniform(-1, 1)))
+            e.connect_stereo(s, vol)
+            e.connect_stereo(vol, pan)
+            e.connect_stereo(pan, leaves[-1], 2 * (v % 32))
+            voices.append((s, vol, pan))
+        root = e.sum(3)
+        for p, m in enumerate(leaves):
+            e.connect_stereo(m, root, 2 * p)
+        e.connect_stereo(root, e.graph_out_node)
+        e.update()
+        for v, (s, _, _) in enumerate(voices):
+            e.sampler_set_sample(s, e.new_sample(PLANAR_F32, 2, scenarios.voice_source(300 + v, 5000, 2)))
+            e.sampler_set_loop_range(s, LOOP_FULL)
+            e.sampler_play(s)
+        outs = []
+        for i in range(46):
+            if i == 6:
+                e.set_param(voices[7][1], 0, 0.0)               # muted, and settled ~21 callbacks later
+            if i == 34 and rewire:
+                for v in (7, 40):
+                    s, vol, pan = voices[v]
+                    for ch in (0, 1):
+                        e.disconnect(s, ch, vol, ch)
+                        e.disconnect(vol, ch, pan, ch)
+                        e.disconnect(pan, ch, leaves[v // 32], 2 * (v % 32) + ch)
+                    e.connect_stereo(s, pan)
+                    e.connect_stereo(pan, vol)
+                    e.connect_stereo(vol, leaves[v // 32], 2 * (v % 32))
+                e.update()
+            if i == 39:
+                e.set_param(voices[7][1], 0, 80.0)
+            outs.append(np.asarray(e.process_interleaved(MBF)))
+        return np.concatenate(outs)
+
+    g, o = GpuEngine(max_block_frames=MBF), OracleEngine(max_block_frames=MBF)
+    out_g, out_o = run(g), run(o)
+    assert g.cx.plan_kind() == 1
+    assert_bits_equal(out_o, out_g, "callbacks around an in-place rewire")
+    plain = run(OracleEngine(max_block_frames=MBF), rewire=False)
+    lo = 34 * MBF * 2
+    assert np.array_equal(out_o[:lo], plain[:lo]) and np.any(out_o[lo:] != plain[lo:])   # the oracle hears the rewire
+    launches, doorbells = g.cx.rt_resident_stats()
+    if os.environ.get("FWGPU_RT_PERSIST") != "0":
+        assert launches >= 3 and doorbells >= 20, (launches, doorbells)
 
 
 @pytest.mark.parametrize("idle_ms,pause_ms", [(1, 0.7), (1, 1.0), (1, 1.4), (2, 2.0)])
