@@ -34,6 +34,10 @@ class SchedNode(C.Structure):
                 ("in_should_clear", C.POINTER(C.c_uint8)), ("out_buffer_index", C.POINTER(u32))]
 
 
+class MeterReading(C.Structure):  # fwgpu_meter_reading: one record per (block, input channel) of a FWGPU_METER node
+    _fields_ = [("peak", f32), ("sum_squares", f32), ("over", u32), ("frames", u32)]
+
+
 # fwgpu_host_process_fn: AudioNodeProcessor::process + ProcInfo as a C callback (FWGPU_HOST_NODE)
 HOST_PROCESS_FN = C.CFUNCTYPE(None, vp, u64, C.POINTER(fp), u32, C.POINTER(fp), u32, u64, C.POINTER(u64), f64, u32)
 
@@ -132,6 +136,7 @@ SIGNATURES = {
     "fwgpu_bus_exchange_status": (ci, [vp, C.POINTER(u64), C.POINTER(u64)]),
     "fwgpu_bus_exchange_wait_stats": (ci, [vp, C.POINTER(u64), u32, ci]),
     "fwgpu_synchronize": (ci, [vp]),
+    "fwgpu_meter_read": (i64, [vp, i64, u64, u32, C.POINTER(MeterReading), C.POINTER(u64)]),
     "fwgpu_node_process": (ci, [vp, i64, u64, C.POINTER(fp), u32, C.POINTER(fp), u32, u64, C.POINTER(u64), f64, u32]),
     "fwgpu_timing_enable": (ci, [vp, ci]),
     "fwgpu_timing_read": (ci, [vp, ci, C.POINTER(f64), C.POINTER(u64)]),

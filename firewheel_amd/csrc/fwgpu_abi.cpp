@@ -1343,6 +1343,38 @@ int fwgpu_synchronize(fwgpu_ctx* c) {
     return 0;
 }
 
+// Level meters (K_METER): the records of blocks [first_block, first_block + n) of `node`, out[i * n_in + c].  Audio side: waits for the
+// ctx stream, then copies from the node's ring in the ext pool (at most two pieces: the ring wraps once).
+int64_t fwgpu_meter_read(fwgpu_ctx* c, int64_t node, uint64_t first_block, uint32_t num_blocks, fwgpu_meter_reading* out, uint64_t* blocks_done) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    AudioCallScope audio;
+    use_device(c);
+    AudioGate gate(c);
+    const uint64_t done = c->blocks_done;
+    if (blocks_done) *blocks_done = done;
+    HIPC(c, hipStreamSynchronize(c->stream));
+    const PlanImage::Meter* m = nullptr;
+    if (c->have_plan)
+        for (const PlanImage::Meter& x : c->meters)
+            if (x.id == node) m = &x;
+    if (!m) return fail(c, FWGPU_ERR_INVALID, "not a meter node of the installed plan");
+    if (num_blocks == 0) return 0;
+    if (!out) return fail(c, FWGPU_ERR_INVALID, "meter_read: null output with blocks requested");
+    if (first_block + (uint64_t)m->ring < done) return fail(c, FWGPU_ERR_INVALID, "meter_read: first_block is older than the ring retains");
+    if (first_block < m->first_block) return fail(c, FWGPU_ERR_INVALID, "meter_read: first_block is older than the meter's first plan");
+    static_assert(sizeof(fwgpu_meter_reading) == sizeof(MeterRec), "fwgpu_meter_reading layout");
+    const uint64_t exist = done > first_block ? done - first_block : 0;
+    const uint32_t n = (uint32_t)std::min<uint64_t>(num_blocks, exist);  // (<= ring: first_block + ring >= done)
+    const MeterRec* ring = (const MeterRec*)(c->d_ext.as<float>() + m->ext_off);
+    const uint32_t s0 = (uint32_t)(first_block % m->ring);
+    const uint32_t n0 = std::min<uint32_t>(n, m->ring - s0);
+    if (n0) HIPC(c, hipMemcpyAsync(out, ring + (size_t)s0 * m->n_in, (size_t)n0 * m->n_in * sizeof(MeterRec), hipMemcpyDeviceToHost, c->stream));
+    if (n > n0)
+        HIPC(c, hipMemcpyAsync(out + (size_t)n0 * m->n_in, ring, (size_t)(n - n0) * m->n_in * sizeof(MeterRec), hipMemcpyDeviceToHost, c->stream));
+    if (n) HIPC(c, hipStreamSynchronize(c->stream));
+    return (int64_t)n;
+}
+
 int fwgpu_node_process(fwgpu_ctx* c, int64_t node, uint64_t frames, const float* const* inputs, uint32_t n_in,
                        float* const* outputs, uint32_t n_out, uint64_t in_mask, uint64_t* out_mask, double, uint32_t) {
     NEED_CTX(c, FWGPU_ERR_INVALID);

@@ -199,6 +199,12 @@ NodeState make_state(int kind, const float* params, int n_params, uint32_t sampl
             s.playhead = 0;
             break;
         }
+        case K_METER: {  // params: ring_blocks (how many blocks of readings the node retains), 1..65536, default 1024
+            const float r = p(0, (float)METER_RING_DEFAULT);
+            // anything else — NaN, a fraction, out of range — leaves 0 here, and the node fails activation at the next update
+            s.loop_end = (r >= 1.0f && r <= (float)METER_RING_MAX && r == floorf(r)) ? (uint64_t)r : 0;
+            break;
+        }
         default:
             break;
     }

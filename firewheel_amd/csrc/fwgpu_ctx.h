@@ -253,6 +253,15 @@ struct PlanImage {
     std::vector<const float*> host_in_ptrs;  // scratch for the callback's pointer tables (sized at install: no allocation per call)
     std::vector<float*> host_out_ptrs;
 
+    // level meters (K_METER) of this plan: where fwgpu_meter_read finds a node's ring.  first_block = the ctx's block count when the
+    // node first became part of an active plan — filled in at adoption, carried from the image before (audio side)
+    struct Meter {
+        int64_t id = 0;
+        uint32_t n_in = 0, ring = 0, ext_off = 0;
+        uint64_t first_block = 0;
+    };
+    std::vector<Meter> meters;
+
     // the steady realtime launch sequence of THIS plan kept as a hipGraph (FWGPU_RT_GRAPH=1)
     struct RtGraph {
         hipGraphExec_t exec = nullptr;
@@ -391,6 +400,8 @@ struct fwgpu_ctx : fwgpu::PlanImage {
     unsigned long long *h_lazy_pub = nullptr, *d_lazy_pub = nullptr;  // pinned {horizon, seq of the control launch it belongs to}
     uint64_t ctl_launch_seq = 0;                 // control kernels launched (with a publish behind each)
     uint64_t abs_blk = 0;                        // blocks the fused voice-bank plan has rendered (any plan image: it only orders)
+    uint64_t blocks_done = 0;                    // blocks processed so far, full or partial, by every process call of any plan: a level
+                                                 // meter's block index (fwgpu_meter_read); audio side
     uint64_t lazy_base_blk = 0;                  // abs_blk right behind the last control run: the LazyRecs' block 0
     uint64_t lazy_pending = 0;                   // blocks rendered from the LazyRecs that node state has not seen yet
     uint32_t lazy_epoch = 0;                     // epoch the LazyRecs were made under

@@ -254,6 +254,13 @@ bool check_activation(int kind, uint32_t n_in, uint32_t n_out, std::string& err)
                 return false;
             }
             return true;
+        case K_METER:  // SPEC: a pass-through (n_out == n_in) or a tap (n_out == 0) over 1..64 channels
+            if (n_in < 1 || n_in > 64 || !(n_out == n_in || n_out == 0)) {
+                err = "MeterNode needs 1..64 inputs and either as many outputs or none. Got num_inputs: " + std::to_string(n_in) +
+                      ", num_outputs: " + std::to_string(n_out);
+                return false;
+            }
+            return true;
         case K_MONO_TO_STEREO:
             if (n_in < 1 || n_out < 2) {
                 err = "MonoToStereoNode needs 1 input and 2 outputs.";

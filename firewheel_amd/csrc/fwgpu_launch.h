@@ -35,6 +35,11 @@ struct DevView {
     // wave that rendered a downstream node's block in registers, read by that node's own wave a level later.  nullptr: no fusion.
     uint32_t* chain_done = nullptr;  // (initialised here: the upper-tree / master-chain / realtime views are filled field by field)
     int chain_words = 0;
+    // level meters (K_METER): the ctx's block count at block 0 of this launch and the launch's block count — block b writes its
+    // records to ring slot (meter_blk0 + b) % R, and only if meter_K - b <= R (a launch longer than the ring keeps its last R
+    // blocks: two waves never meet in a slot).  meter_K = 0: nothing is recorded (fwgpu_node_process).
+    uint64_t meter_blk0 = 0;
+    uint32_t meter_K = 0;
 };
 
 // The compact records are tiled: 32 voices x 8 blocks per 4 KiB tile, [voice % 32][block % 8].  A voice's 8 consecutive blocks

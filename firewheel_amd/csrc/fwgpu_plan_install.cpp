@@ -387,6 +387,7 @@ static void reset_for_build(fwgpu_ctx* c, PlanImage& P) {
     P.slots_cap = 0;
     P.grow_cur_sample.clear();
     P.grow_slot_ids.clear();
+    P.meters.clear();
 }
 
 // what the control kernel writes and the render kernels read, per voice and block of a batch (both fused plans and the hybrid one)
@@ -579,6 +580,10 @@ static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
             len = (size_t)nch * (size_t)n.init.loop_end;
         } else if (n.kind == K_SPATIAL) {
             len = SP_HIST;
+        } else if (n.kind == K_METER) {  // ring[R][n_in] of 16-byte records, zeroed like every slice
+            if (n.init.loop_end < 1 || n.init.loop_end > METER_RING_MAX)
+                return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "MeterNode: ring_blocks must be a whole number in 1..65536");
+            len = (size_t)n.init.loop_end * (size_t)n.n_in * (sizeof(MeterRec) / sizeof(float));
         } else if (n.kind == K_FIR) {
             int ir = n.init.sample;
             if (ir < 0 || ir >= (int)c->samples.size() || !c->samples[ir].alive)
@@ -1137,6 +1142,16 @@ static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
     P.slot_index.assign(c->graph.nodes.size(), -1);
     for (int i = 0; i < N; ++i)
         if (plan.nodes[i].slot < P.slot_index.size()) P.slot_index[plan.nodes[i].slot] = i;
+    for (int i = 0; i < N; ++i)
+        if (plan.nodes[i].kind == K_METER) {
+            const NodeState st = node_init(plan.nodes[i].slot);
+            PlanImage::Meter m;
+            m.id = c->graph.id_of(plan.nodes[i].slot);
+            m.n_in = (uint32_t)plan.nodes[i].n_in;
+            m.ring = (uint32_t)st.loop_end;
+            m.ext_off = st.ext_off;
+            P.meters.push_back(m);
+        }
     P.plan = std::move(plan);  // (nothing below, and no caller, looks at `plan` again: a copy was 33 000 small vectors on config 3)
     P.have_plan = true;
     phase_mark(c, 3);
@@ -1261,6 +1276,12 @@ void adopt_image(fwgpu_ctx* c, PlanImage* n, bool on_audio_thread) {
             c->slot_ids[a.first] = a.second;
         }
     if (c->ret_this_call) finish_returns(c);  // (completion event on the ctx stream: the old plan's kernels are in front of it)
+    // level meters: a node the old plan held keeps the block it was first metered at, a new one starts at the block that comes next
+    for (PlanImage::Meter& m : n->meters) {
+        m.first_block = c->blocks_done;
+        for (const PlanImage::Meter& o : c->meters)
+            if (o.id == m.id) m.first_block = o.first_block;
+    }
     // 4. the swap
     std::swap(static_cast<PlanImage&>(*c), *n);
     std::swap(c->retired_ev, n->retired_ev);  // (the event belongs to the heap object that travels through the ring)

@@ -391,6 +391,8 @@ int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const
     c->lazy_valid = false;  // (the level executor and the hybrid plan move node state their own way)
     if (K == 1) c->rt_path[3]++;
     DevView v = generic_view(c, frames);
+    v.meter_blk0 = c->blocks_done;  // level meters record this batch's blocks
+    v.meter_K = (uint32_t)K;
     // which gain-like stateful nodes cannot change during this batch (their blocks then run in parallel): decided once,
     // before the first level
     if (K > 1 && c->d_frozen.ensure_n("d_frozen", (size_t)c->plan.nodes.size()) == hipSuccess &&
@@ -726,6 +728,8 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
         v.n_cmds = fv.n_cmds;
         v.frozen = nullptr;
         v.frozen_playhead = nullptr;  // (no sampler can sit in a master chain)
+        v.meter_blk0 = c->blocks_done;  // a master meter: one more launch_level below, its K blocks in parallel
+        v.meter_K = (uint32_t)K;
         if (K > 1) {
             LCHK(c, launch_frozen_scan(c->stream, v, c->n_tail, cmd_block0, K, c->d_tail_frozen.as<uint8_t>(),
                                        c->d_tail_frozen.as<unsigned long long>()));
@@ -819,7 +823,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     // steady realtime call: no message on the device, one fused batch, the same output block as last time — every
     // kernel argument repeats (block counters and playheads live in device state), so the launch sequence is replayed
     // from a hipGraph instead of being re-issued kernel by kernel
-    if (stable_out && c->rt_use_graph && can_fuse && !c->timing && c->n_cmds_dev == 0 && frames % mbf == 0 &&
+    if (stable_out && c->rt_use_graph && c->meters.empty() && can_fuse && !c->timing && c->n_cmds_dev == 0 && frames % mbf == 0 &&
         frames / mbf <= (c->fused_fx ? std::min<uint32_t>(c->kmax, CH_FAST_KMAX) : c->kmax)) {
         const uint32_t K = (uint32_t)(frames / mbf);
         fwgpu_ctx::RtGraph& g = c->rt_graph;
@@ -846,6 +850,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
             g.n_out_ch = n_out_ch;
         }
         HIPC(c, hipGraphLaunch(g.exec, c->stream));
+        c->blocks_done += nblocks;
         retire_cmds(c, nblocks);
         return 0;
     }
@@ -858,6 +863,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
             rc = run_fused_batch(c, (int)K, blk, d_out + done * n_out_ch, n_out_ch);
             c->rt_last_batch = false;
             if (rc) return rc;
+            c->blocks_done += K;
             done += (uint64_t)K * mbf;
             blk += K;
             continue;
@@ -867,6 +873,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
         int K = bf == (int)mbf ? (int)std::min<uint64_t>(left / mbf, c->generic_k) : 1;
         rc = run_generic_batch(c, K, bf, blk, d_in ? d_in + done * n_in_ch : nullptr, n_in_ch, d_out + done * n_out_ch, n_out_ch);
         if (rc) return rc;
+        c->blocks_done += (uint64_t)K;
         done += (uint64_t)K * bf;
         blk += K;
     }

@@ -9,8 +9,18 @@ enum : int {
     K_MONO_TO_STEREO = 6, K_STEREO_TO_MONO = 7, K_PAN = 8, K_WIDTH = 9, K_BIQUAD = 10, K_DELAY = 11,
     K_FIR = 12, K_RESAMPLER = 13, K_SPATIAL = 14,
     K_HOST = 15,  // a node the library does not implement: the caller's own AudioNodeProcessor::process, run on the host
-    K_LAST = K_HOST,
+    K_METER = 16,  // SPEC level meter: per block and input channel peak, sum of squares and overs; audio passes through
+    K_LAST = K_METER,
 };
+// K_METER: one record per (block, input channel) — include/fwgpu.h fwgpu_meter_reading, written as ONE 16-byte store.  The node's
+// ext slice is a ring of R x n_in of them (R = NodeState::loop_end); block g of the ctx's block count sits in slot g % R.
+struct MeterRec {
+    float peak, sum_squares;
+    uint32_t over, frames;
+};
+static_assert(sizeof(MeterRec) == 16, "MeterRec layout");
+#define METER_RING_DEFAULT 1024u
+#define METER_RING_MAX 65536u
 #define RS_PHASES 32  // SPEC resampler: polyphase windowed-sinc table [RS_PHASES][RS_TAPS], 32.32 fixed-point position
 #define RS_TAPS 16
 // realtime edge, resident kernel (k_rt_persist): the mailbox in pinned, device-mapped host memory
@@ -63,6 +73,7 @@ struct NodeState {
     //   RESAMPLER: sample = source, playhead = 32.32 source position, loop_start = 32.32 step, has_loop, playing
     //   SPATIAL: p0/p1 = ear gain targets (s0/s1 smooth them), playing = left-ear delay, has_loop = right-ear delay
     //        (frames), ext = the last SP_HIST mono samples
+    //   METER: ext = ring[R][n_in] of MeterRec (4 floats each), loop_end = R (0: the creation parameter was refused)
     uint32_t ext_off;
     uint32_t ext_len;
     int pad[1];

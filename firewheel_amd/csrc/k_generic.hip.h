@@ -126,6 +126,36 @@ __device__ __forceinline__ float beep_step(float ph, float inc) {  // beep_test.
     return t - truncf(t);
 }
 
+// K_METER (SPEC level meter): what a lane keeps per channel, one 16-byte load's worth of a 256-frame chunk, and the
+// reduction over the wave.  Unfused: -ffp-contract=off, one rounding per product and per sum.
+struct MeterAcc {
+    v4f acc = {0.f, 0.f, 0.f, 0.f};
+    float peak = 0.f;
+    uint32_t over = 0u;
+};
+__device__ __forceinline__ void meter_take(MeterAcc& m, const v4f x, const bool live, const int f0, const int frames) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const bool ok = live && f0 + e < frames;  // (frames beyond the block contribute nothing)
+        const float a = fabsf(x[e]);
+        if (ok) {
+            m.acc[e] = m.acc[e] + (x[e] * x[e]);
+            m.peak = fmaxf(m.peak, a);  // (a NaN sample leaves the peak alone)
+        }
+        m.over += (uint32_t)__popcll(__ballot(ok && a > 1.0f));  // (NaN > 1 is false); wave-uniform
+    }
+}
+__device__ __forceinline__ void meter_store(v4f* rec, const MeterAcc& m, const int frames, const int lane) {
+    float t = ((m.acc[0] + m.acc[1]) + m.acc[2]) + m.acc[3];
+    float p = m.peak;
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1) {  // partners add the same two values: every lane ends with the same bits
+        t = t + __shfl_xor(t, h);
+        p = fmaxf(p, __shfl_xor(p, h));
+    }
+    if (lane == 0) *rec = (v4f){p, t, __uint_as_float(m.over), __uint_as_float((uint32_t)frames)};
+}
+
 // node kinds whose audio half carries state from block to block
 __device__ __forceinline__ bool kind_is_stateful(int kind) {
     return kind == K_VOLUME || kind == K_SAMPLER || kind == K_BEEP || kind == K_PAN || kind == K_HARD_CLIP ||
@@ -669,6 +699,48 @@ __device__ void node_process_wave(const DevView& v, int node_idx, uint32_t blk, 
                 const float keep = __shfl(hreg, (SP_HIST + j) & 63);
                 hist[lane] = j >= 0 ? mono(j) : keep;
             }
+            break;
+        }
+
+        case K_METER: if constexpr (SET == 0 || SET == 3) {  // SPEC level meter: out = in, one record per input channel
+            const int n_in = nd.n_in;
+            const bool pass = nd.n_out == n_in;  // (n_out == 0: a tap that only measures)
+            v4f* rec = nullptr;                  // this block's records, or nullptr: not recorded (B1; a block the launch's last R overwrite)
+            if (v.meter_K) {
+                const NodeState& ms = v.states[nd.state];
+                const uint32_t R = (uint32_t)ms.loop_end;
+                if (R && v.meter_K - blk <= R) rec = (v4f*)(v.ext + ms.ext_off) + (size_t)((v.meter_blk0 + blk) % R) * (size_t)n_in;
+            }
+            if (!rec && !pass) break;
+            // two channels at a time, their 16-byte loads in flight together (a master meter is one such pair).  Lane l keeps accumulators
+            // 4l .. 4l+3 of the SPEC's 256: frame i goes to accumulator i % 256, ascending.  A channel flagged silent is not read: zeros
+            // out, {+0, +0, 0, frames}.
+            for (int c0 = 0; c0 < n_in; c0 += 2) {
+                const bool two = c0 + 1 < n_in;
+                const bool live0 = !mask_bit(in_mask, c0), live1 = two && !mask_bit(in_mask, c0 + 1);
+                const float* const in0 = io.in(c0);
+                const float* const in1 = two ? io.in(c0 + 1) : in0;
+                float* const out0 = pass ? io.out(c0) : nullptr;
+                float* const out1 = pass && two ? io.out(c0 + 1) : nullptr;
+                MeterAcc m0, m1;
+                for (int f0 = lane * 4; f0 - lane * 4 < frames; f0 += 256) {  // (every lane makes every trip: the ballots below count the whole wave)
+                    const bool in_block = f0 < frames;
+                    v4f x0 = splat(0.f), x1 = splat(0.f);
+                    if (live0 && in_block) x0 = *(const v4f*)(in0 + f0);
+                    if (live1 && in_block) x1 = *(const v4f*)(in1 + f0);
+                    if (out0 && in_block) *(v4f*)(out0 + f0) = x0;
+                    if (out1 && in_block) *(v4f*)(out1 + f0) = x1;
+                    if (rec) {
+                        meter_take(m0, x0, live0, f0, frames);
+                        if (two) meter_take(m1, x1, live1, f0, frames);
+                    }
+                }
+                if (rec) {
+                    meter_store(rec + c0, m0, frames, lane);
+                    if (two) meter_store(rec + c0 + 1, m1, frames, lane);
+                }
+            }
+            if (pass) out_mask = in_mask;
             break;
         }
 

@@ -295,6 +295,43 @@ class HostNode(_Node):
         cx._check(cx.L.fwgpu_host_node_set_process(cx.c, node_id, self._cb, None))
 
 
+METER_DTYPE = np.dtype([("peak", np.float32), ("sum_squares", np.float32), ("over", np.uint32), ("frames", np.uint32)])  # fwgpu_meter_reading
+
+
+class MeterNode(_Node):
+    """SPEC node: level meter — per block and input channel the peak, the sum of squares and the number of
+    samples over 1.0, measured on the device.  add_node(n, n, MeterNode()) passes the audio through, add_node(n, 0, ...) is a tap.
+    `ring_blocks` (1..65536) = how many blocks of readings the node retains for `read` / FirewheelGpuCtx.meter_read"""
+    KIND = 16
+
+    def __init__(self, ring_blocks=1024):
+        self.ring_blocks = ring_blocks
+
+    def params(self):
+        return [float(self.ring_blocks)]
+
+    def read(self, first_block, num_blocks):
+        return self.cx.meter_read(self.id, first_block, num_blocks)
+
+    @staticmethod
+    def gain_to_db(amp):
+        """core/util.rs gain_to_db: 20 * log10(amp), in f32 (0 -> -inf)"""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (np.float32(20.0) * np.log10(np.asarray(amp, dtype=np.float32))).astype(np.float32)
+
+    @staticmethod
+    def peak_db(readings):
+        return MeterNode.gain_to_db(np.asarray(readings)["peak"])
+
+    @staticmethod
+    def rms_db(readings):
+        """rms = sqrt(sum_squares / frames) through gain_to_db"""
+        r = np.asarray(readings)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rms = np.sqrt(r["sum_squares"] / r["frames"].astype(np.float32), dtype=np.float32)
+        return MeterNode.gain_to_db(rms)
+
+
 class _RawNode(_Node):
     def __init__(self, kind, params):
         self.KIND = kind
@@ -359,6 +396,7 @@ class FirewheelGpuCtx(object):
         nid = self.L.fwgpu_add_node(self.c, node.KIND, num_inputs, num_outputs, _fptr(p), len(p))
         self._check(nid)
         node._bind(self, nid)
+        node._n_in = num_inputs
         self._nodes[nid] = node
         return nid
 
@@ -610,6 +648,25 @@ class FirewheelGpuCtx(object):
 
     def synchronize(self):
         self._check(self.L.fwgpu_synchronize(self.c))
+
+    def meter_read(self, node_id, first_block, num_blocks):
+        """fwgpu_meter_read: (readings, blocks_done) — readings is a structured array [n][n_in] (METER_DTYPE: peak, sum_squares,
+        over, frames) of the blocks [first_block, first_block + n) that exist yet, n <= num_blocks; blocks_done is the ctx's block
+        count.  Waits for the ctx stream.  Raises FwgpuError (-20) for a node that is no meter of the installed plan and for blocks
+        the ring no longer holds; the error carries the block count as `blocks_done`."""
+        n_in = 0
+        node = self._nodes.get(node_id)
+        if node is not None:
+            n_in = getattr(node, "_n_in", 0)
+        buf = np.zeros((max(num_blocks, 1), max(n_in, 1)), dtype=METER_DTYPE)
+        done = C.c_uint64(0)
+        n = self.L.fwgpu_meter_read(self.c, node_id, first_block, num_blocks, buf.ctypes.data_as(C.POINTER(_lib.MeterReading)) if num_blocks and n_in else None,
+                                    C.byref(done))
+        if n < 0:
+            e = FwgpuError(n, self.L.fwgpu_last_error(self.c).decode())
+            e.blocks_done = done.value
+            raise e
+        return buf[:n, :n_in], done.value
 
     # ---- AudioNodeProcessor::process for one node on host buffers (core/node.rs:37-53)
     def node_process(self, node_id, frames, inputs, outputs, in_silence_mask=0, out_silence_mask=0):

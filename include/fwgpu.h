@@ -56,7 +56,8 @@ enum fwgpu_node_kind {
     FWGPU_FIR = 12,           /* SPEC convolution     params: impulse-response sample id (fwgpu_sample_create) */
     FWGPU_RESAMPLER = 13,     /* SPEC polyphase resampling source (0 inputs)  params: sample id, ratio, loop, playing */
     FWGPU_SPATIAL = 14,       /* SPEC 3D spatialiser (1|2 in, 2 out)          params: x, y, z of the source */
-    FWGPU_HOST_NODE = 15      /* any other `dyn AudioNodeProcessor` (graph/processor.rs:243): runs on the HOST, see below */
+    FWGPU_HOST_NODE = 15,     /* any other `dyn AudioNodeProcessor` (graph/processor.rs:243): runs on the HOST, see below */
+    FWGPU_METER = 16          /* SPEC level meter     params: ring_blocks (1..65536, default 1024); see fwgpu_meter_read */
 };
 
 /* sample formats — core/sample_resource.rs:28-335 */
@@ -390,6 +391,40 @@ int fwgpu_bus_allgather_ordered(fwgpu_rccl_comm* comm, const float* d_bus, const
                                 uint8_t* d_out_silence, uint64_t n_floats, uint32_t frames_per_block, uint32_t n_channels);
 const char* fwgpu_rccl_last_error(void);
 int fwgpu_synchronize(fwgpu_ctx* ctx);
+
+/* ---- level meter (FWGPU_METER; SPEC, DESIGN.md section 6: the "decibel meter" of the reference's DESIGN_DOC.md:11-28).  The mix lives in
+ * HBM and the throughput calls never bring audio to the host: a meter node measures a bus ON the device, one 16-byte record per
+ * (block, input channel), and the host fetches only those.  n_in in 1..64; n_out == n_in passes the audio and the silence mask
+ * through bit for bit (a channel flagged silent is zero-filled and flagged, its record reads {+0, +0, 0, frames} without touching the
+ * buffer), n_out == 0 is a tap that only measures; any other shape — and a ring_blocks outside 1..65536, NaN, a fraction — fails
+ * activation at fwgpu_update.  No parameters after creation, no smoother, no messages.
+ *   peak         max |x[i]| over the block's `frames` samples, NaN samples ignored (fmaxf); never negative.
+ *   over         samples with |x[i]| > 1.0f (NaN does not count).
+ *   sum_squares  f32, no FMA, in this fixed order: 256 accumulators acc[j] = +0.0, acc[i % 256] += x[i] * x[i] for i ascending;
+ *                t[l] = ((acc[4l] + acc[4l+1]) + acc[4l+2]) + acc[4l+3] for l in 0..63; then t[l] += t[l + h] for l < h with
+ *                h = 32, 16, 8, 4, 2, 1; the result is t[0].  (The order is part of the numeric SPEC.)
+ *   frames       the block's length: max_block_frames, or less for the short last block of a fwgpu_process_interleaved call.
+ * The ctx counts every block it processes, full or partial, over every process call; block g's records sit in slot g % ring_blocks of
+ * the node's ring, which is zeroed at activation and travels across plan changes like every node state.  One launch covering more
+ * blocks than the ring holds writes only its last ring_blocks.  A 2 -> 2 meter in the master chain (between the root SumNode and
+ * graph_out) leaves the fused plan kind and its lazy calls as they are: it is one more launch per batch; a master chain of any kind
+ * takes one-block calls off the one-launch / resident realtime paths (fwgpu_rt_path_stats paths[2]).  Anywhere else — a leaf bus, a
+ * voice chain, a tap — the level executor renders the meter and the fused plans keep what they can.  Blocks run through
+ * fwgpu_node_process are NOT recorded (that call passes the audio and the mask through and returns). */
+typedef struct fwgpu_meter_reading {
+    float peak;
+    float sum_squares;
+    uint32_t over;
+    uint32_t frames;
+} fwgpu_meter_reading;
+/* Audio-side call, like fwgpu_synchronize: waits for the ctx stream, stores the ctx's block count in *blocks_done (when non-NULL, on
+ * every return that has a valid ctx), copies the records of blocks [first_block, first_block + n) to out[i * n_in + c] and returns n
+ * <= num_blocks: how many of those blocks exist yet.  num_blocks == 0 (out may be NULL) only reports the count.  FWGPU_ERR_INVALID:
+ * `node` is not a meter of the installed plan; first_block + ring_blocks < *blocks_done (older than the ring retains); first_block is
+ * older than the first block the meter was part of a plan for; out == NULL with blocks requested.  Polling from a control thread
+ * without a stream wait is out of scope (it would need a pinned, device-mapped ring). */
+int64_t fwgpu_meter_read(fwgpu_ctx* ctx, int64_t node, uint64_t first_block, uint32_t num_blocks, fwgpu_meter_reading* out,
+                         uint64_t* blocks_done);
 /* ProcInfo::stream_time_secs / stream_status (core/node.rs:111-132) of the most recent fwgpu_process_interleaved call —
  * what a custom node run through fwgpu_node_process inside that call would be handed — and how often the backend has
  * reported StreamStatus::OUTPUT_UNDERFLOW (bit 1) / INPUT_OVERFLOW (bit 0) so far.  Any pointer may be NULL. */

@@ -46,6 +46,15 @@ pub struct fwgpu_sched_node {
     pub in_should_clear: *const u8,
     pub out_buffer_index: *const u32,
 }
+/// one record per (block, input channel) of a FWGPU_METER node (fwgpu_meter_read)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct fwgpu_meter_reading {
+    pub peak: f32,
+    pub sum_squares: f32,
+    pub over: u32,
+    pub frames: u32,
+}
 
 // enum fwgpu_node_kind
 pub const FWGPU_DUMMY: c_int = 0;
@@ -64,6 +73,7 @@ pub const FWGPU_FIR: c_int = 12;
 pub const FWGPU_RESAMPLER: c_int = 13;
 pub const FWGPU_SPATIAL: c_int = 14;
 pub const FWGPU_HOST_NODE: c_int = 15;
+pub const FWGPU_METER: c_int = 16;
 
 // enum fwgpu_sample_format
 pub const FWGPU_INTERLEAVED_I16: c_int = 0;
@@ -163,6 +173,7 @@ extern "C" {
     pub fn fwgpu_bus_allgather_ordered(comm: *mut fwgpu_rccl_comm, d_bus: *const f32, d_silence: *const u8, d_out: *mut f32, d_out_silence: *mut u8, n_floats: u64, frames_per_block: u32, n_channels: u32) -> c_int;
     pub fn fwgpu_rccl_last_error() -> *const c_char;
     pub fn fwgpu_synchronize(ctx: *mut fwgpu_ctx) -> c_int;
+    pub fn fwgpu_meter_read(ctx: *mut fwgpu_ctx, node: i64, first_block: u64, num_blocks: u32, out: *mut fwgpu_meter_reading, blocks_done: *mut u64) -> i64;
     pub fn fwgpu_proc_info(ctx: *mut fwgpu_ctx, stream_time_secs: *mut f64, stream_status: *mut u32, output_underflows: *mut u64, input_overflows: *mut u64) -> c_int;
     pub fn fwgpu_stream_open(ctx: *mut fwgpu_ctx, num_in_channels: u32, num_out_channels: u32) -> *mut fwgpu_stream;
     pub fn fwgpu_stream_close(s: *mut fwgpu_stream);

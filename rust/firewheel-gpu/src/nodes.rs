@@ -466,3 +466,54 @@ impl AudioNode for GpuResamplerNode {
         self.b.deactivate()
     }
 }
+
+/// Level meter (SPEC, DESIGN.md §6 of the fwgpu repository): per block and input channel the peak, the f32 sum of squares and the
+/// number of samples over 1.0, measured on the device.  `num_outputs == num_inputs` passes the audio through, `num_outputs == 0` is a
+/// tap.  Readings are recorded by the whole-graph executor ([`crate::GpuProcessor`], B2); a block run through `fwgpu_node_process`
+/// (B1) passes through unrecorded.
+pub struct GpuMeterNode {
+    b: Binding,
+    ring_blocks: u32,
+    num_inputs: usize,
+}
+/// one record per (block, input channel)
+pub type MeterReading = ffi::fwgpu_meter_reading;
+impl GpuMeterNode {
+    /// `ring_blocks` (1..=65536): how many blocks of readings the node retains
+    pub fn new(cx: &Arc<GpuContext>, ring_blocks: u32) -> Self {
+        Self { b: Binding::new(cx), ring_blocks, num_inputs: 0 }
+    }
+    /// The records of blocks `[first_block, first_block + n)`, `out[i * num_inputs + c]`, for the `n <= num_blocks` of them that exist
+    /// yet, and the context's block count.  Audio-side call: waits for the context's stream.
+    pub fn read(&self, first_block: u64, num_blocks: u32) -> Result<(Vec<MeterReading>, u64), GpuError> {
+        let node = self.b.node.unwrap_or(-1);
+        let mut out = vec![MeterReading::default(); num_blocks as usize * self.num_inputs.max(1)];
+        let mut done: u64 = 0;
+        let n = self.b.cx.check(unsafe { ffi::fwgpu_meter_read(self.b.cx.as_ptr(), node, first_block, num_blocks, out.as_mut_ptr(), &mut done) })?;
+        out.truncate(n as usize * self.num_inputs);
+        Ok((out, done))
+    }
+    /// core/util.rs gain_to_db of a reading's peak
+    pub fn peak_db(r: &MeterReading) -> f32 {
+        firewheel_core::util::gain_to_db(r.peak)
+    }
+    /// ... and of its rms = sqrt(sum_squares / frames)
+    pub fn rms_db(r: &MeterReading) -> f32 {
+        firewheel_core::util::gain_to_db((r.sum_squares / r.frames as f32).sqrt())
+    }
+}
+impl AudioNode for GpuMeterNode {
+    fn debug_name(&self) -> &'static str {
+        "meter"
+    }
+    fn info(&self) -> AudioNodeInfo {
+        io(1, 64, 0, 64, false)
+    }
+    fn activate(&mut self, _sr: u32, _mbf: usize, num_inputs: usize, num_outputs: usize) -> Result<Box<dyn AudioNodeProcessor>, Box<dyn Error>> {
+        self.num_inputs = num_inputs;
+        self.b.activate(ffi::FWGPU_METER, num_inputs, num_outputs, &[self.ring_blocks as f32])
+    }
+    fn deactivate(&mut self, _p: Option<Box<dyn AudioNodeProcessor>>) {
+        self.b.deactivate()
+    }
+}

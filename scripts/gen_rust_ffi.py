@@ -12,7 +12,7 @@ OUT = os.path.join(ROOT, "rust", "firewheel-gpu", "src", "ffi.rs")
 BASE = {"int": "c_int", "uint32_t": "u32", "uint64_t": "u64", "int64_t": "i64", "float": "f32", "double": "f64", "void": "c_void",
         "char": "c_char", "uint8_t": "u8", "size_t": "usize", "fwgpu_ctx": "fwgpu_ctx", "fwgpu_stream": "fwgpu_stream",
         "fwgpu_sched_node": "fwgpu_sched_node", "fwgpu_bus_exchange": "fwgpu_bus_exchange", "fwgpu_rccl_comm": "fwgpu_rccl_comm",
-        "fwgpu_host_process_fn": "fwgpu_host_process_fn"}
+        "fwgpu_host_process_fn": "fwgpu_host_process_fn", "fwgpu_meter_reading": "fwgpu_meter_reading"}
 
 
 def rust_type(c):
@@ -90,6 +90,9 @@ def generate():
     o.append("/// one ScheduledNode of Firewheel's CompiledSchedule (graph/graph/compiler/schedule.rs:12-30)")
     o.append("#[repr(C)]\npub struct fwgpu_sched_node {\n    pub node: i64,\n    pub num_inputs: u32,\n    pub num_outputs: u32,\n"
              "    pub in_buffer_index: *const u32,\n    pub in_should_clear: *const u8,\n    pub out_buffer_index: *const u32,\n}")
+    o.append("/// one record per (block, input channel) of a FWGPU_METER node (fwgpu_meter_read)")
+    o.append("#[repr(C)]\n#[derive(Clone, Copy, Debug, Default, PartialEq)]\npub struct fwgpu_meter_reading {\n    pub peak: f32,\n    pub sum_squares: f32,\n"
+             "    pub over: u32,\n    pub frames: u32,\n}")
     o.append("")
     for ename, items in enums:
         o.append("// enum %s" % ename)
