@@ -133,6 +133,9 @@ struct ProcInfo {
     SilenceMask* out_silence_mask;
     double stream_time_secs;
     uint32_t stream_status;
+    // test switch (not in the reference; FirewheelProcessor::short_blocks): the sampler reads gain.values[0 .. frames) where the
+    // reference's assert_eq! on the gain length (Q5) would panic
+    bool short_blocks = false;
 };
 
 struct AudioNodeProcessor {  // core/node.rs:37-53
@@ -394,6 +397,9 @@ struct FirewheelProcessor {
     // test hook (not in the reference): when set, the silence mask read_graph_outputs hands its closure (schedule.rs:255-287)
     // is appended here once per block — what a shard's partial mix bus carries into the top-level SumNode
     std::vector<uint64_t>* record_out_masks = nullptr;
+    // test switch (not in the reference), off by default: a sampler block with frames != max_block_frames is rendered from the first
+    // `frames` smoothed gain values — what sampler.rs computes below its assert_eq! (Q5) — where the assertion would abort
+    bool short_blocks = false;
     explicit FirewheelProcessor(size_t mbf) : max_block_frames(mbf) {}
     // processor.rs:61-165.  Returns 0 (Ok).
     int process_interleaved(const float* input, size_t input_len, float* output, size_t output_len,

@@ -65,6 +65,7 @@ def oracle_lib():
         sig = {
             "fwo_ctx_new": (vp, [u32, u32, u32, u32]),
             "fwo_ctx_free": (None, [vp]),
+            "fwo_set_short_blocks": (None, [vp, ci]),
             "fwo_last_error": (C.c_char_p, [vp]),
             "fwo_graph_in_node": (i64, [vp]),
             "fwo_graph_out_node": (i64, [vp]),
@@ -197,11 +198,16 @@ class Engine(object):
 class OracleEngine(Engine):
     backend = "oracle"
 
-    def __init__(self, sample_rate=48000, max_block_frames=256, num_graph_inputs=0, num_graph_outputs=2):
+    def __init__(self, sample_rate=48000, max_block_frames=256, num_graph_inputs=0, num_graph_outputs=2, short_blocks=False):
+        """short_blocks: a sampler block with frames != max_block_frames is rendered from the first `frames` smoothed gain values
+        (what sampler.rs computes below its assert_eq!, Q5) where the reference — and this engine by default — panics"""
         self.L = oracle_lib()
         self.sample_rate = sample_rate
         self.max_block_frames = max_block_frames
+        self.short_blocks = bool(short_blocks)
         self.c = self.L.fwo_ctx_new(sample_rate, max_block_frames, num_graph_inputs, num_graph_outputs)
+        if short_blocks:
+            self.L.fwo_set_short_blocks(self.c, 1)
         self._keep = []
 
     def __del__(self):

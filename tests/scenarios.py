@@ -404,6 +404,7 @@ class TaggedOracle(object):
         self.backend = "oracle"
         self.sample_rate = eng.sample_rate
         self.max_block_frames = eng.max_block_frames
+        self.short_blocks = getattr(eng, "short_blocks", False)
 
     def __getattr__(self, name):
         return getattr(self.e, name)
@@ -452,8 +453,26 @@ class TaggedOracle(object):
         return np.concatenate(outs)
 
     def process_interleaved(self, frames, *a, **kw):
-        assert not self.q
-        return self.e.process_interleaved(frames, *a, **kw)
+        if not self.q:
+            return self.e.process_interleaved(frames, *a, **kw)
+        # tagged messages in a call of any length (an engine with short_blocks): block b of the call is its b-th stretch of
+        # max_block_frames frames, the last one may be short — the product's at_block counts the same way
+        assert not a and not kw
+        mbf = self.max_block_frames
+        outs, b = [], 0
+        while frames > 0 or not outs:
+            keep = []
+            for at, fn, args in self.q:
+                if at == b:
+                    fn(*args)
+                elif at > b:
+                    keep.append((at, fn, args))
+            self.q = keep
+            outs.append(self.e.process_interleaved(min(frames, mbf)))
+            frames -= min(frames, mbf)
+            b += 1
+        self.q = [(at - b, fn, args) for at, fn, args in self.q]
+        return np.concatenate(outs)
 
 
 def scenario_hybrid_sends(e, n_a=26, n_b=11, src_frames=2100, seed=5, long_call=40):
