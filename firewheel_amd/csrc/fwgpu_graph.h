@@ -167,7 +167,7 @@ class HostGraph {
     std::vector<HostEdge> edges;
     std::vector<uint32_t> free_edges;
     bool needs_compile = true;
-    bool canonical_order = true;  // build_plan: level by level, slots ascending (FWGPU_PLAN_ORDER=reference: the reference's Kahn order)
+    bool canonical_order = true;  // build_plan: post-order of a depth-first walk from graph_out over the input ports (FWGPU_PLAN_ORDER=reference: the reference's Kahn order)
     std::vector<uint32_t> nodes_to_activate;
 
     HostNode* get(int64_t id);

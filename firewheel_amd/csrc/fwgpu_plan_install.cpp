@@ -4,6 +4,9 @@
 //   build_image   (control thread, may take milliseconds, may allocate, may fail) works out everything a plan needs in a
 //                 PlanImage that no process call can see: tables, pool, voice descriptors, staging areas — and the list of
 //                 things adopting it must do to the state that outlives plans (initial states of new nodes, larger arrays).
+//                 Its steps, over one ImageBuild: size_persistent_state, activate_nodes, choose_launch_plan, write_node_tables,
+//                 plan_host_nodes, plan_fir_banks, size_pool, install_fused_plan | install_hybrid_plan (both through
+//                 install_voice_bank), size_generic_scratch, commit_bookkeeping.  reset_for_build clears; the steps only fill.
 //   publish       hands the image over: adopted at once when no process call is in flight, else left for the next one.
 //   adopt_image   (whoever holds the gate; on the audio thread: a member swap + a handful of asynchronous launches) makes
 //                 the image the active one and sends the old one back.
@@ -322,6 +325,8 @@ static int fill_rows(fwgpu_ctx* c, void* p, size_t row_bytes, size_t pitch, size
     return 0;
 }
 static int zero(fwgpu_ctx* c, void* p, size_t bytes) { return fill_rows(c, p, bytes, bytes, 1, 0); }
+// a table of ints; an empty one goes up as a single 0
+#define up_ints(c, b, v) ((v).empty() ? (v).push_back(0) : (void)0, up(c, b, (v).data(), (v).size() * sizeof(int)))
 
 void PlanImage::release_device() {
     DevBuf* bufs[] = {&d_nodes, &d_in_buf, &d_out_buf, &d_level_nodes, &d_pool, &d_flags, &d_gin_bufs, &d_gout_bufs, &d_groups, &d_blks2, &d_refs2,
@@ -355,6 +360,9 @@ static void reset_for_build(fwgpu_ctx* c, PlanImage& P) {
     P.n_gout_bufs = P.n_gin_bufs = 0;
     P.slot_index.clear();
     P.slot_voice.clear();
+    P.ctl_mark.clear();
+    P.hot_prev.clear();
+    P.hot_now.clear();
     P.ctl_order_live = false;
     P.fused = P.fused_fx = P.ctl_ahead_on = P.fused_rs = P.fused_prog = P.fused_sp = P.hybrid = P.hybrid_fx = P.lazy_capable = false;
     P.generic_k = 1;
@@ -438,11 +446,8 @@ static int alloc_voice_tables(fwgpu_ctx* c, PlanImage& P) {
     }
     HIPC(c, P.d_ctl_order.ensure_n("d_ctl_order", std::max<size_t>(1, (size_t)P.n_voices) * sizeof(int)));
     P.ctl_mark.assign((size_t)P.n_voices, 0);
-    P.hot_prev.clear();
-    P.hot_now.clear();
     P.hot_prev.reserve((size_t)P.n_voices);
     P.hot_now.reserve((size_t)P.n_voices);
-    P.ctl_order_live = false;
     // lazy records: plain voice-bank plans only (the leaf kernel's lazy instantiation knows samplers and gain / program stages)
     // (P.lazy_capable is set by the caller: the voice-bank branch of install_plan, never the hybrid one)
     if (P.lazy_capable && P.n_voices > 0) {
@@ -461,7 +466,6 @@ static int alloc_voice_tables(fwgpu_ctx* c, PlanImage& P) {
 // k_chain workgroups: consecutive leaves packed greedily into groups of <= 32 voices / <= 8 leaves (the voices of
 // consecutive leaves are consecutive), so that a tree of small leaves fills the 32 voice rows
 static int upload_chain_groups(fwgpu_ctx* c, PlanImage& P, const std::vector<LeafDesc>& leaves) {
-    int rc;
     std::vector<ChainGroup> groups;
     for (size_t l = 0; l < leaves.size(); ++l) {
         const LeafDesc& ld = leaves[l];
@@ -489,65 +493,47 @@ static int upload_chain_groups(fwgpu_ctx* c, PlanImage& P, const std::vector<Lea
         g.uniform_ports = uni ? P : 0;
     }
     P.n_groups = (int)groups.size();
-    if ((rc = up(c, P.d_groups, groups.data(), groups.size() * sizeof(ChainGroup)))) return rc;
-    return 0;
+    return up(c, P.d_groups, groups.data(), groups.size() * sizeof(ChainGroup));
 }
 
-// Everything a plan needs, worked out on the control thread in an image no process call can see.  Nothing the audio side reads
-// is written; the control side's own bookkeeping (activated flags, init records, ext_used, ir_cache) is committed only at the
-// very end, when nothing can fail any more — a failure anywhere leaves the ctx exactly as it was and the next fwgpu_update
-// tries the same nodes again (the reference keeps its schedule when a compile fails, context.rs:115-131).
-static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
-    reset_for_build(c, P);
-    c->build_jobs.clear();
-    c->h_up_used = 0;
-    c->h_jobs_used = 0;
-    P.kmax = c->kmax_req;
-    P.gen = ++c->build_gen;
-    phase_mark(c, 21);
-    // 1. node state capacity (persists across recompiles: processor.rs:19,195-197): a larger array is allocated here and
-    //    swapped in — old contents copied over on the ctx stream — when the image is adopted
-    {
-        const size_t need = c->graph.nodes.size();
-        if (need > c->ctl_states_cap) {
-            const size_t cap = std::max<size_t>(need * 2, 4096);
-            HIPC(c, P.grow_states.ensure_n("grow_states", cap * sizeof(NodeState)));
-            int rc0 = zero(c, P.grow_states.p, cap * sizeof(NodeState));
-            if (rc0) return rc0;
-            P.grow_states_cap = cap;
-        }
-        P.slots_cap = std::max<size_t>(need, 1);
-        if (c->cur_sample.size() < need) {  // (control side reads the size only; the audio side swaps the vectors in at adoption)
-            const size_t cap = std::max<size_t>(need * 2, 4096);
-            P.grow_cur_sample.assign(cap, -1);
-            P.grow_slot_ids.assign(cap, -1);
+// ------------------------------------------------------------------------------------------------------------------ the build
+// What the steps of build_image share.  Everything a plan needs is worked out on the control thread in an image no process call
+// can see.  Nothing the audio side reads is written; the control side's own bookkeeping (activated flags, init records, ext_used,
+// ir_cache) is committed only at the very end, when nothing can fail any more — a failure anywhere leaves the ctx exactly as it
+// was (the destructor puts the ext free lists and the generation number back unless commit_bookkeeping disarmed it) and the next
+// fwgpu_update tries the same nodes again (the reference keeps its schedule when a compile fails, context.rs:115-131).
+struct ImageBuild {
+    fwgpu_ctx* c;
+    Plan& plan;
+    PlanImage& P;
+    std::map<size_t, std::vector<uint32_t>> ext_free_backup;  // the guard: put back, and build_gen with it, by the destructor ...
+    bool armed = true;                                        // ... unless commit_bookkeeping disarmed it
+    // step 2: the nodes this image activates
+    std::vector<StateInitHost> inits;                // per new node: slot, init record with its ext slice / FIR ring geometry filled in
+    std::vector<AdoptExtJobHost> ext_jobs;           // per new node with an ext slice: recycled slices zeroed, head floats (coefficients) set
+    std::map<std::pair<int, int>, uint32_t> new_ir;  // impulse responses to convert to f32 -> ext offset
+    size_t ext_need;
+    // the launch plan
+    FusedBuild fb, hb;
+    bool is_fused = false, is_hybrid = false;
+    // step 3: the node tables (nd: the plan's nodes, then the continuation entries of a hybrid plan's split SumNodes)
+    std::vector<NodeDesc> nd;
+    std::vector<int> in_tab, out_tab;
+    std::vector<std::vector<int>> levels;
+    std::vector<int> gin_bufs, gout_bufs, host_nodes;
+    std::vector<int> split_entry;  // plan node -> its continuation entry in nd, -1: not split
+
+    ImageBuild(fwgpu_ctx* c_, Plan& plan_, PlanImage& P_) : c(c_), plan(plan_), P(P_), ext_free_backup(c_->ext_free), ext_need(c_->ext_used) {
+        P.gen = ++c->build_gen;
+    }
+    ~ImageBuild() {
+        if (armed) {
+            c->ext_free = std::move(ext_free_backup);
+            --c->build_gen;
         }
     }
-    phase_mark(c, 22);
-    // 2. activate new nodes (graph.rs:594-612): their initial states and ext-pool slices are worked out here and applied at
-    //    adoption (scatter kernels on the ctx stream), never written into live buffers from this thread
-    struct Act {
-        uint32_t slot;
-        NodeState st;  // the node's init record with its ext slice / FIR ring geometry filled in
-    };
-    std::vector<Act> acts;
-    std::vector<StateInitHost> inits;
-    std::map<std::pair<int, int>, uint32_t> new_ir;                // impulse responses to convert to f32 -> ext offset
-    size_t ext_need = c->ext_used;
-    std::map<size_t, std::vector<uint32_t>> free_backup = c->ext_free;  // restored on failure
-    struct Rollback {  // any return before `armed = false` puts the free lists back
-        fwgpu_ctx* c;
-        std::map<size_t, std::vector<uint32_t>>* backup;
-        uint64_t* gen;
-        bool armed = true;
-        ~Rollback() {
-            if (armed) {
-                c->ext_free = *backup;
-                --*gen;
-            }
-        }
-    } rollback{c, &free_backup, &c->build_gen};
-    auto take_ext = [&](size_t len, uint32_t* off) -> bool {  // recycled slice of exactly this (64-rounded) size, else bump
+
+    bool take_ext(size_t len, uint32_t* off) {  // recycled slice of exactly this (64-rounded) size, else bump
         const size_t rounded = (len + 63) / 64 * 64;
         auto it = c->ext_free.find(rounded);
         if (it != c->ext_free.end() && !it->second.empty()) {
@@ -559,16 +545,50 @@ static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
         *off = (uint32_t)ext_need;
         ext_need += rounded;
         return true;
-    };
-    std::vector<AdoptExtJobHost> ext_jobs;  // per new node with an ext slice: recycled slices zeroed, head floats (coefficients) set
+    }
+    // what the tables need from nodes this image activates (their init records are committed only at the end)
+    NodeState node_init(uint32_t slot) const {
+        for (const StateInitHost& si : inits)
+            if ((uint32_t)si.index == slot) return si.st;
+        return c->graph.nodes[slot].init;
+    }
+    uint32_t ir_off(const std::pair<int, int>& key) const {
+        auto it = new_ir.find(key);
+        return it != new_ir.end() ? it->second : c->ir_cache[key];
+    }
+};
+
+// 1. node state capacity (persists across recompiles: processor.rs:19,195-197): a larger array is allocated here and
+//    swapped in — old contents copied over on the ctx stream — when the image is adopted
+static int size_persistent_state(ImageBuild& b) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
+    const size_t need = c->graph.nodes.size(), cap = std::max<size_t>(need * 2, 4096);
+    if (need > c->ctl_states_cap) {
+        HIPC(c, P.grow_states.ensure_n("grow_states", cap * sizeof(NodeState)));
+        int rc = zero(c, P.grow_states.p, cap * sizeof(NodeState));
+        if (rc) return rc;
+        P.grow_states_cap = cap;
+    }
+    P.slots_cap = std::max<size_t>(need, 1);
+    if (c->cur_sample.size() < need) {  // (control side reads the size only; the audio side swaps the vectors in at adoption)
+        P.grow_cur_sample.assign(cap, -1);
+        P.grow_slot_ids.assign(cap, -1);
+    }
+    return 0;
+}
+// 2. activate new nodes (graph.rs:594-612): their initial states and ext-pool slices are worked out here and applied at
+//    adoption (scatter kernels on the ctx stream), never written into live buffers from this thread
+static int activate_nodes(ImageBuild& b) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
     for (uint32_t slot : c->graph.nodes_to_activate) {
         const HostNode& n = c->graph.nodes[slot];
         if (!n.alive || n.activated) continue;
         if (n.kind == K_HOST && (slot >= c->host_procs.size() || !c->host_procs[slot].fn))
             return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "host node without a process function (fwgpu_host_node_set_process)");
-        Act a;
-        a.slot = slot;
-        a.st = n.init;
+        StateInitHost si;
+        si.index = (int)slot;
+        si.pad = 0;
+        si.st = n.init;
         uint32_t nch = n.n_in < n.n_out ? n.n_in : n.n_out;
         size_t len = 0;
         std::vector<float> head;
@@ -591,90 +611,75 @@ static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
             uint64_t T = c->samples[ir].desc.frames;
             if (T == 0 || T > (1u << 24)) return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "FIR node: 1 <= taps <= 2^24");
             uint64_t R = T - 1 + (uint64_t)P.kmax * c->mbf;  // every block of a K-batch finds its whole window in the ring
-            a.st.loop_start = T;
-            a.st.loop_end = R;
-            a.st.playhead = 0;
+            si.st.loop_start = T;
+            si.st.loop_end = R;
+            si.st.playhead = 0;
             len = (size_t)nch * 2 * (size_t)R;
             for (uint32_t ch = 0; ch < nch; ++ch) {
                 auto key = std::make_pair(ir, (int)std::min<uint32_t>(ch, (uint32_t)c->samples[ir].desc.channels - 1));
-                if (!c->ir_cache.count(key)) new_ir.emplace(key, 0u);  // offset assigned below, once the pool layout is final
+                if (!c->ir_cache.count(key)) b.new_ir.emplace(key, 0u);  // offset assigned below, once the pool layout is final
             }
         }
         if (len) {
-            const size_t before = ext_need;
+            const size_t before = b.ext_need;
             uint32_t off = 0;
-            if (!take_ext(len, &off)) return fail(c, FWGPU_ERR_INVALID, "ext state pool exceeds 2^32 floats");
-            a.st.ext_off = off;
-            a.st.ext_len = (uint32_t)len;
-            AdoptExtJobHost j;
-            memset(&j, 0, sizeof(j));
+            if (!b.take_ext(len, &off)) return fail(c, FWGPU_ERR_INVALID, "ext state pool exceeds 2^32 floats");
+            si.st.ext_off = off;
+            si.st.ext_len = (uint32_t)len;
+            AdoptExtJobHost j{};
             j.off = off;
-            j.zero_len = ext_need == before ? (uint32_t)((len + 63) / 64 * 64) : 0u;  // (a bumped slice is zero already)
+            j.zero_len = b.ext_need == before ? (uint32_t)((len + 63) / 64 * 64) : 0u;  // (a bumped slice is zero already)
             j.n_head = (uint32_t)std::min<size_t>(head.size(), 8);
             for (uint32_t k = 0; k < j.n_head; ++k) j.head[k] = head[k];
-            if (j.zero_len || j.n_head) ext_jobs.push_back(j);
+            if (j.zero_len || j.n_head) b.ext_jobs.push_back(j);
         }
-        StateInitHost si;
-        si.index = (int)slot;
-        si.pad = 0;
-        si.st = a.st;
-        inits.push_back(si);
-        acts.push_back(a);
+        b.inits.push_back(si);
     }
-    for (auto& kv : new_ir) {  // one f32 copy of each impulse-response channel
+    for (auto& kv : b.new_ir) {  // one f32 copy of each impulse-response channel
         uint64_t T = c->samples[kv.first.first].desc.frames;
-        if (ext_need + (T + 63) / 64 * 64 > 0xffffffffull) return fail(c, FWGPU_ERR_INVALID, "ext state pool exceeds 2^32 floats");
-        kv.second = (uint32_t)ext_need;
-        ext_need += (T + 63) / 64 * 64;
-        PlanImage::IrConv ic;
-        ic.sample = kv.first.first;
-        ic.ch = kv.first.second;
-        ic.off = kv.second;
-        ic.T = (uint32_t)T;
-        P.ir_convs.push_back(ic);
+        if (b.ext_need + (T + 63) / 64 * 64 > 0xffffffffull) return fail(c, FWGPU_ERR_INVALID, "ext state pool exceeds 2^32 floats");
+        kv.second = (uint32_t)b.ext_need;
+        b.ext_need += (T + 63) / 64 * 64;
+        P.ir_convs.push_back({kv.first.first, kv.first.second, kv.second, (uint32_t)T});
     }
     int rc;
-    if (ext_need > c->ctl_ext_cap) {
-        const size_t cap = std::max<size_t>(ext_need * 2, 4096);
+    if (b.ext_need > c->ctl_ext_cap) {
+        const size_t cap = std::max<size_t>(b.ext_need * 2, 4096);
         HIPC(c, P.grow_ext.ensure_n("grow_ext", (cap + 256) * sizeof(float)));  // slack: vector loads may overhang the last slice
         if ((rc = zero(c, P.grow_ext.p, (cap + 256) * sizeof(float)))) return rc;
         P.grow_ext_cap = cap;
     }
-    if (!ext_jobs.empty()) {
-        if ((rc = up(c, P.d_ext_jobs, ext_jobs.data(), ext_jobs.size() * sizeof(AdoptExtJobHost)))) return rc;
-        P.n_ext_jobs = (int)ext_jobs.size();
+    if (!b.ext_jobs.empty()) {
+        if ((rc = up(c, P.d_ext_jobs, b.ext_jobs.data(), b.ext_jobs.size() * sizeof(AdoptExtJobHost)))) return rc;
+        P.n_ext_jobs = (int)b.ext_jobs.size();
     }
-    if (!inits.empty()) {
-        if ((rc = up(c, P.d_state_inits, inits.data(), inits.size() * sizeof(StateInitHost)))) return rc;
-        P.n_state_inits = (int)inits.size();
+    if (!b.inits.empty()) {
+        if ((rc = up(c, P.d_state_inits, b.inits.data(), b.inits.size() * sizeof(StateInitHost)))) return rc;
+        P.n_state_inits = (int)b.inits.size();
     }
-    // what the tables below need from nodes this image activates (their init records are committed only at the end)
-    auto node_init = [&](uint32_t slot) -> NodeState {
-        for (const Act& a : acts)
-            if (a.slot == slot) return a.st;
-        return c->graph.nodes[slot].init;
-    };
-    auto ir_off = [&](const std::pair<int, int>& key) -> uint32_t {
-        auto it = new_ir.find(key);
-        return it != new_ir.end() ? it->second : c->ir_cache[key];
-    };
-    // (the launch plans are chosen before the tables are written: a hybrid plan with split SumNodes adds partial buses to the
-    // pool and continuation nodes to the node table)
-    FusedBuild fb, hb;
-    const bool is_fused = !c->force_generic && detect_fused(plan, c->graph, c->mbf, fb);
-    const bool is_hybrid = !is_fused && !c->force_generic && detect_hybrid(plan, c->graph, c->mbf, hb);
-    if (is_hybrid)
-        for (const FusedBuild::Split& sp : hb.splits) {  // a partial bus (two pool buffers) per split SumNode
-            hb.leaves[sp.leaf].out_buf = plan.num_buffers;
-            plan.num_buffers += 2;
+    return 0;
+}
+// (the launch plans are chosen before the tables are written: a hybrid plan with split SumNodes adds partial buses to the
+// pool and continuation nodes to the node table)
+static void choose_launch_plan(ImageBuild& b) {
+    fwgpu_ctx* c = b.c;
+    b.is_fused = !c->force_generic && detect_fused(b.plan, c->graph, c->mbf, b.fb);
+    b.is_hybrid = !b.is_fused && !c->force_generic && detect_hybrid(b.plan, c->graph, c->mbf, b.hb);
+    if (b.is_hybrid)
+        for (const FusedBuild::Split& sp : b.hb.splits) {  // a partial bus (two pool buffers) per split SumNode
+            b.hb.leaves[sp.leaf].out_buf = b.plan.num_buffers;
+            b.plan.num_buffers += 2;
         }
-    phase_mark(c, 23);
-    // 3. node tables
+}
+// 3. node tables
+static int write_node_tables(ImageBuild& b) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
+    const Plan& plan = b.plan;
     const int N = (int)plan.nodes.size();
-    std::vector<NodeDesc> nd(N);
-    std::vector<int> in_tab, out_tab;
-    std::vector<std::vector<int>> levels(plan.num_levels);
-    std::vector<int> gin_bufs, gout_bufs, host_nodes;
+    std::vector<NodeDesc>& nd = b.nd;
+    std::vector<int>&in_tab = b.in_tab, &out_tab = b.out_tab;
+    nd.resize(N);
+    b.levels.resize(plan.num_levels);
     {  // (sized up front: growing these by doubling was a third of this step on config 3)
         size_t n_in = 0;
         std::vector<int> per_level(plan.num_levels, 0);
@@ -684,7 +689,7 @@ static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
         }
         in_tab.reserve(n_in + 64);
         out_tab.reserve((size_t)plan.num_buffers + 64);
-        for (int l = 0; l < plan.num_levels; ++l) levels[l].reserve(per_level[l]);
+        for (int l = 0; l < plan.num_levels; ++l) b.levels[l].reserve(per_level[l]);
     }
     for (int i = 0; i < N; ++i) {
         const PlanNode& p = plan.nodes[i];
@@ -700,10 +705,10 @@ static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
         d.is_graph_io = p.is_graph_io;
         in_tab.insert(in_tab.end(), p.in_buf.begin(), p.in_buf.end());
         out_tab.insert(out_tab.end(), p.out_buf.begin(), p.out_buf.end());
-        if (p.is_graph_io == 1) gin_bufs = p.out_buf;
-        else if (p.is_graph_io == 2) gout_bufs = p.in_buf;
-        else if (p.kind == K_HOST) host_nodes.push_back(i);  // no kernel runs it: the plan is cut at its level (step 3c)
-        else levels[p.level].push_back(i);
+        if (p.is_graph_io == 1) b.gin_bufs = p.out_buf;
+        else if (p.is_graph_io == 2) b.gout_bufs = p.in_buf;
+        else if (p.kind == K_HOST) b.host_nodes.push_back(i);  // no kernel runs it: the plan is cut at its level (step 3c)
+        else b.levels[p.level].push_back(i);
     }
     // vertical fusion of the level executor (k_generic.hip.h fz_links): a stereo sampler or gain-like node whose two output buffers
     // are read by exactly ONE node — a 2 -> 2 volume / pan / width / hard clip, channel for channel — names it in aux0 (+ 1; aux0 is
@@ -713,11 +718,11 @@ static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
         for (int i = 0; i < N; ++i) {
             const PlanNode& p = plan.nodes[i];
             for (int q = 0; q < p.n_in; ++q) {
-                const int b = p.in_buf[q];
-                if (b <= 0 || b >= plan.num_buffers) continue;
-                cnt[b]++;
-                who[b] = i;
-                port[b] = q;
+                const int buf = p.in_buf[q];
+                if (buf <= 0 || buf >= plan.num_buffers) continue;
+                cnt[buf]++;
+                who[buf] = i;
+                port[buf] = q;
             }
         }
         auto gainlike = [](int k) { return k == K_VOLUME || k == K_PAN || k == K_WIDTH || k == K_HARD_CLIP; };
@@ -734,32 +739,28 @@ static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
     }
     // hybrid plan: the continuation of a split SumNode — (partial bus, the ports behind the leading voices) on the path of the
     // node's full port count — as an extra entry behind the plan's nodes; the hybrid level lists name it instead of the node
-    std::vector<int> split_entry(N, -1);
-    if (is_hybrid)
-        for (const FusedBuild::Split& sp : hb.splits) {
+    b.split_entry.assign(N, -1);
+    if (b.is_hybrid)
+        for (const FusedBuild::Split& sp : b.hb.splits) {
             const PlanNode& p = plan.nodes[sp.sum];
             NodeDesc d = nd[sp.sum];
             const int total = p.n_in / 2, rest = total - sp.lead;
             d.in_off = (int)in_tab.size();
             d.n_in = 2 * (1 + rest);
             d.aux0 = (1 + rest) | (total << 16);
-            const int pb = hb.leaves[sp.leaf].out_buf;
+            const int pb = b.hb.leaves[sp.leaf].out_buf;
             in_tab.push_back(pb);
             in_tab.push_back(pb + 1);
             in_tab.insert(in_tab.end(), p.in_buf.begin() + 2 * sp.lead, p.in_buf.end());
-            split_entry[sp.sum] = (int)nd.size();
+            b.split_entry[sp.sum] = (int)nd.size();
             nd.push_back(d);
         }
-    if (in_tab.empty()) in_tab.push_back(0);
-    if (out_tab.empty()) out_tab.push_back(0);
+    int rc;
     if ((rc = up(c, P.d_nodes, nd.data(), nd.size() * sizeof(NodeDesc)))) return rc;
-    if ((rc = up(c, P.d_in_buf, in_tab.data(), in_tab.size() * sizeof(int)))) return rc;
-    if ((rc = up(c, P.d_out_buf, out_tab.data(), out_tab.size() * sizeof(int)))) return rc;
+    if ((rc = up_ints(c, P.d_in_buf, in_tab))) return rc;
+    if ((rc = up_ints(c, P.d_out_buf, out_tab))) return rc;
     std::vector<int> flat;
-    P.level_off.clear();
-    P.level_cnt.clear();
-    P.level_kinds.clear();
-    for (auto& l : levels) {
+    for (auto& l : b.levels) {
         P.level_off.push_back((int)flat.size());
         P.level_cnt.push_back((int)l.size());
         flat.insert(flat.end(), l.begin(), l.end());
@@ -767,410 +768,372 @@ static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
         for (int i : l) kinds |= host_kind_bits(nd[i].kind);
         P.level_kinds.push_back(kinds);
     }
-    if (flat.empty()) flat.push_back(0);
-    if ((rc = up(c, P.d_level_nodes, flat.data(), flat.size() * sizeof(int)))) return rc;
-    P.n_gin_bufs = (int)gin_bufs.size();
-    P.n_gout_bufs = (int)gout_bufs.size();
-    if (gin_bufs.empty()) gin_bufs.push_back(0);
-    if (gout_bufs.empty()) gout_bufs.push_back(0);
-    if ((rc = up(c, P.d_gin_bufs, gin_bufs.data(), gin_bufs.size() * sizeof(int)))) return rc;
-    if ((rc = up(c, P.d_gout_bufs, gout_bufs.data(), gout_bufs.size() * sizeof(int)))) return rc;
-    phase_mark(c, 24);
-    // 3c. host nodes (K_HOST): per level, what the audio side needs to call them — and one pinned, device-mapped staging area
-    //     for their inputs and outputs of a whole K-batch, allocated here (a process call never allocates)
-    {
-        P.host_levels.assign(plan.num_levels, {});
-        P.n_host_nodes = (int)host_nodes.size();
-        P.host_callbacks = 0;
-        size_t floats = 0, flag_bytes = 0, max_in = 1, max_out = 1;
-        for (int i : host_nodes) {
-            const PlanNode& p = plan.nodes[i];
-            PlanImage::HostCall hc;
-            hc.node_idx = i;
-            hc.n_in = p.n_in;
-            hc.n_out = p.n_out;
-            hc.in_off = nd[i].in_off;
-            hc.out_off = nd[i].out_off;
-            hc.fn = p.slot < c->host_procs.size() ? c->host_procs[p.slot].fn : nullptr;
-            hc.user = p.slot < c->host_procs.size() ? c->host_procs[p.slot].user : nullptr;
-            if (!hc.fn) return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "host node without a process function (fwgpu_host_node_set_process)");
-            hc.stage_off = floats;
-            hc.flag_off = flag_bytes;
-            floats += (size_t)P.kmax * (size_t)(p.n_in + p.n_out) * c->stride;
-            flag_bytes += (size_t)P.kmax * (size_t)(p.n_in + p.n_out);
-            max_in = std::max<size_t>(max_in, (size_t)p.n_in);
-            max_out = std::max<size_t>(max_out, (size_t)p.n_out);
-            P.host_levels[p.level].push_back(hc);
-        }
-        if (floats > P.host_stage_floats || flag_bytes > P.host_flag_bytes) {  // (a recycled image keeps its staging area when it is large enough)
-            if (P.h_host_stage) (void)hipHostFree(P.h_host_stage);
-            if (P.h_host_flags) (void)hipHostFree(P.h_host_flags);
-            P.h_host_stage = nullptr;
-            P.h_host_flags = nullptr;
-            P.host_stage_floats = P.host_flag_bytes = 0;
-            void *hs = nullptr, *hf = nullptr, *ds = nullptr, *df = nullptr;
-            HIPC(c, hipHostMalloc(&hs, floats * sizeof(float), hipHostMallocMapped));
-            P.h_host_stage = (float*)hs;
-            HIPC(c, hipHostMalloc(&hf, flag_bytes + 64, hipHostMallocMapped));
-            P.h_host_flags = (uint8_t*)hf;
-            HIPC(c, hipHostGetDevicePointer(&ds, hs, 0));
-            HIPC(c, hipHostGetDevicePointer(&df, hf, 0));
-            P.d_host_stage = (float*)ds;
-            P.d_host_flags = (uint8_t*)df;
-            P.host_stage_floats = floats;
-            P.host_flag_bytes = flag_bytes;
-        }
-        P.host_in_ptrs.assign(max_in, nullptr);
-        P.host_out_ptrs.assign(max_out, nullptr);
+    if ((rc = up_ints(c, P.d_level_nodes, flat))) return rc;
+    P.n_gin_bufs = (int)b.gin_bufs.size();
+    P.n_gout_bufs = (int)b.gout_bufs.size();
+    if ((rc = up_ints(c, P.d_gin_bufs, b.gin_bufs))) return rc;
+    if ((rc = up_ints(c, P.d_gout_bufs, b.gout_bufs))) return rc;
+    return 0;
+}
+// 3c. host nodes (K_HOST): per level, what the audio side needs to call them — and one pinned, device-mapped staging area
+//     for their inputs and outputs of a whole K-batch, allocated here (a process call never allocates)
+static int plan_host_nodes(ImageBuild& b) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
+    P.host_levels.assign(b.plan.num_levels, {});
+    P.n_host_nodes = (int)b.host_nodes.size();
+    size_t floats = 0, flag_bytes = 0, max_in = 1, max_out = 1;
+    for (int i : b.host_nodes) {
+        const PlanNode& p = b.plan.nodes[i];
+        PlanImage::HostCall hc;
+        hc.node_idx = i;
+        hc.n_in = p.n_in;
+        hc.n_out = p.n_out;
+        hc.in_off = b.nd[i].in_off;
+        hc.out_off = b.nd[i].out_off;
+        hc.fn = p.slot < c->host_procs.size() ? c->host_procs[p.slot].fn : nullptr;
+        hc.user = p.slot < c->host_procs.size() ? c->host_procs[p.slot].user : nullptr;
+        if (!hc.fn) return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "host node without a process function (fwgpu_host_node_set_process)");
+        hc.stage_off = floats;
+        hc.flag_off = flag_bytes;
+        floats += (size_t)P.kmax * (size_t)(p.n_in + p.n_out) * c->stride;
+        flag_bytes += (size_t)P.kmax * (size_t)(p.n_in + p.n_out);
+        max_in = std::max<size_t>(max_in, (size_t)p.n_in);
+        max_out = std::max<size_t>(max_out, (size_t)p.n_out);
+        P.host_levels[p.level].push_back(hc);
     }
-    phase_mark(c, 25);
-    // 3b. FIR banks: one GEMM per (level, impulse-response channel)
-    {
-        std::map<std::tuple<int, uint32_t, uint32_t>, std::vector<FirRow>> groups;
-        for (int i = 0; i < N; ++i) {
-            const PlanNode& p = plan.nodes[i];
-            if (p.kind != K_FIR) continue;
-            const NodeState hst = node_init(p.slot);
-            int ir = hst.sample;
-            uint32_t T = (uint32_t)hst.loop_start;
-            int nch = std::min(p.n_in, p.n_out);
-            for (int ch = 0; ch < nch; ++ch) {
-                auto key = std::make_pair(ir, std::min(ch, c->samples[ir].desc.channels - 1));
-                FirRow r;
-                r.state = (int)p.slot;
-                r.ch = ch;
-                r.in_buf = p.in_buf[ch];
-                r.out_buf = p.out_buf[ch];
-                groups[std::make_tuple(p.level, ir_off(key), T)].push_back(r);
-            }
-        }
-        // one launch per (level, T); inside it rows are sorted by impulse-response channel and padded so that
-        // every 32-row tile convolves with a single h (tile_h_off)
-        std::vector<FirRow> flat_rows;
-        std::vector<uint32_t> flat_tiles;
-        P.fir_groups.clear();
-        size_t partial_need = 0;
-        std::map<std::pair<int, uint32_t>, std::vector<std::pair<uint32_t, std::vector<FirRow>*>>> launches;
-        for (auto& g : groups)
-            launches[std::make_pair(std::get<0>(g.first), std::get<2>(g.first))].emplace_back(std::get<1>(g.first), &g.second);
-        for (auto& l : launches) {
-            PlanImage::FirGroup fg;
-            fg.level = l.first.first;
-            fg.T = l.first.second;
-            fg.row_off = (int)flat_rows.size();
-            fg.tile_off = (int)flat_tiles.size();
-            for (auto& part : l.second) {
-                for (const FirRow& r : *part.second) flat_rows.push_back(r);
-                while ((flat_rows.size() - fg.row_off) % 32) {
-                    FirRow pad;
-                    pad.state = -1;
-                    pad.ch = pad.in_buf = pad.out_buf = 0;
-                    flat_rows.push_back(pad);
-                }
-                while (flat_tiles.size() - fg.tile_off < (flat_rows.size() - fg.row_off) / 32) flat_tiles.push_back(part.first);
-            }
-            fg.n_rows = (int)flat_rows.size() - fg.row_off;
-            P.fir_groups.push_back(fg);
-            size_t W = (size_t)fg.T - 1 + c->mbf;
-            size_t segs = (W + FIR_SEG - 1) / FIR_SEG;
-            partial_need = std::max(partial_need, segs * (size_t)fg.n_rows * (size_t)((c->mbf + 255) / 256 * 256) * P.kmax);
-        }
-        if (!flat_rows.empty()) {
-            if ((rc = up(c, P.d_fir_rows, flat_rows.data(), flat_rows.size() * sizeof(FirRow)))) return rc;
-            if ((rc = up(c, P.d_fir_tiles, flat_tiles.data(), flat_tiles.size() * sizeof(uint32_t)))) return rc;
-            HIPC(c, P.d_fir_partials.ensure_n("d_fir_partials", partial_need * sizeof(float)));
+    if (floats > P.host_stage_floats || flag_bytes > P.host_flag_bytes) {  // (a recycled image keeps its staging area when it is large enough)
+        if (P.h_host_stage) (void)hipHostFree(P.h_host_stage);
+        if (P.h_host_flags) (void)hipHostFree(P.h_host_flags);
+        P.h_host_stage = nullptr;
+        P.h_host_flags = nullptr;
+        P.host_stage_floats = P.host_flag_bytes = 0;
+        void *hs = nullptr, *hf = nullptr, *ds = nullptr, *df = nullptr;
+        HIPC(c, hipHostMalloc(&hs, floats * sizeof(float), hipHostMallocMapped));
+        P.h_host_stage = (float*)hs;
+        HIPC(c, hipHostMalloc(&hf, flag_bytes + 64, hipHostMallocMapped));
+        P.h_host_flags = (uint8_t*)hf;
+        HIPC(c, hipHostGetDevicePointer(&ds, hs, 0));
+        HIPC(c, hipHostGetDevicePointer(&df, hf, 0));
+        P.d_host_stage = (float*)ds;
+        P.d_host_flags = (uint8_t*)df;
+        P.host_stage_floats = floats;
+        P.host_flag_bytes = flag_bytes;
+    }
+    P.host_in_ptrs.assign(max_in, nullptr);
+    P.host_out_ptrs.assign(max_out, nullptr);
+    return 0;
+}
+// 3b. FIR banks: one GEMM per (level, impulse-response channel)
+static int plan_fir_banks(ImageBuild& b) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
+    std::map<std::tuple<int, uint32_t, uint32_t>, std::vector<FirRow>> groups;
+    for (const PlanNode& p : b.plan.nodes) {
+        if (p.kind != K_FIR) continue;
+        const NodeState hst = b.node_init(p.slot);
+        int ir = hst.sample;
+        uint32_t T = (uint32_t)hst.loop_start;
+        int nch = std::min(p.n_in, p.n_out);
+        for (int ch = 0; ch < nch; ++ch) {
+            auto key = std::make_pair(ir, std::min(ch, c->samples[ir].desc.channels - 1));
+            FirRow r;
+            r.state = (int)p.slot;
+            r.ch = ch;
+            r.in_buf = p.in_buf[ch];
+            r.out_buf = p.out_buf[ch];
+            groups[std::make_tuple(p.level, b.ir_off(key), T)].push_back(r);
         }
     }
-    phase_mark(c, 26);
-    // 4. buffer pool: a new schedule starts from zeroed buffers (schedule.rs:202-203); one slice per block of a
-    //    generic K-batch.  generic_k: the FIR history rings were sized for the batch size in force when their node was
-    //    activated — a later, larger kmax must not outrun them.
+    // one launch per (level, T); inside it rows are sorted by impulse-response channel and padded so that
+    // every 32-row tile convolves with a single h (tile_h_off)
+    std::vector<FirRow> flat_rows;
+    std::vector<uint32_t> flat_tiles;
+    size_t partial_need = 0;
+    std::map<std::pair<int, uint32_t>, std::vector<std::pair<uint32_t, std::vector<FirRow>*>>> launches;
+    for (auto& g : groups)
+        launches[std::make_pair(std::get<0>(g.first), std::get<2>(g.first))].emplace_back(std::get<1>(g.first), &g.second);
+    for (auto& l : launches) {
+        PlanImage::FirGroup fg;
+        fg.level = l.first.first;
+        fg.T = l.first.second;
+        fg.row_off = (int)flat_rows.size();
+        fg.tile_off = (int)flat_tiles.size();
+        for (auto& part : l.second) {
+            for (const FirRow& r : *part.second) flat_rows.push_back(r);
+            while ((flat_rows.size() - fg.row_off) % 32) {
+                flat_rows.push_back(FirRow{-1, 0, 0, 0});
+            }
+            while (flat_tiles.size() - fg.tile_off < (flat_rows.size() - fg.row_off) / 32) flat_tiles.push_back(part.first);
+        }
+        fg.n_rows = (int)flat_rows.size() - fg.row_off;
+        P.fir_groups.push_back(fg);
+        size_t W = (size_t)fg.T - 1 + c->mbf;
+        size_t segs = (W + FIR_SEG - 1) / FIR_SEG;
+        partial_need = std::max(partial_need, segs * (size_t)fg.n_rows * (size_t)((c->mbf + 255) / 256 * 256) * P.kmax);
+    }
+    if (!flat_rows.empty()) {
+        int rc;
+        if ((rc = up(c, P.d_fir_rows, flat_rows.data(), flat_rows.size() * sizeof(FirRow)))) return rc;
+        if ((rc = up(c, P.d_fir_tiles, flat_tiles.data(), flat_tiles.size() * sizeof(uint32_t)))) return rc;
+        HIPC(c, P.d_fir_partials.ensure_n("d_fir_partials", partial_need * sizeof(float)));
+    }
+    return 0;
+}
+// 4. buffer pool: a new schedule starts from zeroed buffers (schedule.rs:202-203); one slice per block of a
+//    generic K-batch.  generic_k: the FIR history rings were sized for the batch size in force when their node was
+//    activated — a later, larger kmax must not outrun them.
+static int size_pool(ImageBuild& b) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
+    const int num_buffers = b.plan.num_buffers;
     P.generic_k = P.kmax;
-    for (int i = 0; i < N; ++i) {
-        if (plan.nodes[i].kind != K_FIR) continue;
-        const NodeState hst = node_init(plan.nodes[i].slot);
+    for (const PlanNode& p : b.plan.nodes) {
+        if (p.kind != K_FIR) continue;
+        const NodeState hst = b.node_init(p.slot);
         uint64_t room = (hst.loop_end - (hst.loop_start - 1)) / c->mbf;  // (R - (T-1)) / block
         P.generic_k = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(P.generic_k, room));
     }
-    {
-        const size_t Kg = P.generic_k;
-        size_t pool_bytes = Kg * (size_t)plan.num_buffers * c->stride * sizeof(float);
-        HIPC(c, P.d_pool.ensure_n("d_pool", pool_bytes));
-        // buffer 0 of every block is the constant-zero buffer (flagged silent below) and has to BE zero; every other buffer is written
-        // by the node that owns it before anybody reads it (the level order) — the GPU suite passes with FWGPU_POISON=1 filling
-        // fresh pools with 0xCB.  So only those rows are cleared: the whole pool was a 0.5 GB fill per build on config 3, ~100 us of
-        // fill kernel during which the callbacks that ran beside the build took 2-3x as long (fw_edit_race's phase tags).
-        if (plan.num_buffers > 0 && (rc = fill_rows(c, P.d_pool.p, c->stride * sizeof(float), (size_t)plan.num_buffers * c->stride * sizeof(float), Kg, 0))) return rc;
-        // silence flags (the kernels write them): all clear, buffer 0 — constant zero — always flagged silent.  Made on the device:
-        // K x num_buffers bytes were the largest upload of an edit (0.4 of 1.5 MB on config 3)
-        const size_t fl_bytes = Kg * (size_t)plan.num_buffers;
-        HIPC(c, P.d_flags.ensure_n("d_flags", fl_bytes));
-        if (plan.num_buffers > 0 && (rc = fill_rows(c, P.d_flags.p, (size_t)plan.num_buffers, (size_t)plan.num_buffers, Kg, 0, 1))) return rc;
+    int rc;
+    const size_t Kg = P.generic_k;
+    HIPC(c, P.d_pool.ensure_n("d_pool", Kg * (size_t)num_buffers * c->stride * sizeof(float)));
+    // buffer 0 of every block is the constant-zero buffer (flagged silent below) and has to BE zero; every other buffer is written
+    // by the node that owns it before anybody reads it (the level order) — the GPU suite passes with FWGPU_POISON=1 filling
+    // fresh pools with 0xCB.  So only those rows are cleared: the whole pool was a 0.5 GB fill per build on config 3, ~100 us of
+    // fill kernel during which the callbacks that ran beside the build took 2-3x as long (fw_edit_race's phase tags).
+    if (num_buffers > 0 && (rc = fill_rows(c, P.d_pool.p, c->stride * sizeof(float), (size_t)num_buffers * c->stride * sizeof(float), Kg, 0))) return rc;
+    // silence flags (the kernels write them): all clear, buffer 0 — constant zero — always flagged silent.  Made on the device:
+    // K x num_buffers bytes were the largest upload of an edit (0.4 of 1.5 MB on config 3)
+    HIPC(c, P.d_flags.ensure_n("d_flags", Kg * (size_t)num_buffers));
+    if (num_buffers > 0 && (rc = fill_rows(c, P.d_flags.p, (size_t)num_buffers, (size_t)num_buffers, Kg, 0, 1))) return rc;
+    return 0;
+}
+// k_chain's instantiation for a bank: tile = 64*nq frames in bits 0..1 — the larger tile needs whole tiles per block and every
+// delay >= one tile — plus the feature bits of PlanImage::chain_nq
+static int chain_nq_for(uint32_t mbf, const FusedBuild& B) {
+    int nq = (mbf % 128 == 0 && B.min_delay >= 128) ? 2 : 1;
+    if (const char* e = getenv("FWGPU_CHAIN_NQ")) {  // experiments: force the smaller tile
+        if (atoi(e) == 1) nq = 1;
     }
-
-    phase_mark(c, 27);
-    // 5. fused voice-bank plan
-    P.fused = false;
-    P.hybrid = false;
-    P.fused_fx = false;
-    if (is_fused) {
-        P.fused_fx = fb.has_fx;
-        // k_chain tile = 64*nq frames: the larger tile needs whole tiles per block and every delay >= one tile
-        P.chain_nq = (c->mbf % 128 == 0 && fb.min_delay >= 128) ? 2 : 1;
-        if (const char* e = getenv("FWGPU_CHAIN_NQ")) {  // experiments: force the smaller tile
-            if (atoi(e) == 1) P.chain_nq = 1;
-        }
-        for (const VoiceDesc& vd : fb.voices) {  // an EQ cascade somewhere: the instantiation with the second recurrence stage (bit 2); a gain
-            if (vd.bq2_state >= 0) P.chain_nq |= 4;  // stage between two filters or a hard clip: the one with the five-site stage logic (bit 3)
-            if (vd.sampler_state >= 0 && vd.n_mid) P.chain_nq |= 8;
-            for (int j = 0; j < vd.n_stages && vd.sampler_state >= 0; ++j)
-                if (vd.stage_kind[j] == K_HARD_CLIP) P.chain_nq |= 8;
-        }
-        P.n_voices = (int)fb.voices.size();
-        P.n_leaves = (int)fb.leaves.size();
-        P.n_bus = fb.n_bus;
-        P.ramp_slots = 2 * (1 + fb.max_stages);
-        for (VoiceDesc& vd : fb.voices)  // the spatialiser's history slice in the ext pool (its node may be activated by this very plan)
-            if (vd.sp_ext_off >= 0) vd.sp_ext_off = (int)node_init((uint32_t)vd.stage_state[vd.n_stages - 1]).ext_off;
-        P.fused_sp = fb.has_sp;
-        if (fb.has_sp) HIPC(c, P.d_hist.ensure_n("d_hist", fb.voices.size() * SP_HIST * sizeof(float)));
-        build_slot_voice(P, fb.voices);
-        if ((rc = up(c, P.d_slot_voice, P.slot_voice.data(), P.slot_voice.size() * sizeof(int)))) return rc;
-        if ((rc = up(c, P.d_voices, fb.voices.data(), fb.voices.size() * sizeof(VoiceDesc)))) return rc;
-        if ((rc = up(c, P.d_leaves, fb.leaves.data(), fb.leaves.size() * sizeof(LeafDesc)))) return rc;
-        if ((rc = up(c, P.d_progs, fb.progs.data(), fb.progs.size() * sizeof(uint32_t)))) return rc;
-        P.fused_prog = fb.has_prog;
-        P.fused_rs = fb.has_rs;
-        P.n_groups = 0;
-        if (P.fused_fx) {
-            if ((rc = upload_chain_groups(c, P, fb.leaves))) return rc;
-        }
-        const size_t K = P.kmax;
-        // (round 6: chain plans too — k_chain derives its records from the LazyRecs — and resampler banks (k_leaf_rs); spatialiser banks
-        //  keep their control kernel)
-        P.lazy_capable = c->lazy_on && !fb.has_sp && !(fb.has_rs && fb.has_fx);
-        if ((rc = alloc_voice_tables(c, P))) return rc;
-        // (spatialiser stages: their 64-frame history goes from the LAST block of a call to the first block of the next through the ext
-        //  pool; in this mode the copy into the call's scratch is made on the render stream — k_sp_hist_copy — because the control
-        //  kernel runs beside the render kernel that writes it.  A race until the graph fuzz found it at seeds 91, 196, 384.)
-        if (c->ctl_ahead && c->ctl_stream && !P.fused_fx && fb.tail_nodes.empty() && K > 1) {
-            // the second copy of what the control kernel writes and the render kernels read
-            bool ok = P.d_blks2.ensure_n("d_blks2", K * P.n_voices * sizeof(VoiceBlk)) == hipSuccess &&
-                      P.d_refs2.ensure_n("d_refs2", ref_count(P.n_voices, K) * sizeof(VoiceRef)) == hipSuccess &&
-                      P.d_gsets2.ensure_n("d_gsets2", (size_t)P.n_voices * FW_GSETS * sizeof(GainSet)) == hipSuccess &&
-                      P.d_ramps2.ensure_n("d_ramps2", K * P.n_voices * (size_t)P.ramp_slots * c->stride * sizeof(float)) == hipSuccess;
-            if (!ok) (void)hipGetLastError();
-            P.ctl_ahead_on = ok;
-        }
-        size_t bus_bytes = K * (size_t)P.n_bus * c->stride * sizeof(float);
-        HIPC(c, P.d_bus.ensure_n("d_bus", bus_bytes));
-        // bus 0 of every block is the constant-zero bus (flagged silent below) and has to BE zero; every other bus is written by
-        // its leaf / sum / master-chain kernel before anything reads it, as in the pool (step 4): clearing all of it was a 4.4 MB
-        // fill per edit of config 3 — most of what an edit put on the stream
-        if (P.n_bus > 0 && (rc = fill_rows(c, P.d_bus.p, c->stride * sizeof(float), (size_t)P.n_bus * c->stride * sizeof(float), K, 0))) return rc;
-        std::vector<uint8_t> bf(K * P.n_bus, 0);
-        for (size_t k = 0; k < K; ++k) bf[k * P.n_bus] = 1;
-        if ((rc = up(c, P.d_bus_flags, bf.data(), bf.size(), true))) return rc;  // (kernels write flags)
-        if (fb.up_nodes.empty()) {
-            NodeDesc z;
-            memset(&z, 0, sizeof(z));
-            fb.up_nodes.push_back(z);
-        }
-        if (fb.up_in.empty()) fb.up_in.push_back(0);
-        if (fb.up_out.empty()) fb.up_out.push_back(0);
-        if ((rc = up(c, P.d_up_nodes, fb.up_nodes.data(), fb.up_nodes.size() * sizeof(NodeDesc)))) return rc;
-        if ((rc = up(c, P.d_up_in, fb.up_in.data(), fb.up_in.size() * sizeof(int)))) return rc;
-        if ((rc = up(c, P.d_up_out, fb.up_out.data(), fb.up_out.size() * sizeof(int)))) return rc;
-        std::vector<int> uflat;
-        P.up_level_off.clear();
-        P.up_level_cnt.clear();
-        for (auto& l : fb.up_levels) {
-            P.up_level_off.push_back((int)uflat.size());
-            P.up_level_cnt.push_back((int)l.size());
-            uflat.insert(uflat.end(), l.begin(), l.end());
-        }
-        P.up_root_node = (!fb.up_levels.empty() && fb.up_levels.back().size() == 1) ? fb.up_levels.back()[0] : -1;
-        P.n_tail = (int)fb.tail_nodes.size();
-        P.tail_kinds.clear();
-        for (const NodeDesc& t : fb.tail_nodes) P.tail_kinds.push_back(host_kind_bits(t.kind));
-        if (P.n_tail) {
-            P.up_root_node = -1;  // the root's planar result feeds the master chain: no fused root + interleave
-            std::vector<int> idx(P.n_tail);
-            for (int i = 0; i < P.n_tail; ++i) idx[i] = i;
-            if ((rc = up(c, P.d_tail_nodes, fb.tail_nodes.data(), fb.tail_nodes.size() * sizeof(NodeDesc)))) return rc;
-            if ((rc = up(c, P.d_tail_in, fb.tail_in.data(), fb.tail_in.size() * sizeof(int)))) return rc;
-            if ((rc = up(c, P.d_tail_out, fb.tail_out.data(), fb.tail_out.size() * sizeof(int)))) return rc;
-            if ((rc = up(c, P.d_tail_idx, idx.data(), idx.size() * sizeof(int)))) return rc;
-            HIPC(c, P.d_tail_frozen.ensure_n("d_tail_frozen", (size_t)P.n_tail * 16));  // (also a dummy playhead-snapshot area)
-        }
-        if (P.up_root_node >= 0) {
-            const NodeDesc& rn = fb.up_nodes[P.up_root_node];
-            if (rn.n_out == 2 && rn.n_in >= 2 && rn.n_in <= 64 && rn.n_in % 2 == 0) {
-                memset(&P.root_args, 0, sizeof(P.root_args));
-                P.root_args.n_in = rn.n_in;
-                P.root_args.ports = rn.n_in / 2;
-                for (int i = 0; i < rn.n_in; ++i) P.root_args.in_buf[i] = fb.up_in[rn.in_off + i];
-                P.root_args.in_tab = P.d_up_in.as<int>() + rn.in_off;
-            } else {
-                P.up_root_node = -1;
-            }
-        }
-        // the one-launch realtime kernels' way up the mixer tree (k_rt.hip.h): who reads each leaf's / upper node's bus, and how many
-        // connected children each upper node waits for.  Only with a fused root (stereo, no master chain) and a tree in which every
-        // bus has exactly one reader — which detect_fused guarantees; anything unexpected leaves the extents 0: launch sequence.
-        P.rt_tree_leaves = P.rt_tree_up = 0;
-        if (P.up_root_node >= 0 && !fb.leaves.empty() && !is_hybrid) {
-            const int nl = (int)fb.leaves.size(), nu = (int)fb.up_nodes.size();
-            std::vector<int> tree((size_t)nl + 2 * (size_t)nu, -1);
-            int* parent_leaf = tree.data();
-            int* parent_up = tree.data() + nl;
-            int* kids = tree.data() + nl + nu;
-            for (int u = 0; u < nu; ++u) kids[u] = 0;
-            std::vector<int> who((size_t)P.n_bus, -1);  // bus -> leaf i (i) or upper node u (nl + u)
-            for (int i = 0; i < nl; ++i)
-                if (fb.leaves[i].out_buf > 0 && fb.leaves[i].out_buf < P.n_bus) who[fb.leaves[i].out_buf] = i;
-            for (int u = 0; u < nu; ++u) {
-                const int ob = fb.up_out[fb.up_nodes[u].out_off];
-                if (ob > 0 && ob < P.n_bus) who[ob] = nl + u;
-            }
-            bool ok = true;
-            for (int u = 0; u < nu && ok; ++u) {
-                const NodeDesc& nd = fb.up_nodes[u];
-                for (int p = 0; p < nd.n_in; p += 2) {
-                    const int b = fb.up_in[nd.in_off + p];
-                    if (b == 0) continue;  // an unconnected port: the constant-zero bus, nobody arrives for it
-                    const int w = (b > 0 && b < P.n_bus) ? who[b] : -1;
-                    if (w < 0) {
-                        ok = false;
-                        break;
-                    }
-                    int& par = w < nl ? parent_leaf[w] : parent_up[w - nl];
-                    if (par != -1) ok = false;  // a bus with two readers
-                    par = u;
-                    kids[u]++;
-                }
-            }
-            for (int i = 0; i < nl && ok; ++i) ok = parent_leaf[i] >= 0;
-            for (int u = 0; u < nu && ok; ++u) ok = (u == P.up_root_node) ? parent_up[u] == -1 && kids[u] > 0 : parent_up[u] >= 0 && kids[u] > 0;
-            if (ok) {
-                if ((rc = up(c, P.d_rt_tree, tree.data(), tree.size() * sizeof(int)))) return rc;
-                HIPC(c, P.d_rt_tree_sync.ensure_n("d_rt_tree_sync", (size_t)nu * sizeof(unsigned)));
-                if ((rc = zero(c, P.d_rt_tree_sync.p, (size_t)nu * sizeof(unsigned)))) return rc;
-                P.rt_tree_leaves = nl;
-                P.rt_tree_up = nu;
-            }
-        }
-        if (uflat.empty()) uflat.push_back(0);
-        if ((rc = up(c, P.d_up_level_nodes, uflat.data(), uflat.size() * sizeof(int)))) return rc;
-        if ((rc = up(c, P.d_root_bufs, fb.root_buf, sizeof(fb.root_buf)))) return rc;
-        P.fused = true;
-        P.n_fused_real = 0;
-        for (const VoiceDesc& vd : fb.voices) P.n_fused_real += vd.sampler_state >= 0 ? 1 : 0;
+    for (const VoiceDesc& vd : B.voices) {  // an EQ cascade somewhere: the instantiation with the second recurrence stage (bit 2); a gain
+        if (vd.bq2_state >= 0) nq |= 4;     // stage between two filters or a hard clip: the one with the five-site stage logic (bit 3)
+        if (vd.sampler_state >= 0 && vd.n_mid) nq |= 8;
+        for (int j = 0; j < vd.n_stages && vd.sampler_state >= 0; ++j)
+            if (vd.stage_kind[j] == K_HARD_CLIP) nq |= 8;
     }
-    phase_mark(c, 28);
-    // 5b. hybrid plan: not a fused shape as a whole, but with voice banks inside that the fused kernels render
-    // straight into their mixers' pool buffers; the level executor then runs the rest.
-    P.hybrid_fx = false;
-    if (is_hybrid) {
-        P.n_voices = (int)hb.voices.size();
-        P.n_leaves = (int)hb.leaves.size();
-        P.ramp_slots = 2 * (1 + hb.max_stages);
-        P.fused_prog = hb.has_prog;
-        P.fused_rs = hb.has_rs;
-        P.n_groups = 0;
-        P.hybrid_fx = hb.has_fx;
-        if (P.hybrid_fx) {  // the banks go through k_chain: its workgroups, its tile size, at most 64 blocks per launch
-            if ((rc = upload_chain_groups(c, P, hb.leaves))) return rc;
-            P.chain_nq = (c->mbf % 128 == 0 && hb.min_delay >= 128) ? 2 : 1;
-            if (const char* e = getenv("FWGPU_CHAIN_NQ")) {
-                if (atoi(e) == 1) P.chain_nq = 1;
-            }
-            for (const VoiceDesc& vd : hb.voices) {
-                if (vd.bq2_state >= 0) P.chain_nq |= 4;
-                if (vd.sampler_state >= 0 && vd.n_mid) P.chain_nq |= 8;
-                for (int j = 0; j < vd.n_stages && vd.sampler_state >= 0; ++j)
-                    if (vd.stage_kind[j] == K_HARD_CLIP) P.chain_nq |= 8;
-            }
-            P.generic_k = std::min<uint32_t>(P.generic_k, CH_FAST_KMAX);
-        }
-        P.n_tail = 0;
-        P.up_root_node = -1;
-        P.up_level_off.clear();
-        P.up_level_cnt.clear();
-        for (VoiceDesc& vd : hb.voices)
-            if (vd.sp_ext_off >= 0) vd.sp_ext_off = (int)node_init((uint32_t)vd.stage_state[vd.n_stages - 1]).ext_off;
-        P.fused_sp = hb.has_sp;
-        if (hb.has_sp) HIPC(c, P.d_hist.ensure_n("d_hist", hb.voices.size() * SP_HIST * sizeof(float)));
-        build_slot_voice(P, hb.voices);
-        if ((rc = up(c, P.d_slot_voice, P.slot_voice.data(), P.slot_voice.size() * sizeof(int)))) return rc;
-        if ((rc = up(c, P.d_voices, hb.voices.data(), hb.voices.size() * sizeof(VoiceDesc)))) return rc;
-        if ((rc = up(c, P.d_leaves, hb.leaves.data(), hb.leaves.size() * sizeof(LeafDesc)))) return rc;
-        if ((rc = up(c, P.d_progs, hb.progs.data(), hb.progs.size() * sizeof(uint32_t)))) return rc;
-        P.lazy_capable = false;
-        if ((rc = alloc_voice_tables(c, P))) return rc;
-        // the level lists without the nodes the voice-bank kernels render
-        std::vector<char> cov(N, 0);
-        for (int i : hb.covered) cov[i] = 1;
-        std::vector<int> hflat;
-        P.hlevel_off.clear();
-        P.hlevel_cnt.clear();
-        P.hlevel_kinds.clear();
-        for (auto& l : levels) {
-            P.hlevel_off.push_back((int)hflat.size());
-            int kinds = 0, cnt = 0;
-            for (int i : l)
-                if (!cov[i]) {
-                    hflat.push_back(split_entry[i] >= 0 ? split_entry[i] : i);
-                    kinds |= host_kind_bits(nd[i].kind);
-                    cnt++;
-                }
-            P.hlevel_cnt.push_back(cnt);
-            P.hlevel_kinds.push_back(kinds);
-        }
-        if (hflat.empty()) hflat.push_back(0);
-        if ((rc = up(c, P.d_hlevel_nodes, hflat.data(), hflat.size() * sizeof(int)))) return rc;
-        P.hybrid = true;
-        P.n_fused_real = 0;
-        for (const VoiceDesc& vd : hb.voices) P.n_fused_real += vd.sampler_state >= 0 ? 1 : 0;
+    return nq;
+}
+// 5 / 5b, the part the fused and the hybrid plan share: the voice banks' descriptors and the tables the control kernel writes
+// for the render kernels.  What differs between the two sits behind `hybrid`, the rest in their own steps below.
+static int install_voice_bank(ImageBuild& b, FusedBuild& B, bool hybrid) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
+    int rc;
+    P.n_voices = (int)B.voices.size();
+    P.n_leaves = (int)B.leaves.size();
+    P.ramp_slots = 2 * (1 + B.max_stages);
+    P.fused_prog = B.has_prog;
+    P.fused_rs = B.has_rs;
+    P.fused_sp = B.has_sp;
+    (hybrid ? P.hybrid_fx : P.fused_fx) = B.has_fx;
+    // (a fused plan records k_chain's instantiation whether or not its leaves run k_chain; a hybrid one only when its banks do)
+    if (!hybrid || B.has_fx) P.chain_nq = chain_nq_for(c->mbf, B);
+    for (VoiceDesc& vd : B.voices)  // the spatialiser's history slice in the ext pool (its node may be activated by this very plan)
+        if (vd.sp_ext_off >= 0) vd.sp_ext_off = (int)b.node_init((uint32_t)vd.stage_state[vd.n_stages - 1]).ext_off;
+    if (B.has_sp) HIPC(c, P.d_hist.ensure_n("d_hist", B.voices.size() * SP_HIST * sizeof(float)));
+    build_slot_voice(P, B.voices);
+    if ((rc = up(c, P.d_slot_voice, P.slot_voice.data(), P.slot_voice.size() * sizeof(int)))) return rc;
+    if ((rc = up(c, P.d_voices, B.voices.data(), B.voices.size() * sizeof(VoiceDesc)))) return rc;
+    if ((rc = up(c, P.d_leaves, B.leaves.data(), B.leaves.size() * sizeof(LeafDesc)))) return rc;
+    if ((rc = up(c, P.d_progs, B.progs.data(), B.progs.size() * sizeof(uint32_t)))) return rc;
+    if (B.has_fx) {  // the banks go through k_chain: its workgroups
+        if ((rc = upload_chain_groups(c, P, B.leaves))) return rc;
+        // ... and under the level executor at most 64 blocks per launch (step 4 sized the pool uncapped; chain_words follows the cap)
+        if (hybrid) P.generic_k = std::min<uint32_t>(P.generic_k, CH_FAST_KMAX);
     }
-    // k_frozen_scan's verdict tables (generic executor, K > 1): sized here, on the control thread — a process call never
-    // allocates
-    HIPC(c, P.d_frozen.ensure_n("d_frozen", nd.size()));
-    HIPC(c, P.d_frozen_ph.ensure_n("d_frozen_ph", nd.size() * sizeof(unsigned long long)));
+    // lazy records (alloc_voice_tables reads the verdict): never for the banks of a hybrid plan.
+    // (round 6: chain plans too — k_chain derives its records from the LazyRecs — and resampler banks (k_leaf_rs); spatialiser banks
+    //  keep their control kernel)
+    P.lazy_capable = !hybrid && c->lazy_on && !B.has_sp && !(B.has_rs && B.has_fx);
+    if ((rc = alloc_voice_tables(c, P))) return rc;
+    for (const VoiceDesc& vd : B.voices) P.n_fused_real += vd.sampler_state >= 0 ? 1 : 0;
+    return 0;
+}
+// the one-launch realtime kernels' way up the mixer tree (k_rt.hip.h): who reads each leaf's / upper node's bus, and how many
+// connected children each upper node waits for.  Only with a fused root (stereo, no master chain) and a tree in which every
+// bus has exactly one reader — which detect_fused guarantees; anything unexpected leaves the extents 0: launch sequence.
+static int upload_rt_tree(ImageBuild& b) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
+    const FusedBuild& fb = b.fb;
+    if (P.up_root_node < 0 || fb.leaves.empty()) return 0;
+    const int nl = (int)fb.leaves.size(), nu = (int)fb.up_nodes.size();
+    std::vector<int> tree((size_t)nl + 2 * (size_t)nu, -1);
+    int* parent_leaf = tree.data();
+    int* parent_up = tree.data() + nl;
+    int* kids = tree.data() + nl + nu;
+    for (int u = 0; u < nu; ++u) kids[u] = 0;
+    std::vector<int> who((size_t)P.n_bus, -1);  // bus -> leaf i (i) or upper node u (nl + u)
+    for (int i = 0; i < nl; ++i)
+        if (fb.leaves[i].out_buf > 0 && fb.leaves[i].out_buf < P.n_bus) who[fb.leaves[i].out_buf] = i;
+    for (int u = 0; u < nu; ++u) {
+        const int ob = fb.up_out[fb.up_nodes[u].out_off];
+        if (ob > 0 && ob < P.n_bus) who[ob] = nl + u;
+    }
+    bool ok = true;
+    for (int u = 0; u < nu && ok; ++u) {
+        const NodeDesc& un = fb.up_nodes[u];
+        for (int p = 0; p < un.n_in; p += 2) {
+            const int bus = fb.up_in[un.in_off + p];
+            if (bus == 0) continue;  // an unconnected port: the constant-zero bus, nobody arrives for it
+            const int w = (bus > 0 && bus < P.n_bus) ? who[bus] : -1;
+            if (w < 0) {
+                ok = false;
+                break;
+            }
+            int& par = w < nl ? parent_leaf[w] : parent_up[w - nl];
+            if (par != -1) ok = false;  // a bus with two readers
+            par = u;
+            kids[u]++;
+        }
+    }
+    for (int i = 0; i < nl && ok; ++i) ok = parent_leaf[i] >= 0;
+    for (int u = 0; u < nu && ok; ++u) ok = (u == P.up_root_node) ? parent_up[u] == -1 && kids[u] > 0 : parent_up[u] >= 0 && kids[u] > 0;
+    if (!ok) return 0;
+    int rc;
+    if ((rc = up(c, P.d_rt_tree, tree.data(), tree.size() * sizeof(int)))) return rc;
+    HIPC(c, P.d_rt_tree_sync.ensure_n("d_rt_tree_sync", (size_t)nu * sizeof(unsigned)));
+    if ((rc = zero(c, P.d_rt_tree_sync.p, (size_t)nu * sizeof(unsigned)))) return rc;
+    P.rt_tree_leaves = nl;
+    P.rt_tree_up = nu;
+    return 0;
+}
+// 5. fused voice-bank plan: the banks, their buses, the mixer tree above them and the master chain behind its root
+static int install_fused_plan(ImageBuild& b) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
+    FusedBuild& fb = b.fb;
+    int rc;
+    P.n_bus = fb.n_bus;
+    if ((rc = install_voice_bank(b, fb, false))) return rc;
+    const size_t K = P.kmax;
+    // (spatialiser stages: their 64-frame history goes from the LAST block of a call to the first block of the next through the ext
+    //  pool; in this mode the copy into the call's scratch is made on the render stream — k_sp_hist_copy — because the control
+    //  kernel runs beside the render kernel that writes it.  A race until the graph fuzz found it at seeds 91, 196, 384.)
+    if (c->ctl_ahead && c->ctl_stream && !P.fused_fx && fb.tail_nodes.empty() && K > 1) {
+        // the second copy of what the control kernel writes and the render kernels read
+        bool ok = P.d_blks2.ensure_n("d_blks2", K * P.n_voices * sizeof(VoiceBlk)) == hipSuccess &&
+                  P.d_refs2.ensure_n("d_refs2", ref_count(P.n_voices, K) * sizeof(VoiceRef)) == hipSuccess &&
+                  P.d_gsets2.ensure_n("d_gsets2", (size_t)P.n_voices * FW_GSETS * sizeof(GainSet)) == hipSuccess &&
+                  P.d_ramps2.ensure_n("d_ramps2", K * P.n_voices * (size_t)P.ramp_slots * c->stride * sizeof(float)) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        P.ctl_ahead_on = ok;
+    }
+    HIPC(c, P.d_bus.ensure_n("d_bus", K * (size_t)P.n_bus * c->stride * sizeof(float)));
+    // bus 0 of every block is the constant-zero bus (flagged silent below) and has to BE zero; every other bus is written by
+    // its leaf / sum / master-chain kernel before anything reads it, as in the pool (step 4): clearing all of it was a 4.4 MB
+    // fill per edit of config 3 — most of what an edit put on the stream
+    if (P.n_bus > 0 && (rc = fill_rows(c, P.d_bus.p, c->stride * sizeof(float), (size_t)P.n_bus * c->stride * sizeof(float), K, 0))) return rc;
+    std::vector<uint8_t> bf(K * P.n_bus, 0);
+    for (size_t k = 0; k < K; ++k) bf[k * P.n_bus] = 1;
+    if ((rc = up(c, P.d_bus_flags, bf.data(), bf.size(), true))) return rc;  // (kernels write flags)
+    // the upper tree
+    if (fb.up_nodes.empty()) fb.up_nodes.push_back(NodeDesc{});
+    if ((rc = up(c, P.d_up_nodes, fb.up_nodes.data(), fb.up_nodes.size() * sizeof(NodeDesc)))) return rc;
+    if ((rc = up_ints(c, P.d_up_in, fb.up_in))) return rc;
+    if ((rc = up_ints(c, P.d_up_out, fb.up_out))) return rc;
+    std::vector<int> uflat;
+    for (auto& l : fb.up_levels) {
+        P.up_level_off.push_back((int)uflat.size());
+        P.up_level_cnt.push_back((int)l.size());
+        uflat.insert(uflat.end(), l.begin(), l.end());
+    }
+    if ((rc = up_ints(c, P.d_up_level_nodes, uflat))) return rc;
+    if ((rc = up(c, P.d_root_bufs, fb.root_buf, sizeof(fb.root_buf)))) return rc;
+    P.up_root_node = (!fb.up_levels.empty() && fb.up_levels.back().size() == 1) ? fb.up_levels.back()[0] : -1;
+    // the master chain
+    P.n_tail = (int)fb.tail_nodes.size();
+    for (const NodeDesc& t : fb.tail_nodes) P.tail_kinds.push_back(host_kind_bits(t.kind));
+    if (P.n_tail) {
+        P.up_root_node = -1;  // the root's planar result feeds the master chain: no fused root + interleave
+        std::vector<int> idx(P.n_tail);
+        for (int i = 0; i < P.n_tail; ++i) idx[i] = i;
+        if ((rc = up(c, P.d_tail_nodes, fb.tail_nodes.data(), fb.tail_nodes.size() * sizeof(NodeDesc)))) return rc;
+        if ((rc = up(c, P.d_tail_in, fb.tail_in.data(), fb.tail_in.size() * sizeof(int)))) return rc;
+        if ((rc = up(c, P.d_tail_out, fb.tail_out.data(), fb.tail_out.size() * sizeof(int)))) return rc;
+        if ((rc = up(c, P.d_tail_idx, idx.data(), idx.size() * sizeof(int)))) return rc;
+        HIPC(c, P.d_tail_frozen.ensure_n("d_tail_frozen", (size_t)P.n_tail * 16));  // (also a dummy playhead-snapshot area)
+    }
+    if (P.up_root_node >= 0) {  // the fused root's port table (root_args is all zero here)
+        const NodeDesc& rn = fb.up_nodes[P.up_root_node];
+        if (rn.n_out == 2 && rn.n_in >= 2 && rn.n_in <= 64 && rn.n_in % 2 == 0) {
+            P.root_args.n_in = rn.n_in;
+            P.root_args.ports = rn.n_in / 2;
+            for (int i = 0; i < rn.n_in; ++i) P.root_args.in_buf[i] = fb.up_in[rn.in_off + i];
+            P.root_args.in_tab = P.d_up_in.as<int>() + rn.in_off;
+        } else {
+            P.up_root_node = -1;
+        }
+    }
+    if ((rc = upload_rt_tree(b))) return rc;
+    P.fused = true;
+    return 0;
+}
+// 5b. hybrid plan: not a fused shape as a whole, but with voice banks inside that the fused kernels render
+// straight into their mixers' pool buffers; the level executor then runs the rest.  No buses, no upper tree and
+// no master chain of its own: n_bus, n_tail, up_root_node and the up_level lists stay as reset_for_build left them.
+static int install_hybrid_plan(ImageBuild& b) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
+    int rc;
+    if ((rc = install_voice_bank(b, b.hb, true))) return rc;
+    // the level lists without the nodes the voice-bank kernels render
+    std::vector<char> cov(b.plan.nodes.size(), 0);
+    for (int i : b.hb.covered) cov[i] = 1;
+    std::vector<int> hflat;
+    for (auto& l : b.levels) {
+        P.hlevel_off.push_back((int)hflat.size());
+        int kinds = 0, cnt = 0;
+        for (int i : l)
+            if (!cov[i]) {
+                hflat.push_back(b.split_entry[i] >= 0 ? b.split_entry[i] : i);
+                kinds |= host_kind_bits(b.nd[i].kind);
+                cnt++;
+            }
+        P.hlevel_cnt.push_back(cnt);
+        P.hlevel_kinds.push_back(kinds);
+    }
+    if ((rc = up_ints(c, P.d_hlevel_nodes, hflat))) return rc;
+    P.hybrid = true;
+    return 0;
+}
+// k_frozen_scan's verdict tables (generic executor, K > 1): sized here, on the control thread — a process call never
+// allocates; the slot index and the meters' rings
+static int size_generic_scratch(ImageBuild& b) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
+    const Plan& plan = b.plan;
+    const int N = (int)plan.nodes.size();
+    HIPC(c, P.d_frozen.ensure_n("d_frozen", b.nd.size()));
+    HIPC(c, P.d_frozen_ph.ensure_n("d_frozen_ph", b.nd.size() * sizeof(unsigned long long)));
     P.chain_words = (int)((P.generic_k + 31) / 32);
-    HIPC(c, P.d_chain_done.ensure_n("d_chain_done", nd.size() * (size_t)P.chain_words * sizeof(uint32_t)));
+    HIPC(c, P.d_chain_done.ensure_n("d_chain_done", b.nd.size() * (size_t)P.chain_words * sizeof(uint32_t)));
     P.slot_index.assign(c->graph.nodes.size(), -1);
     for (int i = 0; i < N; ++i)
         if (plan.nodes[i].slot < P.slot_index.size()) P.slot_index[plan.nodes[i].slot] = i;
     for (int i = 0; i < N; ++i)
         if (plan.nodes[i].kind == K_METER) {
-            const NodeState st = node_init(plan.nodes[i].slot);
-            PlanImage::Meter m;
-            m.id = c->graph.id_of(plan.nodes[i].slot);
-            m.n_in = (uint32_t)plan.nodes[i].n_in;
-            m.ring = (uint32_t)st.loop_end;
-            m.ext_off = st.ext_off;
-            P.meters.push_back(m);
+            const NodeState st = b.node_init(plan.nodes[i].slot);
+            P.meters.push_back({c->graph.id_of(plan.nodes[i].slot), (uint32_t)plan.nodes[i].n_in, (uint32_t)st.loop_end, st.ext_off, 0});
         }
-    P.plan = std::move(plan);  // (nothing below, and no caller, looks at `plan` again: a copy was 33 000 small vectors on config 3)
-    P.have_plan = true;
-    phase_mark(c, 3);
-    if ((rc = build_apply(c))) return rc;
-    HIPC(c, hipStreamSynchronize(c->up_stream));  // every table and every zeroed pool of the image is in place
-    phase_mark(c, 4);
-    c->h_up_used = 0;
-    // ---- commit the control side's own bookkeeping: from here on the image WILL be adopted
-    for (const Act& a : acts) {
-        HostNode& n = c->graph.nodes[a.slot];
-        n.init = a.st;
+    return 0;
+}
+// ---- commit the control side's own bookkeeping: from here on the image WILL be adopted
+static void commit_bookkeeping(ImageBuild& b) {
+    fwgpu_ctx* c = b.c; PlanImage& P = b.P;
+    for (const StateInitHost& si : b.inits) {
+        HostNode& n = c->graph.nodes[si.index];
+        n.init = si.st;
         n.activated = true;
-        P.activated.emplace_back(a.slot, c->graph.id_of(a.slot));
+        P.activated.emplace_back((uint32_t)si.index, c->graph.id_of((uint32_t)si.index));
     }
-    for (auto& kv : new_ir) {
+    for (auto& kv : b.new_ir) {
         c->ir_cache[kv.first] = kv.second;
         c->ir_len[kv.first] = (uint32_t)c->samples[kv.first.first].desc.frames;
     }
-    c->ext_used = ext_need;
+    c->ext_used = b.ext_need;
     if (P.grow_states.p) c->ctl_states_cap = P.grow_states_cap;
     if (P.grow_ext.p) c->ctl_ext_cap = P.grow_ext_cap;
     c->graph.nodes_to_activate.clear();
@@ -1179,7 +1142,43 @@ static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
     P.removed_slots.swap(c->pending_removed);
     c->pending_removed.clear();
     c->graph.needs_compile = false;
-    rollback.armed = false;
+    b.armed = false;
+}
+// The steps in order (the phase_mark values are what FWGPU_UPDATE_PROF and fw_edit_race's phase tags report)
+static int build_image(fwgpu_ctx* c, Plan& plan, PlanImage& P) {
+    reset_for_build(c, P);
+    c->build_jobs.clear();
+    c->h_up_used = 0;
+    c->h_jobs_used = 0;
+    P.kmax = c->kmax_req;
+    ImageBuild b(c, plan, P);
+    int rc;
+    phase_mark(c, 21);
+    if ((rc = size_persistent_state(b))) return rc;
+    phase_mark(c, 22);
+    if ((rc = activate_nodes(b))) return rc;
+    choose_launch_plan(b);
+    phase_mark(c, 23);
+    if ((rc = write_node_tables(b))) return rc;
+    phase_mark(c, 24);
+    if ((rc = plan_host_nodes(b))) return rc;
+    phase_mark(c, 25);
+    if ((rc = plan_fir_banks(b))) return rc;
+    phase_mark(c, 26);
+    if ((rc = size_pool(b))) return rc;
+    phase_mark(c, 27);
+    if (b.is_fused && (rc = install_fused_plan(b))) return rc;
+    phase_mark(c, 28);
+    if (b.is_hybrid && (rc = install_hybrid_plan(b))) return rc;
+    if ((rc = size_generic_scratch(b))) return rc;
+    P.plan = std::move(plan);  // (nothing below, and no caller, looks at `plan` again: a copy was 33 000 small vectors on config 3)
+    P.have_plan = true;
+    phase_mark(c, 3);
+    if ((rc = build_apply(c))) return rc;
+    HIPC(c, hipStreamSynchronize(c->up_stream));  // every table and every zeroed pool of the image is in place
+    phase_mark(c, 4);
+    c->h_up_used = 0;
+    commit_bookkeeping(b);
     return 0;
 }
 

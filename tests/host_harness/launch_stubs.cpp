@@ -888,3 +888,116 @@ extern "C" int fwh_portints_selftest(void) {
     if (!eq(nodes[0].in_buf, {8, 8}) || nodes[1].in_buf.size() != 70 || nodes[1].in_buf[69] != 6) return 14;
     return 0;
 }
+
+// ---- a digest of the ACTIVE plan image (tests: a recycled image builds what a fresh one builds; a restructured build builds
+// what the old one built).  64-bit FNV-1a, field by field in a fixed order: every scalar and host vector that describes the
+// plan, every table the device only reads (byte length — what the image last uploaded — and the bytes as they sit in "device"
+// memory, which the fake runtime keeps on the host), and of the buffers the kernels write the size the plan requires plus the
+// bytes a build defines (row 0 / the heads of every block, or all of it).  Left out: pointers, capacities, gen, rt_graph and what
+// only adoption reads (grow_*, d_state_inits, d_ext_jobs, ir_convs, activated, dropped_samplers, removed_slots), and the audio
+// side's scratch (ctl_mark, hot_prev / hot_now, d_cache).
+#include "../../firewheel_amd/csrc/fwgpu_ctx.h"
+namespace {
+struct ImageDigest {
+    uint64_t all = 1469598103934665603ull;
+    std::string* fields = nullptr;  // debug form: one "name digest" line per field
+    static uint64_t fnv(uint64_t h, const void* p, size_t n) {
+        for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char*)p)[i]) * 1099511628211ull;
+        return h;
+    }
+    void bytes(const char* name, const void* p, size_t n) {
+        uint64_t h = fnv(1469598103934665603ull, &n, sizeof(n));
+        if (n && !p) h = fnv(h, "null", 4);
+        else h = fnv(h, p, n);
+        all = fnv(all, &h, sizeof(h));
+        if (fields) {
+            char line[160];
+            snprintf(line, sizeof(line), "%s %016llx\n", name, (unsigned long long)h);
+            *fields += line;
+        }
+    }
+    template <class T>
+    void val(const char* name, T v) { bytes(name, &v, sizeof(v)); }
+    template <class T>
+    void vec(const char* name, const std::vector<T>& v) { bytes(name, v.data(), v.size() * sizeof(T)); }
+    void table(const char* name, const DevBuf& b, bool used) { bytes(name, b.p, used ? b.shadow.size() : 0); }
+    // rows x row_bytes at a pitch
+    void rows(const char* name, const DevBuf& b, size_t required, size_t row_bytes, size_t pitch, size_t n_rows) {
+        std::vector<unsigned char> flat;
+        for (size_t r = 0; b.p && r < n_rows; ++r) flat.insert(flat.end(), (unsigned char*)b.p + r * pitch, (unsigned char*)b.p + r * pitch + row_bytes);
+        flat.insert(flat.end(), (unsigned char*)&required, (unsigned char*)&required + sizeof(required));
+        bytes(name, flat.data(), flat.size());
+    }
+    void image(const fwgpu_ctx* c) {
+        const PlanImage& P = *c;
+#define V(f) val(#f, P.f)
+#define VEC(f) vec(#f, P.f)
+#define TAB(f, used) table(#f, P.f, used)
+        std::vector<int> pl;
+        pl.push_back(P.plan.num_buffers);
+        pl.push_back(P.plan.num_levels);
+        for (const PlanNode& n : P.plan.nodes) {
+            for (int x : {(int)n.slot, n.kind, n.n_in, n.n_out, n.level, n.is_graph_io}) pl.push_back(x);
+            for (const PortInts* pi : {&n.in_buf, &n.out_buf, &n.in_src_node, &n.in_src_port}) {
+                pl.push_back((int)pi->size());
+                pl.insert(pl.end(), pi->data(), pi->data() + pi->size());
+            }
+        }
+        vec("plan", pl);
+        V(have_plan), V(kmax), VEC(level_off), VEC(level_cnt), VEC(level_kinds), V(n_gout_bufs), V(n_gin_bufs), VEC(slot_index);
+        V(fused), V(generic_k), V(fused_fx), V(chain_nq), V(n_voices), V(n_leaves), V(n_bus), V(ramp_slots), V(n_groups), V(ctl_ahead_on);
+        V(fused_rs), V(fused_prog), V(fused_sp), VEC(slot_voice), V(ctl_order_live), V(lazy_capable);
+        VEC(up_level_off), VEC(up_level_cnt), V(n_tail), VEC(tail_kinds), V(rt_tree_leaves), V(rt_tree_up), V(chain_words), V(up_root_node);
+        V(root_args.n_in), V(root_args.ports), bytes("root_args.in_buf", P.root_args.in_buf, sizeof(P.root_args.in_buf));
+        VEC(fir_groups);  // (five 4-byte members: no padding)
+        V(n_fused_real), V(hybrid), V(hybrid_fx), VEC(hlevel_off), VEC(hlevel_cnt), VEC(hlevel_kinds);
+        std::vector<size_t> hl;
+        for (const auto& l : P.host_levels) {
+            hl.push_back(l.size());
+            for (const PlanImage::HostCall& h : l)
+                for (size_t x : {(size_t)h.node_idx, (size_t)h.n_in, (size_t)h.n_out, (size_t)h.in_off, (size_t)h.out_off, h.stage_off, h.flag_off}) hl.push_back(x);
+        }
+        val("host_levels.size", P.host_levels.size()), vec("host_levels", hl), V(n_host_nodes), V(host_callbacks);
+        val("host_in_ptrs.size", P.host_in_ptrs.size()), val("host_out_ptrs.size", P.host_out_ptrs.size());
+        std::vector<int64_t> mt;
+        for (const PlanImage::Meter& m : P.meters)
+            for (int64_t x : {m.id, (int64_t)m.n_in, (int64_t)m.ring, (int64_t)m.ext_off}) mt.push_back(x);
+        vec("meters", mt), V(slots_cap);
+        // tables the device only reads: those of the plan kind in force (a recycled image keeps the others' buffers, unread)
+        const bool bank = P.fused || P.hybrid;
+        TAB(d_nodes, true), TAB(d_in_buf, true), TAB(d_out_buf, true), TAB(d_level_nodes, true), TAB(d_gin_bufs, true), TAB(d_gout_bufs, true);
+        TAB(d_slot_voice, bank), TAB(d_voices, bank), TAB(d_leaves, bank), TAB(d_progs, bank), TAB(d_groups, bank && (P.fused_fx || P.hybrid_fx));
+        TAB(d_up_nodes, P.fused), TAB(d_up_in, P.fused), TAB(d_up_out, P.fused), TAB(d_up_level_nodes, P.fused), TAB(d_root_bufs, P.fused);
+        TAB(d_tail_nodes, P.fused && P.n_tail), TAB(d_tail_in, P.fused && P.n_tail), TAB(d_tail_out, P.fused && P.n_tail), TAB(d_tail_idx, P.fused && P.n_tail);
+        TAB(d_rt_tree, P.fused && P.rt_tree_up), TAB(d_hlevel_nodes, P.hybrid), TAB(d_fir_rows, !P.fir_groups.empty()), TAB(d_fir_tiles, !P.fir_groups.empty());
+        // buffers the kernels write: required size, the bytes a build defines
+        const size_t nb = (size_t)P.plan.num_buffers, row = (size_t)c->stride * sizeof(float), K = P.kmax, nv = (size_t)P.n_voices;
+        rows("d_pool", P.d_pool, P.generic_k * nb * row, row, nb * row, nb ? P.generic_k : 0);
+        rows("d_flags", P.d_flags, P.generic_k * nb, P.generic_k * nb, 0, 1);
+        rows("d_bus", P.d_bus, P.fused ? K * P.n_bus * row : 0, row, P.n_bus * row, P.fused ? K : 0);
+        rows("d_bus_flags", P.d_bus_flags, P.fused ? K * P.n_bus : 0, K * P.n_bus, 0, P.fused ? 1 : 0);
+        rows("d_lazy", P.d_lazy, bank && P.lazy_capable ? nv * sizeof(LazyRec) : 0, nv * sizeof(LazyRec), 0, bank && P.lazy_capable && nv ? 1 : 0);
+        rows("d_chain_start", P.d_chain_start, bank ? nv * sizeof(ChainStart) : 0, nv * sizeof(ChainStart), 0, bank ? 1 : 0);
+        rows("d_chain_stats", P.d_chain_stats, bank ? 2 * sizeof(unsigned long long) : 0, 2 * sizeof(unsigned long long), 0, bank ? 1 : 0);
+        rows("d_rs_wl", P.d_rs_wl, bank && P.fused_rs ? (2 + 2 * (size_t)P.n_leaves * K * LEAF_WPB_MAX) * sizeof(unsigned) : 0, 2 * sizeof(unsigned), 0, bank && P.fused_rs ? 1 : 0);
+        rows("d_rt_tree_sync", P.d_rt_tree_sync, (size_t)P.rt_tree_up * sizeof(unsigned), (size_t)P.rt_tree_up * sizeof(unsigned), 0, P.rt_tree_up ? 1 : 0);
+#undef V
+#undef VEC
+#undef TAB
+    }
+};
+}  // namespace
+extern "C" unsigned long long fwh_image_digest(const fwgpu_ctx* c) {
+    ImageDigest d;
+    d.image(c);
+    return d.all;
+}
+// debug form: "field digest" lines into buf (truncated to cap - 1 characters); returns the length the whole text has
+extern "C" size_t fwh_image_digest_fields(const fwgpu_ctx* c, char* buf, size_t cap) {
+    std::string s;
+    ImageDigest d;
+    d.fields = &s;
+    d.image(c);
+    if (cap) snprintf(buf, cap, "%s", s.c_str());
+    return s.size();
+}

@@ -941,3 +941,69 @@ def test_resampler_plan_lazy_calls_on_the_host_harness():
     _, marks = rs_quiet_run(e, 256)
     assert e.cx.plan_kind() == 1 and e.violation() == "", e.violation()
     assert marks[-1][0] >= 6, marks
+
+
+def _image_digest(e, fields=False):
+    """tests/host_harness/launch_stubs.cpp fwh_image_digest: the active plan image, field by field (fields=True: the per-field text)"""
+    L = hostonly_lib()
+    L.fwh_image_digest.restype = C.c_ulonglong
+    L.fwh_image_digest.argtypes = [C.c_void_p]
+    L.fwh_image_digest_fields.restype = C.c_size_t
+    L.fwh_image_digest_fields.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    if not fields:
+        return int(L.fwh_image_digest(e.cx.c))
+    buf = C.create_string_buffer(int(L.fwh_image_digest_fields(e.cx.c, None, 0)) + 1)
+    L.fwh_image_digest_fields(e.cx.c, buf, len(buf))
+    return buf.value.decode()
+
+
+def _fir_host_meter_graph(e):
+    """12 samplers -> FIR (two impulse responses, one of them mono: padded tiles) -> mixer -> host node -> meter -> graph_out"""
+    irs = [e.new_sample(PLANAR_F32, ch, np.ones((ch, T), np.float32)) for ch, T in ((2, 700), (1, 4097))]
+    m = e.sum(12)
+    for v in range(12):
+        f = e.fir(irs[v % 2])
+        e.connect_stereo(e.sampler(100.0), f)
+        e.connect_stereo(f, m, 2 * v)
+    host = e.host_node(2, 2, lambda frames, ins, outs, in_mask, t, status: 0)
+    meter = e.add_node(16, 2, 2, [8])  # FWGPU_METER, a ring of 8 blocks
+    e.connect_stereo(m, host)
+    e.connect_stereo(host, meter)
+    e.connect_stereo(meter, e.graph_out_node)
+    e.update()
+
+
+@pytest.mark.parametrize("name,kind,generic_first,build", [
+    ("voice bank", 1, False, lambda e: bank(e, clip_in_voice=True, master=True)),
+    ("chain bank", 2, False, lambda e: bank(e, chain=True, clip_in_voice=True, master=True)),
+    ("hybrid", 3, False, send_graph),
+    ("hybrid, FIR banks, host node, meter", 3, False, _fir_host_meter_graph),
+    ("generic", 0, True, lambda e: bank(e, chain=True, master=True)),
+], ids=lambda x: x if isinstance(x, str) else "")
+def test_a_recycled_image_builds_what_a_fresh_one_builds(name, kind, generic_first, build):
+    """reset_for_build is the only code that clears what describes a plan; the build's steps only fill.  A plan image is recycled
+    two updates later, so a field the reset misses shows up as whatever the image's previous plan left there.  Here the same
+    graph is rebuilt with the generic executor forced on and off — the repeats make each of the two images hold both plans in
+    turn — and the digest of the active image (every describing field, every table's bytes, the defined part of every buffer
+    the kernels write) must come back to what the FIRST build, into a fresh image, gave."""
+    L = hostonly_lib()
+    L.fwh_build_applies.restype = C.c_ulonglong
+    e = HostOnlyEngine(max_block_frames=128, max_batch=16, force_generic=generic_first)
+    build(e)
+    assert e.cx.plan_kind() == kind
+    first, first_fields = _image_digest(e), _image_digest(e, fields=True)
+    other = None
+    for flip in (True, False, False, True, True, False, False):
+        e.cx.set_force_generic(flip != generic_first)
+        e.cx.set_max_batch(16)  # (the same value: marks the graph for a rebuild)
+        builds = int(L.fwh_build_applies())
+        e.update()
+        assert int(L.fwh_build_applies()) > builds
+        if not flip:
+            assert e.cx.plan_kind() == kind
+            assert _image_digest(e) == first, (first_fields, _image_digest(e, fields=True))
+        elif other is None:
+            other = _image_digest(e)
+        else:
+            assert _image_digest(e) == other
+    assert e.violation() == "", e.violation()
