@@ -18,6 +18,7 @@ from .graph import (  # noqa: F401
     FirewheelGpuCtx,
     HardClipNode,
     HostNode,
+    LimiterNode,
     LoopRange,
     MeterNode,
     MonoToStereoNode,
@@ -34,6 +35,6 @@ from .graph import (  # noqa: F401
 
 __all__ = [
     "FirewheelGpuCtx", "HostNode", "VolumeNode", "SumNode", "SamplerNode", "BeepTestNode", "HardClipNode", "MonoToStereoNode",
-    "StereoToMonoNode", "DummyAudioNode", "StereoPanNode", "StereoWidthNode", "BiquadNode", "DelayNode", "FirReverbNode", "ResamplerNode", "SpatialNode", "MeterNode", "LoopRange", "SampleFormat", "AddEdgeError",
+    "StereoToMonoNode", "DummyAudioNode", "StereoPanNode", "StereoWidthNode", "BiquadNode", "DelayNode", "FirReverbNode", "ResamplerNode", "SpatialNode", "MeterNode", "LimiterNode", "LoopRange", "SampleFormat", "AddEdgeError",
     "CompileGraphError", "FwgpuError", "load_library", "build_library", "LIB_PATH",
 ]

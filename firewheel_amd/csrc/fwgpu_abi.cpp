@@ -382,6 +382,10 @@ int64_t fwgpu_add_node(fwgpu_ctx* c, int kind, uint32_t n_in, uint32_t n_out, co
             return fail(c, FWGPU_ERR_INVALID, "Resampler node: source longer than 2^31 frames");
     }
     if (n_in > 64 || n_out > 64) return fail(c, FWGPU_ERR_INVALID, "a node has at most 64 ports per side (core/node.rs:62,69)");
+    if (kind == K_LIMITER) {  // (its shape is refused here; its creation parameters at the next update, as a meter's ring is)
+        std::string err;
+        if (!check_activation(kind, n_in, n_out, err)) return fail(c, FWGPU_ERR_INVALID, err);
+    }
     NodeState st = make_state(kind, params, n_params, c->sample_rate);
     return c->graph.add_node(kind, n_in, n_out, st);
 }
@@ -863,6 +867,8 @@ int fwgpu_node_set_param(fwgpu_ctx* c, int64_t node, int param, float value, uin
             m.i1 = dr;
             return push_cmd(c, node, -1, m, false);
         }
+        case K_LIMITER:  // ceiling and hold are fixed at construction (a moving ceiling would need a smoother: out of scope)
+            return fail(c, FWGPU_ERR_INVALID, "LimiterNode has no runtime params: ceiling and hold_frames are set at add_node");
         default:
             return fail(c, FWGPU_ERR_INVALID, "node kind has no runtime params");
     }

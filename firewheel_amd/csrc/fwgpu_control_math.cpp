@@ -205,6 +205,15 @@ NodeState make_state(int kind, const float* params, int n_params, uint32_t sampl
             s.loop_end = (r >= 1.0f && r <= (float)METER_RING_MAX && r == floorf(r)) ? (uint64_t)r : 0;
             break;
         }
+        case K_LIMITER: {  // params: ceiling (linear, 0.001..1000, default 1.0), hold_frames (0..1920, default 128)
+            const float ceil_ = p(0, 1.0f), h = p(1, (float)LIM_HOLD_DEFAULT);
+            // anything else — NaN, inf, a fraction, out of range — leaves loop_end 0, and the node fails activation at the next update
+            const bool ok = ceil_ >= 0.001f && ceil_ <= 1000.0f && h >= 0.0f && h <= (float)LIM_HOLD_MAX && h == floorf(h);
+            s.p0 = ok ? ceil_ : 1.0f;
+            s.loop_start = ok ? (uint64_t)h : 0;
+            s.loop_end = ok ? (uint64_t)h + LIM_HIST_PAD : 0;
+            break;
+        }
         default:
             break;
     }

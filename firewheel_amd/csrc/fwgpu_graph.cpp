@@ -261,6 +261,13 @@ bool check_activation(int kind, uint32_t n_in, uint32_t n_out, std::string& err)
                 return false;
             }
             return true;
+        case K_LIMITER:  // SPEC: linked channels, as many outputs as inputs, 1..8
+            if (n_in != n_out || n_in < 1 || n_in > LIM_CH_MAX) {
+                err = "LimiterNode needs 1..8 inputs and as many outputs. Got num_inputs: " + std::to_string(n_in) +
+                      ", num_outputs: " + std::to_string(n_out);
+                return false;
+            }
+            return true;
         case K_MONO_TO_STEREO:
             if (n_in < 1 || n_out < 2) {
                 err = "MonoToStereoNode needs 1 input and 2 outputs.";

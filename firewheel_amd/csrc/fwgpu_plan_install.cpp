@@ -604,6 +604,11 @@ static int activate_nodes(ImageBuild& b) {
             if (n.init.loop_end < 1 || n.init.loop_end > METER_RING_MAX)
                 return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "MeterNode: ring_blocks must be a whole number in 1..65536");
             len = (size_t)n.init.loop_end * (size_t)n.n_in * (sizeof(MeterRec) / sizeof(float));
+        } else if (n.kind == K_LIMITER) {  // hist[n_in][HK], zeroed like every slice: zeros are the SPEC's x[n < 0]
+            if (n.init.loop_end < LIM_HIST_PAD || n.init.loop_end > LIM_HOLD_MAX + LIM_HIST_PAD)
+                return fail(c, FWGPU_ERR_INVALID,
+                            "LimiterNode: ceiling must be finite and in 0.001..1000, hold_frames a whole number in 0..1920");
+            len = (size_t)n.n_in * (size_t)n.init.loop_end;
         } else if (n.kind == K_FIR) {
             int ir = n.init.sample;
             if (ir < 0 || ir >= (int)c->samples.size() || !c->samples[ir].alive)

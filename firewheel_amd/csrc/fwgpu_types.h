@@ -10,8 +10,16 @@ enum : int {
     K_FIR = 12, K_RESAMPLER = 13, K_SPATIAL = 14,
     K_HOST = 15,  // a node the library does not implement: the caller's own AudioNodeProcessor::process, run on the host
     K_METER = 16,  // SPEC level meter: per block and input channel peak, sum of squares and overs; audio passes through
-    K_LAST = K_METER,
+    K_LIMITER = 17,  // SPEC look-ahead limiter: linked channels, sliding minimum + 64-term moving average, 63 frames of latency
+    K_LAST = K_LIMITER,
 };
+// K_LIMITER: LIM_LOOK terms in the moving average (one per lane of a wave; 1/64 is an exact scale), latency LIM_LOOK - 1 frames.  The
+// node's ext slice keeps the last H + LIM_HIST_PAD input frames per channel (H = hold_frames); a block reads back H + 2 * (LIM_LOOK - 1).
+#define LIM_LOOK 64
+#define LIM_HOLD_DEFAULT 128u
+#define LIM_HOLD_MAX 1920u
+#define LIM_HIST_PAD 128u
+#define LIM_CH_MAX 8
 // K_METER: one record per (block, input channel) — include/fwgpu.h fwgpu_meter_reading, written as ONE 16-byte store.  The node's
 // ext slice is a ring of R x n_in of them (R = NodeState::loop_end); block g of the ctx's block count sits in slot g % R.
 struct MeterRec {
@@ -74,6 +82,8 @@ struct NodeState {
     //   SPATIAL: p0/p1 = ear gain targets (s0/s1 smooth them), playing = left-ear delay, has_loop = right-ear delay
     //        (frames), ext = the last SP_HIST mono samples
     //   METER: ext = ring[R][n_in] of MeterRec (4 floats each), loop_end = R (0: the creation parameter was refused)
+    //   LIMITER: p0 = ceiling C, loop_start = hold_frames H, loop_end = HK = H + LIM_HIST_PAD (0: a creation parameter was refused),
+    //        ext = hist[n_in][HK]: the last HK input frames per channel, oldest first
     uint32_t ext_off;
     uint32_t ext_len;
     int pad[1];

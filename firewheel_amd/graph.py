@@ -320,6 +320,11 @@ class MeterNode(_Node):
             return (np.float32(20.0) * np.log10(np.asarray(amp, dtype=np.float32))).astype(np.float32)
 
     @staticmethod
+    def db_to_gain(db):
+        """core/util.rs db_to_gain: 10 ** (0.05 * db), in f32 — what gain_to_db inverts"""
+        return np.power(np.float32(10.0), np.float32(0.05) * np.asarray(db, dtype=np.float32)).astype(np.float32)
+
+    @staticmethod
     def peak_db(readings):
         return MeterNode.gain_to_db(np.asarray(readings)["peak"])
 
@@ -330,6 +335,28 @@ class MeterNode(_Node):
         with np.errstate(divide="ignore", invalid="ignore"):
             rms = np.sqrt(r["sum_squares"] / r["frames"].astype(np.float32), dtype=np.float32)
         return MeterNode.gain_to_db(rms)
+
+
+class LimiterNode(_Node):
+    """SPEC node: look-ahead limiter — linked channels, brickwall at `ceiling` (linear, 0.001..1000) with a hold of
+    `hold_frames` (0..1920), `latency_frames` = 63 frames late.  A sliding minimum of the target gain and a 64-term moving average, no
+    recurrence in time: the blocks of a batch render in parallel, bit-exact against the numpy model of tests/test_limiter.py.
+    add_node(channels, channels, LimiterNode(...)), channels in 1..8.  `ceiling_db=` gives the ceiling in decibels instead, converted by
+    the function MeterNode.peak_db inverts.  No parameters after creation."""
+    KIND = 17
+    latency_frames = 63
+
+    def __init__(self, ceiling=1.0, hold_frames=128, channels=2, ceiling_db=None):
+        self.ceiling = float(MeterNode.db_to_gain(ceiling_db)) if ceiling_db is not None else ceiling
+        self.hold_frames = hold_frames
+        self.channels = channels
+
+    @property
+    def ceiling_db(self):
+        return float(MeterNode.gain_to_db(self.ceiling))
+
+    def params(self):
+        return [float(self.ceiling), float(self.hold_frames)]
 
 
 class _RawNode(_Node):

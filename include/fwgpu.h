@@ -57,7 +57,9 @@ enum fwgpu_node_kind {
     FWGPU_RESAMPLER = 13,     /* SPEC polyphase resampling source (0 inputs)  params: sample id, ratio, loop, playing */
     FWGPU_SPATIAL = 14,       /* SPEC 3D spatialiser (1|2 in, 2 out)          params: x, y, z of the source */
     FWGPU_HOST_NODE = 15,     /* any other `dyn AudioNodeProcessor` (graph/processor.rs:243): runs on the HOST, see below */
-    FWGPU_METER = 16          /* SPEC level meter     params: ring_blocks (1..65536, default 1024); see fwgpu_meter_read */
+    FWGPU_METER = 16,         /* SPEC level meter     params: ring_blocks (1..65536, default 1024); see fwgpu_meter_read */
+    FWGPU_LIMITER = 17        /* SPEC look-ahead limiter (n in, n out, n in 1..8)  params: ceiling (linear, 0.001..1000, default 1.0),
+                                 hold_frames (0..1920, default 128); see FWGPU_LIMITER_LATENCY */
 };
 
 /* sample formats — core/sample_resource.rs:28-335 */
@@ -425,6 +427,27 @@ typedef struct fwgpu_meter_reading {
  * without a stream wait is out of scope (it would need a pinned, device-mapped ring). */
 int64_t fwgpu_meter_read(fwgpu_ctx* ctx, int64_t node, uint64_t first_block, uint32_t num_blocks, fwgpu_meter_reading* out,
                          uint64_t* blocks_done);
+
+/* ---- look-ahead limiter (FWGPU_LIMITER; SPEC).  The remedy that goes with the meter's `over` count and, like it,
+ * leaves the mix in HBM: a linked-channel brickwall limiter with a hold, written as FIR stages — a sliding minimum of the target gain and
+ * a 64-term moving average in a fixed order of summation — so it has no recurrence in time, its K blocks of a batch render in parallel,
+ * and its output is bit-exact against a dozen lines of numpy (tests/test_limiter.py).  n_in == n_out in 1..8, refused at fwgpu_add_node
+ * otherwise; a ceiling that is NaN, infinite or outside 0.001..1000 and a hold_frames that is NaN, a fraction or outside 0..1920 fail
+ * activation at fwgpu_update (FWGPU_ERR_INVALID).  No parameters after creation (fwgpu_node_set_param is refused), no smoother, no
+ * messages.  With C = ceiling, H = hold_frames, x_c[n] input channel c at frame n since the node's activation (every frame of every
+ * block, full or short; +0.0 for n < 0; a channel flagged silent for a block counts as +0.0):
+ *   key[n] = max over c of |x_c[n]|      (fmaxf: a NaN sample is ignored; never negative)
+ *   t[n]   = key[n] > C ? C / key[n] : 1.0f                      (IEEE f32 division)
+ *   m[n]   = min of t[k], k in [n-63-H, n], t[k < 0] = 1.0f
+ *   s[n]   = (((m[n-63] + m[n-62]) + m[n-61]) + ...) + m[n]      (64 terms, one ascending chain of f32 adds, no FMA)
+ *   y_c[n] = x_c[n-63] * (s[n] * 0.015625f)
+ * The output is late by FWGPU_LIMITER_LATENCY frames.  |y| <= C * (1 + 66 * 2^-24): every m[j], j in [n-63, n], has frame n-63 in its
+ * window.  While nothing exceeds C the gain is exactly 1.0f and the output is the delayed input bit for bit; after an over the gain holds
+ * for H + 64 frames and returns along a 64-frame staircase average — a safety limiter, not a mastering one.  Outputs are never flagged
+ * silent.  The node's state is the last H + 128 input frames per channel, zeroed at activation and kept across plan changes.  A 2 -> 2
+ * limiter in the master chain leaves the fused plan kind and its lazy calls as they are: one more launch per batch, as a meter; anywhere
+ * else the level executor renders it.  fwgpu_node_process renders it block by block with the history kept between calls. */
+#define FWGPU_LIMITER_LATENCY 63
 /* ProcInfo::stream_time_secs / stream_status (core/node.rs:111-132) of the most recent fwgpu_process_interleaved call —
  * what a custom node run through fwgpu_node_process inside that call would be handed — and how often the backend has
  * reported StreamStatus::OUTPUT_UNDERFLOW (bit 1) / INPUT_OVERFLOW (bit 0) so far.  Any pointer may be NULL. */

@@ -21,6 +21,8 @@ pub struct fwgpu_rccl_comm {
     _private: [u8; 0],
 }
 pub const FWGPU_RCCL_UNIQUE_ID_BYTES: usize = 128;
+/// frames a FWGPU_LIMITER node's output is late by
+pub const FWGPU_LIMITER_LATENCY: u32 = 63;
 /// AudioNodeProcessor::process + ProcInfo (core/node.rs:37-53,94-118) as the C callback of a FWGPU_HOST_NODE
 pub type fwgpu_host_process_fn = Option<
     unsafe extern "C" fn(
@@ -74,6 +76,7 @@ pub const FWGPU_RESAMPLER: c_int = 13;
 pub const FWGPU_SPATIAL: c_int = 14;
 pub const FWGPU_HOST_NODE: c_int = 15;
 pub const FWGPU_METER: c_int = 16;
+pub const FWGPU_LIMITER: c_int = 17;
 
 // enum fwgpu_sample_format
 pub const FWGPU_INTERLEAVED_I16: c_int = 0;

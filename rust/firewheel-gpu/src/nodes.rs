@@ -517,3 +517,38 @@ impl AudioNode for GpuMeterNode {
         self.b.deactivate()
     }
 }
+
+/// Look-ahead limiter (SPEC, DESIGN.md §6 of the fwgpu repository): linked channels, brickwall at `ceiling` (linear), a hold of
+/// `hold_frames`, [`GpuLimiterNode::LATENCY_FRAMES`] frames of latency.  A sliding minimum of the target gain and a 64-term moving average:
+/// no recurrence in time, so the blocks of a batch render in parallel on the device.  As many outputs as inputs, 1..=8.
+pub struct GpuLimiterNode {
+    b: Binding,
+    ceiling: f32,
+    hold_frames: u32,
+}
+impl GpuLimiterNode {
+    /// what the output is late by
+    pub const LATENCY_FRAMES: u32 = ffi::FWGPU_LIMITER_LATENCY;
+    /// `ceiling`: linear, finite, 0.001..=1000; `hold_frames`: 0..=1920.  Anything else fails activation.
+    pub fn new(cx: &Arc<GpuContext>, ceiling: f32, hold_frames: u32) -> Self {
+        Self { b: Binding::new(cx), ceiling, hold_frames }
+    }
+    /// the ceiling in decibels, through core/util.rs db_to_gain (what [`GpuMeterNode::peak_db`] inverts)
+    pub fn with_ceiling_db(cx: &Arc<GpuContext>, ceiling_db: f32, hold_frames: u32) -> Self {
+        Self::new(cx, firewheel_core::util::db_to_gain(ceiling_db), hold_frames)
+    }
+}
+impl AudioNode for GpuLimiterNode {
+    fn debug_name(&self) -> &'static str {
+        "limiter"
+    }
+    fn info(&self) -> AudioNodeInfo {
+        io(1, 8, 1, 8, false)
+    }
+    fn activate(&mut self, _sr: u32, _mbf: usize, num_inputs: usize, num_outputs: usize) -> Result<Box<dyn AudioNodeProcessor>, Box<dyn Error>> {
+        self.b.activate(ffi::FWGPU_LIMITER, num_inputs, num_outputs, &[self.ceiling, self.hold_frames as f32])
+    }
+    fn deactivate(&mut self, _p: Option<Box<dyn AudioNodeProcessor>>) {
+        self.b.deactivate()
+    }
+}

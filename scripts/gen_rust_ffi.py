@@ -83,6 +83,8 @@ def generate():
     o.append("pub const FWGPU_EXCHANGE_HANDLE_BYTES: usize = %d;" % int(re.search(r"#define FWGPU_EXCHANGE_HANDLE_BYTES (\d+)", open(HDR).read()).group(1)))
     o.append("#[repr(C)]\npub struct fwgpu_rccl_comm {\n    _private: [u8; 0],\n}")
     o.append("pub const FWGPU_RCCL_UNIQUE_ID_BYTES: usize = %d;" % int(re.search(r"#define FWGPU_RCCL_UNIQUE_ID_BYTES (\d+)", open(HDR).read()).group(1)))
+    o.append("/// frames a FWGPU_LIMITER node's output is late by")
+    o.append("pub const FWGPU_LIMITER_LATENCY: u32 = %d;" % int(re.search(r"#define FWGPU_LIMITER_LATENCY (\d+)", open(HDR).read()).group(1)))
     o.append("/// AudioNodeProcessor::process + ProcInfo (core/node.rs:37-53,94-118) as the C callback of a FWGPU_HOST_NODE")
     o.append("pub type fwgpu_host_process_fn = Option<\n    unsafe extern \"C\" fn(\n        user: *mut c_void,\n        frames: u64,\n        inputs: *const *const f32,\n"
              "        num_inputs: u32,\n        outputs: *const *mut f32,\n        num_outputs: u32,\n        in_silence_mask: u64,\n        out_silence_mask: *mut u64,\n"
