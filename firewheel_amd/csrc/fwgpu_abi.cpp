@@ -382,7 +382,7 @@ int64_t fwgpu_add_node(fwgpu_ctx* c, int kind, uint32_t n_in, uint32_t n_out, co
             return fail(c, FWGPU_ERR_INVALID, "Resampler node: source longer than 2^31 frames");
     }
     if (n_in > 64 || n_out > 64) return fail(c, FWGPU_ERR_INVALID, "a node has at most 64 ports per side (core/node.rs:62,69)");
-    if (kind == K_LIMITER) {  // (its shape is refused here; its creation parameters at the next update, as a meter's ring is)
+    if (kind == K_LIMITER || kind == K_DUCKER) {  // (its shape is refused here; its creation parameters at the next update, as a meter's ring is)
         std::string err;
         if (!check_activation(kind, n_in, n_out, err)) return fail(c, FWGPU_ERR_INVALID, err);
     }
@@ -869,6 +869,8 @@ int fwgpu_node_set_param(fwgpu_ctx* c, int64_t node, int param, float value, uin
         }
         case K_LIMITER:  // ceiling and hold are fixed at construction (a moving ceiling would need a smoother: out of scope)
             return fail(c, FWGPU_ERR_INVALID, "LimiterNode has no runtime params: ceiling and hold_frames are set at add_node");
+        case K_DUCKER:  // threshold, depth and the three times are fixed at construction (moving ones: out of scope)
+            return fail(c, FWGPU_ERR_INVALID, "DuckerNode has no runtime params: threshold, depth, attack, release and hold are set at add_node");
         default:
             return fail(c, FWGPU_ERR_INVALID, "node kind has no runtime params");
     }

@@ -214,6 +214,20 @@ NodeState make_state(int kind, const float* params, int n_params, uint32_t sampl
             s.loop_end = ok ? (uint64_t)h + LIM_HIST_PAD : 0;
             break;
         }
+        case K_DUCKER: {  // params: threshold (linear, 1e-6..1000), depth (0..1), attack_frames, release_frames (1..32768), hold_frames (0..32768)
+            const float t = p(0, DUCK_THRESHOLD_DEFAULT), d = p(1, DUCK_DEPTH_DEFAULT), a = p(2, (float)DUCK_ATTACK_DEFAULT),
+                        r = p(3, (float)DUCK_RELEASE_DEFAULT), h = p(4, (float)DUCK_HOLD_DEFAULT);
+            // anything else — NaN, inf, a fraction, out of range — leaves loop_end 0, and the node fails activation at the next update
+            const bool ok = t >= 1e-6f && t <= 1000.0f && d >= 0.0f && d <= 1.0f && a >= 1.0f && a <= (float)DUCK_WIN_MAX && a == floorf(a) &&
+                            r >= 1.0f && r <= (float)DUCK_WIN_MAX && r == floorf(r) && h >= 0.0f && h <= (float)DUCK_HOLD_MAX && h == floorf(h);
+            s.p0 = ok ? t : DUCK_THRESHOLD_DEFAULT;
+            s.p1 = ok ? d : 1.0f;
+            s.playhead = ok ? (uint64_t)a : 1;
+            s.loop_start = ok ? (uint64_t)r : 1;
+            s.full_range = ok ? (int)h : 0;
+            s.loop_end = ok ? (uint64_t)(a > r ? a : r) + (uint64_t)h : 0;
+            break;
+        }
         default:
             break;
     }

@@ -268,6 +268,13 @@ bool check_activation(int kind, uint32_t n_in, uint32_t n_out, std::string& err)
                 return false;
             }
             return true;
+        case K_DUCKER:  // SPEC: n main channels and k key channels in, n out, n and k in 1..8
+            if (n_out < 1 || n_out > DUCK_CH_MAX || n_in <= n_out || n_in - n_out > DUCK_CH_MAX) {
+                err = "DuckerNode needs 1..8 outputs and that many inputs plus 1..8 key inputs. Got num_inputs: " + std::to_string(n_in) +
+                      ", num_outputs: " + std::to_string(n_out);
+                return false;
+            }
+            return true;
         case K_MONO_TO_STEREO:
             if (n_in < 1 || n_out < 2) {
                 err = "MonoToStereoNode needs 1 input and 2 outputs.";

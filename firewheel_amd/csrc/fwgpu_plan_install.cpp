@@ -609,6 +609,12 @@ static int activate_nodes(ImageBuild& b) {
                 return fail(c, FWGPU_ERR_INVALID,
                             "LimiterNode: ceiling must be finite and in 0.001..1000, hold_frames a whole number in 0..1920");
             len = (size_t)n.n_in * (size_t)n.init.loop_end;
+        } else if (n.kind == K_DUCKER) {  // the last W gate bits in 64-bit groups, zeroed like every slice: zeros are the SPEC's closed gate
+            if (n.init.loop_end < 1 || n.init.loop_end > DUCK_WIN_MAX + DUCK_HOLD_MAX)
+                return fail(c, FWGPU_ERR_INVALID,
+                            "DuckerNode: threshold must be finite and in 1e-6..1000, depth in 0..1, attack_frames and release_frames whole "
+                            "numbers in 1..32768, hold_frames a whole number in 0..32768");
+            len = 2 * (((size_t)n.init.loop_end + 63) / 64);
         } else if (n.kind == K_FIR) {
             int ir = n.init.sample;
             if (ir < 0 || ir >= (int)c->samples.size() || !c->samples[ir].alive)

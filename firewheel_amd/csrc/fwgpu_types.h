@@ -11,8 +11,21 @@ enum : int {
     K_HOST = 15,  // a node the library does not implement: the caller's own AudioNodeProcessor::process, run on the host
     K_METER = 16,  // SPEC level meter: per block and input channel peak, sum of squares and overs; audio passes through
     K_LIMITER = 17,  // SPEC look-ahead limiter: linked channels, sliding minimum + 64-term moving average, 63 frames of latency
-    K_LAST = K_LIMITER,
+    K_DUCKER = 18,  // SPEC sidechain ducker: n main + k key inputs, n outputs; window counts of the key's gate bits, no latency
+    K_LAST = K_DUCKER,
 };
+// K_DUCKER: the caps of attack, release and hold (frames).  The gate's history is W = max(A, R) + H bits, at most DUCK_WIN_MAX +
+// DUCK_HOLD_MAX = 65 536 bits = 8 KiB, and a wave stages it in LDS in front of the DUCK_RUN_MAX frames (1 KiB of bits) it renders:
+// the caps are sized so that the staged bit window stays around 10 KB of LDS (k_ducker.hip.h DuckLds).
+#define DUCK_WIN_MAX 32768u
+#define DUCK_HOLD_MAX 32768u
+#define DUCK_RUN_MAX 8192
+#define DUCK_CH_MAX 8
+#define DUCK_THRESHOLD_DEFAULT 0.05f
+#define DUCK_DEPTH_DEFAULT 0.25f
+#define DUCK_ATTACK_DEFAULT 480u
+#define DUCK_RELEASE_DEFAULT 12000u
+#define DUCK_HOLD_DEFAULT 4800u
 // K_LIMITER: LIM_LOOK terms in the moving average (one per lane of a wave; 1/64 is an exact scale), latency LIM_LOOK - 1 frames.  The
 // node's ext slice keeps the last H + LIM_HIST_PAD input frames per channel (H = hold_frames); a block reads back H + 2 * (LIM_LOOK - 1).
 #define LIM_LOOK 64
@@ -84,6 +97,9 @@ struct NodeState {
     //   METER: ext = ring[R][n_in] of MeterRec (4 floats each), loop_end = R (0: the creation parameter was refused)
     //   LIMITER: p0 = ceiling C, loop_start = hold_frames H, loop_end = HK = H + LIM_HIST_PAD (0: a creation parameter was refused),
     //        ext = hist[n_in][HK]: the last HK input frames per channel, oldest first
+    //   DUCKER: p0 = threshold T, p1 = depth D, playhead = A, loop_start = R, full_range = H, loop_end = W = max(A, R) + H (0: a
+    //        creation parameter was refused), ext = the last W gate bits on[], oldest first, bit i in bit i % 32 of word i / 32 (the
+    //        float slots hold 32-bit words), 2 * ceil(W / 64) words, the bits from W on zero
     uint32_t ext_off;
     uint32_t ext_len;
     int pad[1];

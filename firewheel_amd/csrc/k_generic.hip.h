@@ -168,6 +168,7 @@ __device__ __forceinline__ bool kind_is_stateful(int kind) {
 __device__ __forceinline__ int kind_set(int kind) {
     if (kind == K_SAMPLER) return 2;
     if (kind == K_LIMITER) return 4;  // (no instantiation of k_level: k_limiter.hip.h, a kernel of its own)
+    if (kind == K_DUCKER) return 5;   // (nor here: k_ducker.hip.h)
     return (kind == K_BEEP || kind == K_BIQUAD || kind == K_DELAY || kind == K_RESAMPLER || kind == K_SPATIAL) ? 1 : 0;
 }
 // SET: 0 / 1 / 2 = that set only, 3 = all kinds (single-node entry).
@@ -176,7 +177,7 @@ template <int SET>
 __device__ void node_process_wave(const DevView& v, int node_idx, uint32_t blk, uint32_t cmd_block, bool store_state = true,
                                   uint32_t adv_blocks = 0, bool frozen_sampler = false) {
     const NodeDesc nd = v.nodes[node_idx];
-    if (nd.is_graph_io || nd.kind == K_FIR || nd.kind == K_LIMITER) return;  // I/O edges (k_graph_in/out); FIR banks run as MFMA GEMMs; k_limiter
+    if (nd.is_graph_io || nd.kind == K_FIR || nd.kind == K_LIMITER || nd.kind == K_DUCKER) return;  // I/O edges (k_graph_in/out); FIR banks run as MFMA GEMMs; k_limiter; k_ducker
     // the other instantiation's kinds return here; their switch cases are compiled out below (`if constexpr`: a case
     // that is compiled out falls through, which nothing can reach)
     if constexpr (SET != 3) {
@@ -1343,15 +1344,7 @@ __global__ __launch_bounds__(WAVE* WPB) void k_bus_iir(DevView v, const int* __r
     }
 }
 
-// B1: one node on scratch buffers (single wave)
-__device__ void limiter_node(const DevView& v, const NodeDesc& nd, uint32_t b, uint32_t K);  // (k_limiter.hip.h)
-__global__ __launch_bounds__(WAVE) void k_single_node(DevView v, int node_idx) {
-    if (v.nodes[node_idx].kind == K_LIMITER) {  // one block through the stored history, which the call leaves advanced
-        limiter_node(v, v.nodes[node_idx], 0, 1);
-        return;
-    }
-    node_process_wave<3>(v, node_idx, 0, 0);
-}
+// (B1, one node on scratch buffers — k_single_node — is in k_ducker.hip.h, behind the two kinds that bring LDS of their own)
 
 // ------------------------------------------------------------------ state init / graph I/O edges
 struct StateInit {

@@ -151,8 +151,8 @@ __device__ void limiter_history(const DevView& v, const NodeDesc& nd, const Node
 
 // block b of a launch of K blocks.  Parallel path: every block has at least H + 126 frames, so block b > 0 finds all it needs in block
 // b-1's input.  Otherwise (short blocks, a one-block launch) the b == 0 wave takes the K blocks in order through the stored history.
-__device__ void limiter_node(const DevView& v, const NodeDesc& nd, uint32_t b, uint32_t K) {
-    __shared__ LimLds L;
+// (L: the caller's LDS — k_limiter's own, or k_single_node's, which a ducker shares)
+__device__ void limiter_node(const DevView& v, const NodeDesc& nd, uint32_t b, uint32_t K, LimLds& L) {
     const NodeState& s = v.states[nd.state];
     const uint64_t H = s.loop_start;
     // (nothing a plan build lets through; a slice of another size would be indexed out of bounds)
@@ -172,8 +172,9 @@ __device__ void limiter_node(const DevView& v, const NodeDesc& nd, uint32_t b, u
 
 // one workgroup of one wave per (node of the level, block); nodes of other kinds are k_level's
 __global__ __launch_bounds__(WAVE) void k_limiter(DevView v, const int* __restrict__ level_nodes, int n_nodes, uint32_t K) {
+    __shared__ LimLds L;
     if ((int)blockIdx.x >= n_nodes) return;
     const NodeDesc nd = v.nodes[level_nodes[blockIdx.x]];
     if (nd.kind != K_LIMITER) return;
-    limiter_node(v, nd, blockIdx.y, K);
+    limiter_node(v, nd, blockIdx.y, K, L);
 }

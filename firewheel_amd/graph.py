@@ -359,6 +359,49 @@ class LimiterNode(_Node):
         return [float(self.ceiling), float(self.hold_frames)]
 
 
+class DuckerNode(_Node):
+    """SPEC node: sidechain ducker — while the key bus is above `threshold` (linear, 1e-6..1000) the main bus is
+    turned down to `depth` (linear gain while ducked, 0..1): down over `attack_frames`, held for `hold_frames` after the key has gone
+    quiet, back up over `release_frames` (1..32768, 1..32768, 0..32768).  The gain is a function of integer counts over windows of the
+    key's gate bits, no recurrence in time: the blocks of a batch render in parallel, bit-exact against the numpy model of
+    tests/test_ducker.py; no latency.  add_node(channels + key_channels, channels, DuckerNode(...)): inputs 0..channels-1 are the main
+    bus, the rest the key, which is never heard; channels and key_channels in 1..8.  `threshold_db=` / `depth_db=` give the two in
+    decibels instead, converted by MeterNode.db_to_gain.  No parameters after creation."""
+    KIND = 18
+
+    def __init__(self, threshold=0.05, depth=0.25, attack_frames=480, release_frames=12000, hold_frames=4800, channels=2, key_channels=2,
+                 threshold_db=None, depth_db=None):
+        self.threshold = float(MeterNode.db_to_gain(threshold_db)) if threshold_db is not None else threshold
+        self.depth = float(MeterNode.db_to_gain(depth_db)) if depth_db is not None else depth
+        self.attack_frames = attack_frames
+        self.release_frames = release_frames
+        self.hold_frames = hold_frames
+        self.channels = channels
+        self.key_channels = key_channels
+
+    @property
+    def num_inputs(self):
+        return self.channels + self.key_channels
+
+    def attack_secs(self, sample_rate):
+        return self.attack_frames / float(sample_rate)
+
+    def release_secs(self, sample_rate):
+        return self.release_frames / float(sample_rate)
+
+    def hold_secs(self, sample_rate):
+        return self.hold_frames / float(sample_rate)
+
+    @classmethod
+    def from_secs(cls, sample_rate, attack_secs=0.01, release_secs=0.25, hold_secs=0.1, **kw):
+        """the three times in seconds, rounded to whole frames of `sample_rate`"""
+        return cls(attack_frames=max(1, int(round(attack_secs * sample_rate))), release_frames=max(1, int(round(release_secs * sample_rate))),
+                   hold_frames=max(0, int(round(hold_secs * sample_rate))), **kw)
+
+    def params(self):
+        return [float(self.threshold), float(self.depth), float(self.attack_frames), float(self.release_frames), float(self.hold_frames)]
+
+
 class _RawNode(_Node):
     def __init__(self, kind, params):
         self.KIND = kind

@@ -58,8 +58,11 @@ enum fwgpu_node_kind {
     FWGPU_SPATIAL = 14,       /* SPEC 3D spatialiser (1|2 in, 2 out)          params: x, y, z of the source */
     FWGPU_HOST_NODE = 15,     /* any other `dyn AudioNodeProcessor` (graph/processor.rs:243): runs on the HOST, see below */
     FWGPU_METER = 16,         /* SPEC level meter     params: ring_blocks (1..65536, default 1024); see fwgpu_meter_read */
-    FWGPU_LIMITER = 17        /* SPEC look-ahead limiter (n in, n out, n in 1..8)  params: ceiling (linear, 0.001..1000, default 1.0),
+    FWGPU_LIMITER = 17,       /* SPEC look-ahead limiter (n in, n out, n in 1..8)  params: ceiling (linear, 0.001..1000, default 1.0),
                                  hold_frames (0..1920, default 128); see FWGPU_LIMITER_LATENCY */
+    FWGPU_DUCKER = 18         /* SPEC sidechain ducker (n + k in, n out, n and k in 1..8)  params: threshold (linear, 1e-6..1000, default
+                                 0.05), depth (0..1, default 0.25), attack_frames (1..32768, default 480), release_frames (1..32768,
+                                 default 12000), hold_frames (0..32768, default 4800); see "sidechain ducker" below */
 };
 
 /* sample formats — core/sample_resource.rs:28-335 */
@@ -448,6 +451,34 @@ int64_t fwgpu_meter_read(fwgpu_ctx* ctx, int64_t node, uint64_t first_block, uin
  * limiter in the master chain leaves the fused plan kind and its lazy calls as they are: one more launch per batch, as a meter; anywhere
  * else the level executor renders it.  fwgpu_node_process renders it block by block with the history kept between calls. */
 #define FWGPU_LIMITER_LATENCY 63
+
+/* ---- sidechain ducker (FWGPU_DUCKER; SPEC).  A key bus turns another bus down — dialogue over music — without
+ * either leaving HBM: the first node with a sidechain, an input that steers the node and is not heard.  n_out = n outputs and
+ * n_in = n + k inputs, n and k in 1..8: inputs 0..n-1 are the main bus, inputs n..n+k-1 the key; any other shape is refused at
+ * fwgpu_add_node.  A threshold that is NaN, infinite or outside 1e-6..1000, a depth outside 0..1, an attack_frames or release_frames
+ * that is NaN, a fraction or outside 1..32768 and a hold_frames that is NaN, a fraction or outside 0..32768 fail activation at
+ * fwgpu_update (FWGPU_ERR_INVALID).  No parameters after creation (fwgpu_node_set_param is refused), no smoother, no messages.  With
+ * T = threshold, D = depth, A, R, H = attack, release and hold frames, x_c[n] main channel c and k_j[n] key channel j at frame n since
+ * the node's activation (every frame of every block, full or short; everything false or zero for n < 0; a key channel flagged silent
+ * for a block counts as +0.0 and is not read):
+ *   key[n]  = max over j of |k_j[n]|      (fmaxf from +0.0: a NaN sample is ignored; never negative)
+ *   on[n]   = key[n] > T                  (a sample of exactly T does not open the gate)
+ *   open[n] = on[k] for some k in [n-H, n]
+ *   ca[n]   = number of k in (n-A, n] with open[k]        cr[n] = number of k in (n-R, n] with open[k]        (integers)
+ *   a[n]    = (float)ca[n] / (float)A     r[n] = (float)cr[n] / (float)R                (IEEE f32 division, correctly rounded)
+ *   u[n]    = fmaxf(a[n], r[n])           (the ducking amount, 0..1)
+ *   g[n]    = 1.0f - ((1.0f - D) * u[n])  (1.0f - D once; one product, one subtraction, no FMA)
+ *   y_c[n]  = x_c[n] * g[n]
+ * No latency.  No recurrence in time: the gain is a function of integer counts over windows of the key, so the K blocks of a batch
+ * render in parallel and the output is bit-exact against a few lines of numpy (tests/test_ducker.py) in any order of evaluation.
+ * While the gate has been closed for max(A, R) + H frames g is exactly 1.0f and the output is the input bit for bit; after max(A, R)
+ * open frames g = 1.0f - (1.0f - D); u never steps by more than 1 / min(A, R).  With A <= R the gain falls over A frames and comes
+ * back linearly over R.  An open run shorter than R ducks to full depth in A frames, recovers over A frames to the plateau len / R
+ * and leaves over the rest of R: the price of having no recurrence.  A main channel flagged silent gives an output that is
+ * zero-filled and flagged; any other output is never flagged.  The node's state is the last max(A, R) + H gate bits on[], bit-packed,
+ * zeroed at activation (the gate was closed) and kept across plan changes.  A ducker is never part of a fused plan's master chain
+ * (it is not 2 -> 2): the level executor renders it.  fwgpu_node_process renders it block by block with the history kept between
+ * calls. */
 /* ProcInfo::stream_time_secs / stream_status (core/node.rs:111-132) of the most recent fwgpu_process_interleaved call —
  * what a custom node run through fwgpu_node_process inside that call would be handed — and how often the backend has
  * reported StreamStatus::OUTPUT_UNDERFLOW (bit 1) / INPUT_OVERFLOW (bit 0) so far.  Any pointer may be NULL. */

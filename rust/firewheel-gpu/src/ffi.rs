@@ -77,6 +77,7 @@ pub const FWGPU_SPATIAL: c_int = 14;
 pub const FWGPU_HOST_NODE: c_int = 15;
 pub const FWGPU_METER: c_int = 16;
 pub const FWGPU_LIMITER: c_int = 17;
+pub const FWGPU_DUCKER: c_int = 18;
 
 // enum fwgpu_sample_format
 pub const FWGPU_INTERLEAVED_I16: c_int = 0;

@@ -552,3 +552,52 @@ impl AudioNode for GpuLimiterNode {
         self.b.deactivate()
     }
 }
+
+/// Sidechain ducker (SPEC, DESIGN.md §6 of the fwgpu repository): while the key bus is above `threshold` the main bus is turned down
+/// to `depth` (linear gain while ducked) — down over `attack_frames`, held for `hold_frames`, back over `release_frames`.  The gain is
+/// a function of integer counts over windows of the key's gate bits: no recurrence in time, so the blocks of a batch render in
+/// parallel on the device; no latency.  Inputs `0..n` are the main bus, inputs `n..n + k` the key (never heard); `n` outputs;
+/// `n` and `k` in 1..=8.
+pub struct GpuDuckerNode {
+    b: Binding,
+    threshold: f32,
+    depth: f32,
+    attack_frames: u32,
+    release_frames: u32,
+    hold_frames: u32,
+}
+impl GpuDuckerNode {
+    /// `threshold`: linear, finite, 1e-6..=1000; `depth`: 0..=1; `attack_frames`, `release_frames`: 1..=32768; `hold_frames`:
+    /// 0..=32768.  Anything else fails activation.
+    pub fn new(cx: &Arc<GpuContext>, threshold: f32, depth: f32, attack_frames: u32, release_frames: u32, hold_frames: u32) -> Self {
+        Self { b: Binding::new(cx), threshold, depth, attack_frames, release_frames, hold_frames }
+    }
+    /// threshold and depth in decibels, through core/util.rs db_to_gain
+    pub fn with_db(cx: &Arc<GpuContext>, threshold_db: f32, depth_db: f32, attack_frames: u32, release_frames: u32, hold_frames: u32) -> Self {
+        Self::new(cx, firewheel_core::util::db_to_gain(threshold_db), firewheel_core::util::db_to_gain(depth_db), attack_frames,
+                  release_frames, hold_frames)
+    }
+    /// a time in seconds as whole frames of `sample_rate` (what the three `_frames` arguments take)
+    pub fn secs_to_frames(secs: f64, sample_rate: u32) -> u32 {
+        (secs * sample_rate as f64).round().max(0.0) as u32
+    }
+}
+impl AudioNode for GpuDuckerNode {
+    fn debug_name(&self) -> &'static str {
+        "ducker"
+    }
+    fn info(&self) -> AudioNodeInfo {
+        io(2, 16, 1, 8, false)
+    }
+    fn activate(&mut self, _sr: u32, _mbf: usize, num_inputs: usize, num_outputs: usize) -> Result<Box<dyn AudioNodeProcessor>, Box<dyn Error>> {
+        self.b.activate(
+            ffi::FWGPU_DUCKER,
+            num_inputs,
+            num_outputs,
+            &[self.threshold, self.depth, self.attack_frames as f32, self.release_frames as f32, self.hold_frames as f32],
+        )
+    }
+    fn deactivate(&mut self, _p: Option<Box<dyn AudioNodeProcessor>>) {
+        self.b.deactivate()
+    }
+}
