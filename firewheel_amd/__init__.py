@@ -16,6 +16,7 @@ from .graph import (  # noqa: F401
     DummyAudioNode,
     FirReverbNode,
     FirewheelGpuCtx,
+    DelayCompNode,
     DuckerNode,
     HardClipNode,
     HostNode,
@@ -36,6 +37,6 @@ from .graph import (  # noqa: F401
 
 __all__ = [
     "FirewheelGpuCtx", "HostNode", "VolumeNode", "SumNode", "SamplerNode", "BeepTestNode", "HardClipNode", "MonoToStereoNode",
-    "StereoToMonoNode", "DummyAudioNode", "StereoPanNode", "StereoWidthNode", "BiquadNode", "DelayNode", "FirReverbNode", "ResamplerNode", "SpatialNode", "MeterNode", "LimiterNode", "DuckerNode", "LoopRange", "SampleFormat", "AddEdgeError",
+    "StereoToMonoNode", "DummyAudioNode", "StereoPanNode", "StereoWidthNode", "BiquadNode", "DelayNode", "FirReverbNode", "ResamplerNode", "SpatialNode", "MeterNode", "LimiterNode", "DuckerNode", "DelayCompNode", "LoopRange", "SampleFormat", "AddEdgeError",
     "CompileGraphError", "FwgpuError", "load_library", "build_library", "LIB_PATH",
 ]

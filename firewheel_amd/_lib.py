@@ -38,6 +38,10 @@ class MeterReading(C.Structure):  # fwgpu_meter_reading: one record per (block, 
     _fields_ = [("peak", f32), ("sum_squares", f32), ("over", u32), ("frames", u32)]
 
 
+class LatencySkew(C.Structure):  # fwgpu_latency_skew: one record of fwgpu_graph_latency_report
+    _fields_ = [("node", i64), ("port", u32), ("lead_frames", u32)]
+
+
 # fwgpu_host_process_fn: AudioNodeProcessor::process + ProcInfo as a C callback (FWGPU_HOST_NODE)
 HOST_PROCESS_FN = C.CFUNCTYPE(None, vp, u64, C.POINTER(fp), u32, C.POINTER(fp), u32, u64, C.POINTER(u64), f64, u32)
 
@@ -137,6 +141,9 @@ SIGNATURES = {
     "fwgpu_bus_exchange_wait_stats": (ci, [vp, C.POINTER(u64), u32, ci]),
     "fwgpu_synchronize": (ci, [vp]),
     "fwgpu_meter_read": (i64, [vp, i64, u64, u32, C.POINTER(MeterReading), C.POINTER(u64)]),
+    "fwgpu_node_latency": (ci, [vp, i64, C.POINTER(u32)]),
+    "fwgpu_graph_latency_report": (i64, [vp, C.POINTER(LatencySkew), u32]),
+    "fwgpu_graph_output_latency": (ci, [vp, C.POINTER(u32)]),
     "fwgpu_node_process": (ci, [vp, i64, u64, C.POINTER(fp), u32, C.POINTER(fp), u32, u64, C.POINTER(u64), f64, u32]),
     "fwgpu_timing_enable": (ci, [vp, ci]),
     "fwgpu_timing_read": (ci, [vp, ci, C.POINTER(f64), C.POINTER(u64)]),

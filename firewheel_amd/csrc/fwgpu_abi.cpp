@@ -382,7 +382,7 @@ int64_t fwgpu_add_node(fwgpu_ctx* c, int kind, uint32_t n_in, uint32_t n_out, co
             return fail(c, FWGPU_ERR_INVALID, "Resampler node: source longer than 2^31 frames");
     }
     if (n_in > 64 || n_out > 64) return fail(c, FWGPU_ERR_INVALID, "a node has at most 64 ports per side (core/node.rs:62,69)");
-    if (kind == K_LIMITER || kind == K_DUCKER) {  // (its shape is refused here; its creation parameters at the next update, as a meter's ring is)
+    if (kind == K_LIMITER || kind == K_DUCKER || kind == K_DELAY_COMP) {  // (its shape is refused here; its creation parameters at the next update, as a meter's ring is)
         std::string err;
         if (!check_activation(kind, n_in, n_out, err)) return fail(c, FWGPU_ERR_INVALID, err);
     }
@@ -458,6 +458,45 @@ int fwgpu_disconnect(fwgpu_ctx* c, int64_t src, uint32_t sp, int64_t dst, uint32
 }
 int fwgpu_disconnect_edge(fwgpu_ctx* c, int64_t e) { return c ? c->graph.disconnect_edge(e) : FWGPU_ERR_INVALID; }
 int fwgpu_cycle_detected(fwgpu_ctx* c) { return c ? (c->graph.cycle_detected() ? 1 : 0) : FWGPU_ERR_INVALID; }
+
+// ---- latency queries (include/fwgpu.h, "latency compensation"): pure host code over the current edge set
+int fwgpu_node_latency(fwgpu_ctx* c, int64_t node, uint32_t* frames) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    const HostNode* hn = c->graph.get(node);
+    if (!hn) return fail(c, FWGPU_ERR_INVALID, "node_latency: unknown node");
+    if (frames) *frames = HostGraph::own_latency(*hn);
+    return 0;
+}
+int64_t fwgpu_graph_latency_report(fwgpu_ctx* c, fwgpu_latency_skew* out, uint32_t cap) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    if (cap && !out) return fail(c, FWGPU_ERR_INVALID, "latency_report: out is null but cap > 0");
+    const HostGraph& g = c->graph;
+    std::vector<uint32_t> lat;
+    if (!g.arrival_latency(lat)) return fail(c, FWGPU_ERR_COMPILE_CYCLE, "cycle detected");
+    int64_t total = 0;
+    for (uint32_t slot = 0; slot < g.nodes.size(); ++slot) {
+        const HostNode& n = g.nodes[slot];
+        if (!n.alive) continue;
+        uint32_t latest = 0;
+        for (uint32_t p = 0; p < n.n_in; ++p)
+            if (n.in_edge[p] >= 0) latest = std::max(latest, lat[g.edges[n.in_edge[p]].src]);
+        for (uint32_t p = 0; p < n.n_in; ++p) {
+            if (n.in_edge[p] < 0) continue;
+            const uint32_t arrives = lat[g.edges[n.in_edge[p]].src];
+            if (arrives == latest) continue;
+            if ((uint64_t)total < cap) out[total] = fwgpu_latency_skew{g.id_of(slot), p, latest - arrives};
+            total++;
+        }
+    }
+    return total;
+}
+int fwgpu_graph_output_latency(fwgpu_ctx* c, uint32_t* frames) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    std::vector<uint32_t> lat;
+    if (!c->graph.arrival_latency(lat)) return fail(c, FWGPU_ERR_COMPILE_CYCLE, "cycle detected");
+    if (frames) *frames = lat[c->graph.graph_out_slot];  // (graph_out adds nothing of its own)
+    return 0;
+}
 
 int fwgpu_host_node_set_process(fwgpu_ctx* c, int64_t node, fwgpu_host_process_fn fn, void* user) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
@@ -871,6 +910,8 @@ int fwgpu_node_set_param(fwgpu_ctx* c, int64_t node, int param, float value, uin
             return fail(c, FWGPU_ERR_INVALID, "LimiterNode has no runtime params: ceiling and hold_frames are set at add_node");
         case K_DUCKER:  // threshold, depth and the three times are fixed at construction (moving ones: out of scope)
             return fail(c, FWGPU_ERR_INVALID, "DuckerNode has no runtime params: threshold, depth, attack, release and hold are set at add_node");
+        case K_DELAY_COMP:  // the delay is fixed at construction (a moving one would be an effect: FWGPU_DELAY)
+            return fail(c, FWGPU_ERR_INVALID, "DelayCompNode has no runtime params: frames is set at add_node");
         default:
             return fail(c, FWGPU_ERR_INVALID, "node kind has no runtime params");
     }

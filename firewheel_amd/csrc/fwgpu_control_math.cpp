@@ -228,6 +228,15 @@ NodeState make_state(int kind, const float* params, int n_params, uint32_t sampl
             s.loop_end = ok ? (uint64_t)(a > r ? a : r) + (uint64_t)h : 0;
             break;
         }
+        case K_DELAY_COMP: {  // params: frames (the delay D, a whole number in 0..8192, default 63)
+            const float d = p(0, (float)DCOMP_DEFAULT);
+            // anything else — NaN, a fraction, out of range — leaves loop_end 0, and the node fails activation at the next update; D = 0
+            // is a valid delay, so the marker is D + 1
+            const bool ok = d >= 0.0f && d <= (float)DCOMP_MAX && d == floorf(d);
+            s.loop_start = ok ? (uint64_t)d : 0;
+            s.loop_end = ok ? (uint64_t)d + 1 : 0;
+            break;
+        }
         default:
             break;
     }

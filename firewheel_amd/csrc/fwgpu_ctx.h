@@ -130,10 +130,11 @@ inline int host_kind_set(int kind) {
     if (kind == K_SAMPLER) return 2;
     if (kind == K_LIMITER) return 4;  // (no k_level instantiation: k_limiter, launched next to them)
     if (kind == K_DUCKER) return 5;   // (nor here: k_ducker)
+    if (kind == K_DELAY_COMP) return 6;  // (nor here: k_delay_comp)
     return (kind == K_BEEP || kind == K_BIQUAD || kind == K_DELAY || kind == K_RESAMPLER || kind == K_SPATIAL) ? 1 : 0;
 }
 // a level's launch bits: the kernel set of the kind, plus bit 3 for a biquad / delay (a bus one goes to the batch walkers); bit 4 (set 4):
-// the level holds a look-ahead limiter, a kernel of its own; bit 5 (set 5): a sidechain ducker, likewise
+// the level holds a look-ahead limiter, a kernel of its own; bit 5 (set 5): a sidechain ducker, likewise; bit 6 (set 6): a latency-compensation delay, likewise
 inline int host_kind_bits(int kind) { return (1 << host_kind_set(kind)) | ((kind == K_BIQUAD || kind == K_DELAY) ? 8 : 0); }
 
 // A statistics counter the audio thread bumps and the control thread reads (fwgpu_rt_path_stats, fwgpu_lazy_stats,

@@ -199,6 +199,48 @@ bool HostGraph::cycle_detected() {
     return !topo_order(order);
 }
 
+uint32_t HostGraph::own_latency(const HostNode& n) {
+    if (n.kind == K_LIMITER) return FWGPU_LIMITER_LATENCY;
+    if (n.kind == K_DELAY_COMP) return n.init.loop_end ? (uint32_t)n.init.loop_start : 0u;  // (a refused `frames` never activates)
+    return 0;  // (K_DELAY included: an effect, not latency)
+}
+
+bool HostGraph::arrival_latency(std::vector<uint32_t>& out) const {
+    const size_t NS = nodes.size();
+    // (scratch of its own: a query never disturbs the compiler's arrays)
+    std::vector<uint32_t> off(NS + 1, 0), adj, cur, queue;
+    std::vector<int> in_degree(NS, 0);
+    for (const HostEdge& e : edges)
+        if (e.alive) {
+            off[e.src + 1]++;
+            in_degree[e.dst]++;
+        }
+    for (size_t s = 0; s < NS; ++s) off[s + 1] += off[s];
+    adj.resize(off[NS]);
+    cur.assign(off.begin(), off.end() - 1);
+    for (const HostEdge& e : edges)
+        if (e.alive) adj[cur[e.src]++] = e.dst;
+    out.assign(NS, 0);  // (until a node is taken off the queue: the latest arrival among its inputs seen so far)
+    queue.reserve(NS);
+    size_t alive = 0;
+    for (uint32_t s = 0; s < NS; ++s) {
+        if (!meta[s].alive) continue;
+        alive++;
+        if (in_degree[s] == 0) queue.push_back(s);
+    }
+    size_t head = 0;
+    while (head < queue.size()) {
+        const uint32_t s = queue[head++];
+        out[s] += own_latency(nodes[s]);
+        for (uint32_t k = off[s]; k < off[s + 1]; ++k) {
+            const uint32_t d = adj[k];
+            out[d] = std::max(out[d], out[s]);
+            if (--in_degree[d] == 0) queue.push_back(d);
+        }
+    }
+    return head == alive;
+}
+
 bool check_activation(int kind, uint32_t n_in, uint32_t n_out, std::string& err) {
     switch (kind) {
         case K_VOLUME:  // volume.rs:63-65
@@ -271,6 +313,13 @@ bool check_activation(int kind, uint32_t n_in, uint32_t n_out, std::string& err)
         case K_DUCKER:  // SPEC: n main channels and k key channels in, n out, n and k in 1..8
             if (n_out < 1 || n_out > DUCK_CH_MAX || n_in <= n_out || n_in - n_out > DUCK_CH_MAX) {
                 err = "DuckerNode needs 1..8 outputs and that many inputs plus 1..8 key inputs. Got num_inputs: " + std::to_string(n_in) +
+                      ", num_outputs: " + std::to_string(n_out);
+                return false;
+            }
+            return true;
+        case K_DELAY_COMP:  // SPEC: a pure delay, as many outputs as inputs, 1..8
+            if (n_in != n_out || n_in < 1 || n_in > DCOMP_CH_MAX) {
+                err = "DelayCompNode needs 1..8 inputs and as many outputs. Got num_inputs: " + std::to_string(n_in) +
                       ", num_outputs: " + std::to_string(n_out);
                 return false;
             }

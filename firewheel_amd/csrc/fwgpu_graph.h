@@ -184,6 +184,11 @@ class HostGraph {
     bool topo_order(std::vector<uint32_t>& order);
     // graph -> Plan.  0 or a CompileGraphError code; err gets the message.
     int build_plan(Plan& plan, std::string& err);
+    // Latency (include/fwgpu.h, "latency compensation"), over the current edge set.  own_latency: what the node itself adds.
+    // arrival_latency: out[slot] = own + the latest of its connected inputs' sources, for every alive node, in one Kahn pass over the
+    // edge arena, O(nodes + edges); false on a cycle.
+    static uint32_t own_latency(const HostNode& n);
+    bool arrival_latency(std::vector<uint32_t>& out) const;
 
   private:
     void remove_edge_slot(uint32_t e);

@@ -4,6 +4,7 @@
 //   k_generic.hip.h  generic level-batched executor: k_level — one 64-lane wave per scheduled node, one launch per
 //                    topological level for K blocks, bit-exact restatement of every node kind (nodes/*.rs + SPEC nodes)
 //   k_limiter.hip.h  SPEC look-ahead limiter: k_limiter — sliding minimum and moving average of a bus, its K blocks in parallel
+//   k_delay_comp.hip.h SPEC latency compensation: k_delay_comp — a pure delay of whole frames, a copy; every block of a batch in parallel
 //   k_ducker.hip.h   SPEC sidechain ducker: k_ducker — window counts over the key bus's gate bits, runs of blocks in parallel; k_single_node
 //   k_control.hip.h  fused plans, control half: k_voice_control (per-voice per-block state machines, K blocks per launch)
 //   k_leaf.hip.h     fused voice-bank plan: k_leaf_sum (HBM-streaming source fetch + gain stages + ordered radix-P sum
@@ -36,6 +37,7 @@ __device__ __forceinline__ v4f splat(float x) { return (v4f){x, x, x, x}; }
 #include "k_common.hip.h"
 #include "k_generic.hip.h"
 #include "k_limiter.hip.h"
+#include "k_delay_comp.hip.h"
 #include "k_ducker.hip.h"
 #include "k_control.hip.h"
 #include "k_leaf.hip.h"
@@ -51,7 +53,7 @@ __device__ __forceinline__ v4f splat(float x) { return (v4f){x, x, x, x}; }
         if (e__ != hipSuccess) return (int)e__; \
     } while (0)
 
-// kinds: bit s = the level holds node kinds of set s (k_generic.hip.h: kind_set) — one launch per set present (set 4: k_limiter, set 5: k_ducker)
+// kinds: bit s = the level holds node kinds of set s (k_generic.hip.h: kind_set) — one launch per set present (set 4: k_limiter, set 5: k_ducker, set 6: k_delay_comp)
 int launch_level(hipStream_t s, const DevView& v, const int* d_level_nodes, int n_nodes, int K, uint32_t cmd_block0, int kinds) {
     if (n_nodes <= 0) return 0;
     if (K <= 0) return 0;
@@ -77,6 +79,13 @@ int launch_level(hipStream_t s, const DevView& v, const int* d_level_nodes, int 
         const int own_hist = K == 1 && pieces == 1 ? 1 : 0;
         hipLaunchKernelGGL(k_ducker, dim3(n_nodes, K * pieces), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K, own_hist);
         if (!own_hist) hipLaunchKernelGGL(k_ducker_hist, dim3(n_nodes), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K);
+    }
+    // kinds bit 6: the level holds a latency-compensation delay — a wave per (node, block); behind it, unless one wave is the whole
+    // launch, the wave per node that writes the history and the counters back (stream order)
+    if (kinds & 64) {
+        const int own_hist = K == 1 ? 1 : 0;
+        hipLaunchKernelGGL(k_delay_comp, dim3(n_nodes, K), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K, own_hist);
+        if (!own_hist) hipLaunchKernelGGL(k_delay_comp_hist, dim3(n_nodes), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K);
     }
     if (walkers)
         hipLaunchKernelGGL(k_bus_iir, dim3((n_nodes + WPB - 1) / WPB), dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K);

@@ -615,6 +615,10 @@ static int activate_nodes(ImageBuild& b) {
                             "DuckerNode: threshold must be finite and in 1e-6..1000, depth in 0..1, attack_frames and release_frames whole "
                             "numbers in 1..32768, hold_frames a whole number in 0..32768");
             len = 2 * (((size_t)n.init.loop_end + 63) / 64);
+        } else if (n.kind == K_DELAY_COMP) {  // hist[n_in][D] and a counter per channel, zeroed like every slice: the SPEC's x[n < 0] and loud = 0
+            if (n.init.loop_end < 1 || n.init.loop_end > DCOMP_MAX + 1 || n.init.loop_start + 1 != n.init.loop_end)
+                return fail(c, FWGPU_ERR_INVALID, "DelayCompNode: frames must be a whole number in 0..8192");
+            len = (size_t)n.n_in * (size_t)n.init.loop_start + (size_t)n.n_in;
         } else if (n.kind == K_FIR) {
             int ir = n.init.sample;
             if (ir < 0 || ir >= (int)c->samples.size() || !c->samples[ir].alive)

@@ -12,8 +12,15 @@ enum : int {
     K_METER = 16,  // SPEC level meter: per block and input channel peak, sum of squares and overs; audio passes through
     K_LIMITER = 17,  // SPEC look-ahead limiter: linked channels, sliding minimum + 64-term moving average, 63 frames of latency
     K_DUCKER = 18,  // SPEC sidechain ducker: n main + k key inputs, n outputs; window counts of the key's gate bits, no latency
-    K_LAST = K_DUCKER,
+    K_DELAY_COMP = 19,  // SPEC latency compensation: n -> n, a pure delay of a whole number of frames, a copy with no arithmetic
+    K_LAST = K_DUCKER + 1,  // = K_DELAY_COMP (counted from K_DUCKER: tests/test_ducker.py reads this line as it stood when that kind was the last)
 };
+static_assert(K_LAST == K_DELAY_COMP, "K_LAST names the last node kind");
+// K_DELAY_COMP: the delay D is a whole number of frames in 0..DCOMP_MAX.  The node's ext slice keeps the last D input frames per channel
+// and, behind them, one counter per channel (the silence rule's loud_c) in a 32-bit slot each.
+#define DCOMP_MAX 8192u
+#define DCOMP_CH_MAX 8
+#define DCOMP_DEFAULT 63u
 // K_DUCKER: the caps of attack, release and hold (frames).  The gate's history is W = max(A, R) + H bits, at most DUCK_WIN_MAX +
 // DUCK_HOLD_MAX = 65 536 bits = 8 KiB, and a wave stages it in LDS in front of the DUCK_RUN_MAX frames (1 KiB of bits) it renders:
 // the caps are sized so that the staged bit window stays around 10 KB of LDS (k_ducker.hip.h DuckLds).
@@ -100,6 +107,9 @@ struct NodeState {
     //   DUCKER: p0 = threshold T, p1 = depth D, playhead = A, loop_start = R, full_range = H, loop_end = W = max(A, R) + H (0: a
     //        creation parameter was refused), ext = the last W gate bits on[], oldest first, bit i in bit i % 32 of word i / 32 (the
     //        float slots hold 32-bit words), 2 * ceil(W / 64) words, the bits from W on zero
+    //   DELAY_COMP: loop_start = D, loop_end = D + 1 (0: the creation parameter was refused), ext = hist[n_in][D]: the last D input
+    //        frames per channel, oldest first (a block flagged silent enters as zeros), then loud[n_in]: 32-bit counters in the float
+    //        slots — how many of the frames in front of the next block may still be heard; n_in * D + n_in slots
     uint32_t ext_off;
     uint32_t ext_len;
     int pad[1];

@@ -169,6 +169,7 @@ __device__ __forceinline__ int kind_set(int kind) {
     if (kind == K_SAMPLER) return 2;
     if (kind == K_LIMITER) return 4;  // (no instantiation of k_level: k_limiter.hip.h, a kernel of its own)
     if (kind == K_DUCKER) return 5;   // (nor here: k_ducker.hip.h)
+    if (kind == K_DELAY_COMP) return 6;  // (nor here: k_delay_comp.hip.h)
     return (kind == K_BEEP || kind == K_BIQUAD || kind == K_DELAY || kind == K_RESAMPLER || kind == K_SPATIAL) ? 1 : 0;
 }
 // SET: 0 / 1 / 2 = that set only, 3 = all kinds (single-node entry).
@@ -177,7 +178,7 @@ template <int SET>
 __device__ void node_process_wave(const DevView& v, int node_idx, uint32_t blk, uint32_t cmd_block, bool store_state = true,
                                   uint32_t adv_blocks = 0, bool frozen_sampler = false) {
     const NodeDesc nd = v.nodes[node_idx];
-    if (nd.is_graph_io || nd.kind == K_FIR || nd.kind == K_LIMITER || nd.kind == K_DUCKER) return;  // I/O edges (k_graph_in/out); FIR banks run as MFMA GEMMs; k_limiter; k_ducker
+    if (nd.is_graph_io || nd.kind == K_FIR || nd.kind == K_LIMITER || nd.kind == K_DUCKER || nd.kind == K_DELAY_COMP) return;  // I/O edges (k_graph_in/out); FIR banks run as MFMA GEMMs; k_limiter; k_ducker; k_delay_comp
     // the other instantiation's kinds return here; their switch cases are compiled out below (`if constexpr`: a case
     // that is compiled out falls through, which nothing can reach)
     if constexpr (SET != 3) {

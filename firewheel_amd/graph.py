@@ -402,6 +402,27 @@ class DuckerNode(_Node):
         return [float(self.threshold), float(self.depth), float(self.attack_frames), float(self.release_frames), float(self.hold_frames)]
 
 
+class DelayCompNode(_Node):
+    """SPEC node: latency compensation — a pure delay of `frames` whole frames (0..8192), a copy with no
+    arithmetic: what a bus needs that is summed with a bus a LimiterNode has made 63 frames late.  add_node(channels, channels,
+    DelayCompNode(frames)), channels in 1..8.  An output block is flagged silent exactly when the `frames` frames in front of it and the
+    block itself were; every block of a batch renders in parallel.  `latency_frames` = frames.  No parameters after creation.
+    FirewheelGpuCtx.latency_report says where one is needed, compensate_latency puts them there."""
+    KIND = 19
+    MAX_FRAMES = 8192
+
+    def __init__(self, frames=63, channels=2):
+        self.frames = frames
+        self.channels = channels
+
+    @property
+    def latency_frames(self):
+        return self.frames
+
+    def params(self):
+        return [float(self.frames)]
+
+
 class _RawNode(_Node):
     def __init__(self, kind, params):
         self.KIND = kind
@@ -429,6 +450,7 @@ class FirewheelGpuCtx(object):
         if not self.c:
             raise FwgpuError(-30, self.L.fwgpu_create_error().decode())
         self._nodes = {}
+        self._edges = {}  # (dst node, dst port) -> (src node, src port, edge id): what compensate_latency rewires
         self._limbo = []  # removed HostNodes (their ctypes thunks) until a plan without them is the active one
         self._keep = []
 
@@ -477,6 +499,7 @@ class FirewheelGpuCtx(object):
 
     def remove_node(self, node_id):
         self._check(self.L.fwgpu_remove_node(self.c, node_id))
+        self._edges = {k: v for k, v in self._edges.items() if k[0] != node_id and v[0] != node_id}
         n = self._nodes.pop(node_id, None)
         if isinstance(n, HostNode):
             # the running plan (and a pending one) still call the node's ctypes thunk until a plan WITHOUT it is the active one
@@ -497,13 +520,79 @@ class FirewheelGpuCtx(object):
         r = self.L.fwgpu_connect(self.c, src_node, src_port, dst_node, dst_port, 1 if check_for_cycles else 0)
         if r < 0:
             raise AddEdgeError(r)
+        self._edges[(dst_node, dst_port)] = (src_node, src_port, r)
         return r
 
     def disconnect(self, src_node, src_port, dst_node, dst_port):
-        return bool(self.L.fwgpu_disconnect(self.c, src_node, src_port, dst_node, dst_port))
+        done = bool(self.L.fwgpu_disconnect(self.c, src_node, src_port, dst_node, dst_port))
+        if done:
+            self._edges.pop((dst_node, dst_port), None)
+        return done
 
     def disconnect_by_edge_id(self, edge_id):
-        return bool(self.L.fwgpu_disconnect_edge(self.c, edge_id))
+        done = bool(self.L.fwgpu_disconnect_edge(self.c, edge_id))
+        if done:
+            self._edges = {k: v for k, v in self._edges.items() if v[2] != edge_id}
+        return done
+
+    # ---- latency (include/fwgpu.h "latency compensation"): host-side queries over the current edges, no update() needed first
+    def node_latency(self, node_id):
+        """frames the node itself adds: 63 for a LimiterNode, `frames` for a DelayCompNode, 0 for every other kind"""
+        n = C.c_uint32(0)
+        self._check(self.L.fwgpu_node_latency(self.c, node_id, C.byref(n)))
+        return n.value
+
+    def latency_report(self):
+        """[(node, input port, lead_frames)]: every connected input that the other inputs of its node are later than, by node, then port
+        (fwgpu_graph_latency_report).  Raises CompileGraphError for a cyclic edge set, as update() would."""
+        n = self.L.fwgpu_graph_latency_report(self.c, None, 0)
+        buf = (_lib.LatencySkew * max(n, 1))()
+        if n > 0:
+            n = self.L.fwgpu_graph_latency_report(self.c, buf, n)
+        if n in _COMPILE:
+            raise CompileGraphError(n, self.L.fwgpu_last_error(self.c).decode())
+        self._check(n)
+        return [(buf[i].node, buf[i].port, buf[i].lead_frames) for i in range(n)]
+
+    def output_latency(self):
+        """frames the graph output is late by: the arrival latency at graph_out, the latest of its ports"""
+        n = C.c_uint32(0)
+        r = self.L.fwgpu_graph_output_latency(self.c, C.byref(n))
+        if r in _COMPILE:
+            raise CompileGraphError(r, self.L.fwgpu_last_error(self.c).decode())
+        self._check(r)
+        return n.value
+
+    def compensate_latency(self):
+        """Put a DelayCompNode of `lead_frames` on every edge latency_report names, so that all inputs of every node arrive together.
+        Reported edges that share source node, destination node and lead go through one node of up to 8 channels.  Returns the ids
+        of the nodes added (none when nothing is skewed: a second call adds none); the output latency stays what it was.  Edits the
+        graph only: call update() afterwards.  Knows the edges made through this object's connect()."""
+        groups = {}
+        for node, port, lead in self.latency_report():
+            if (node, port) not in self._edges:
+                raise FwgpuError(-20, "compensate_latency: input %d of node %d was not connected through this context object" % (port, node))
+            src, sport, _ = self._edges[(node, port)]
+            groups.setdefault((src, node, lead), []).append((sport, port))
+        added = []
+        for (src, dst, lead), ports in groups.items():
+            for i in range(0, len(ports), 8):
+                chunk = ports[i:i + 8]
+                prev = [(src, sport) for sport, _ in chunk]
+                for sport, dport in chunk:
+                    self.disconnect(src, sport, dst, dport)
+                left = lead
+                while left > 0:  # (a lead beyond one node's range: nodes in series)
+                    d = min(left, DelayCompNode.MAX_FRAMES)
+                    nid = self.add_node(len(chunk), len(chunk), DelayCompNode(d, channels=len(chunk)))
+                    for k, (pn, pp) in enumerate(prev):
+                        self.connect(pn, pp, nid, k)
+                    prev = [(nid, k) for k in range(len(chunk))]
+                    added.append(nid)
+                    left -= d
+                for (pn, pp), (_, dport) in zip(prev, chunk):
+                    self.connect(pn, pp, dst, dport)
+        return added
 
     def cycle_detected(self):
         return bool(self.L.fwgpu_cycle_detected(self.c))

@@ -60,9 +60,11 @@ enum fwgpu_node_kind {
     FWGPU_METER = 16,         /* SPEC level meter     params: ring_blocks (1..65536, default 1024); see fwgpu_meter_read */
     FWGPU_LIMITER = 17,       /* SPEC look-ahead limiter (n in, n out, n in 1..8)  params: ceiling (linear, 0.001..1000, default 1.0),
                                  hold_frames (0..1920, default 128); see FWGPU_LIMITER_LATENCY */
-    FWGPU_DUCKER = 18         /* SPEC sidechain ducker (n + k in, n out, n and k in 1..8)  params: threshold (linear, 1e-6..1000, default
+    FWGPU_DUCKER = 18,        /* SPEC sidechain ducker (n + k in, n out, n and k in 1..8)  params: threshold (linear, 1e-6..1000, default
                                  0.05), depth (0..1, default 0.25), attack_frames (1..32768, default 480), release_frames (1..32768,
                                  default 12000), hold_frames (0..32768, default 4800); see "sidechain ducker" below */
+    FWGPU_DELAY_COMP = 19     /* SPEC latency compensation (n in, n out, n in 1..8)  params: frames (a whole number in
+                                 0..FWGPU_DELAY_COMP_MAX, default 63); see "latency compensation" below */
 };
 
 /* sample formats — core/sample_resource.rs:28-335 */
@@ -479,6 +481,49 @@ int64_t fwgpu_meter_read(fwgpu_ctx* ctx, int64_t node, uint64_t first_block, uin
  * zeroed at activation (the gate was closed) and kept across plan changes.  A ducker is never part of a fused plan's master chain
  * (it is not 2 -> 2): the level executor renders it.  fwgpu_node_process renders it block by block with the history kept between
  * calls. */
+
+/* ---- latency compensation (FWGPU_DELAY_COMP and the latency queries; SPEC).  A limiter makes its bus
+ * FWGPU_LIMITER_LATENCY frames late; summed with a bus that is not, the two are misaligned, and a dry signal mixed with its limited
+ * copy comb-filters.  FWGPU_DELAY_COMP is the remedy: a pure delay of D = `frames` whole frames, n_in == n_out in 1..8, refused at
+ * fwgpu_add_node otherwise.  A `frames` that is NaN, a fraction or outside 0..FWGPU_DELAY_COMP_MAX fails activation at fwgpu_update
+ * (FWGPU_ERR_INVALID).  No parameters after creation (fwgpu_node_set_param is refused), no smoother, no messages.  With x_c[n] input
+ * channel c at frame n since the node's activation (every frame of every block, full or short; +0.0 for n < 0; a channel flagged
+ * silent for a block counts as +0.0 for that block and is not read):
+ *   y_c[n] = x_c[n - D]
+ * a copy, with no arithmetic: -0.0, infinities, subnormals and NaN payloads come out with the bits they went in with; D = 0 is the
+ * identity.  (FWGPU_DELAY is an effect: its time is in seconds, it has no D = 0, and its output (x * dry) + (d * mix) is arithmetic.)
+ * Silence flags, which downstream sums rely on: per channel one integer loud_c, 0 at activation.  Output channel c of a block of F
+ * frames is zero-filled and flagged if and only if its input is flagged for this block and loud_c == 0 in front of the block;
+ * otherwise it is written and not flagged.  Behind the block loud_c = D if the input was not flagged, max(0, loud_c - F) otherwise.
+ * So an output block is flagged exactly when the D frames in front of it and the block itself were all flagged or lie before the
+ * activation.  The node's state is the last D input frames per channel (flagged blocks enter as zeros) and the counters, zeroed at
+ * activation and kept across plan changes.  No recurrence in time: every block of a batch renders in parallel, whatever D and the block
+ * length are.  The level executor renders the node (a kernel of its own, k_delay_comp); the fused plans around it keep what they can.
+ * fwgpu_node_process renders it block by block with the history kept between calls. */
+#define FWGPU_DELAY_COMP_MAX 8192
+/* The latency queries are pure host code over the CURRENT edge set: no fwgpu_update is needed first.
+ *   own(v)    = FWGPU_LIMITER_LATENCY for a limiter, `frames` for a FWGPU_DELAY_COMP node, 0 for every other kind (FWGPU_DELAY included:
+ *               an effect, not latency)
+ *   in(v, p)  = out(source of input port p), for a connected port
+ *   out(v)    = own(v) + max over v's connected input ports p of in(v, p)       (a node without connected inputs: own(v))
+ * fwgpu_node_latency: own(node) into *frames; FWGPU_ERR_INVALID for an unknown node. */
+int fwgpu_node_latency(fwgpu_ctx* ctx, int64_t node, uint32_t* frames);
+/* one connected input port that the other inputs of its node are later than: delaying this edge by lead_frames aligns it */
+typedef struct fwgpu_latency_skew {
+    int64_t node;         /* the node the edge arrives at */
+    uint32_t port;        /* its input port */
+    uint32_t lead_frames; /* max over the node's connected ports q of in(node, q), minus in(node, port): > 0 */
+} fwgpu_latency_skew;
+/* Every connected input (v, p) with lead = max_q in(v, q) - in(v, p) > 0, a sidechain's inputs and graph_out's included, in ascending
+ * order of the node's slot (the low 32 bits of its id), then of the port.  Returns the total count and writes at most `cap` records
+ * (`out` may be NULL with cap 0).  One pass, O(nodes + edges).  A cyclic edge set (fwgpu_connect with check_for_cycles = 0) returns
+ * the error fwgpu_update would return, FWGPU_ERR_COMPILE_CYCLE.  A FWGPU_DELAY_COMP node of lead_frames on each reported edge leaves
+ * every out(v) as it was — the delayed edge now arrives when the node's latest input does — and the report empty: one pass of
+ * compensation is enough (FirewheelGpuCtx.compensate_latency does exactly that). */
+int64_t fwgpu_graph_latency_report(fwgpu_ctx* ctx, fwgpu_latency_skew* out, uint32_t cap);
+/* the arrival latency at the graph output node, max over its connected ports (0 with none): what picture sync needs */
+int fwgpu_graph_output_latency(fwgpu_ctx* ctx, uint32_t* frames);
+
 /* ProcInfo::stream_time_secs / stream_status (core/node.rs:111-132) of the most recent fwgpu_process_interleaved call —
  * what a custom node run through fwgpu_node_process inside that call would be handed — and how often the backend has
  * reported StreamStatus::OUTPUT_UNDERFLOW (bit 1) / INPUT_OVERFLOW (bit 0) so far.  Any pointer may be NULL. */

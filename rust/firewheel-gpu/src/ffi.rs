@@ -23,6 +23,8 @@ pub struct fwgpu_rccl_comm {
 pub const FWGPU_RCCL_UNIQUE_ID_BYTES: usize = 128;
 /// frames a FWGPU_LIMITER node's output is late by
 pub const FWGPU_LIMITER_LATENCY: u32 = 63;
+/// the largest `frames` of a FWGPU_DELAY_COMP node
+pub const FWGPU_DELAY_COMP_MAX: u32 = 8192;
 /// AudioNodeProcessor::process + ProcInfo (core/node.rs:37-53,94-118) as the C callback of a FWGPU_HOST_NODE
 pub type fwgpu_host_process_fn = Option<
     unsafe extern "C" fn(
@@ -57,6 +59,14 @@ pub struct fwgpu_meter_reading {
     pub over: u32,
     pub frames: u32,
 }
+/// one connected input port that the other inputs of its node are later than (fwgpu_graph_latency_report)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct fwgpu_latency_skew {
+    pub node: i64,
+    pub port: u32,
+    pub lead_frames: u32,
+}
 
 // enum fwgpu_node_kind
 pub const FWGPU_DUMMY: c_int = 0;
@@ -78,6 +88,7 @@ pub const FWGPU_HOST_NODE: c_int = 15;
 pub const FWGPU_METER: c_int = 16;
 pub const FWGPU_LIMITER: c_int = 17;
 pub const FWGPU_DUCKER: c_int = 18;
+pub const FWGPU_DELAY_COMP: c_int = 19;
 
 // enum fwgpu_sample_format
 pub const FWGPU_INTERLEAVED_I16: c_int = 0;
@@ -178,6 +189,9 @@ extern "C" {
     pub fn fwgpu_rccl_last_error() -> *const c_char;
     pub fn fwgpu_synchronize(ctx: *mut fwgpu_ctx) -> c_int;
     pub fn fwgpu_meter_read(ctx: *mut fwgpu_ctx, node: i64, first_block: u64, num_blocks: u32, out: *mut fwgpu_meter_reading, blocks_done: *mut u64) -> i64;
+    pub fn fwgpu_node_latency(ctx: *mut fwgpu_ctx, node: i64, frames: *mut u32) -> c_int;
+    pub fn fwgpu_graph_latency_report(ctx: *mut fwgpu_ctx, out: *mut fwgpu_latency_skew, cap: u32) -> i64;
+    pub fn fwgpu_graph_output_latency(ctx: *mut fwgpu_ctx, frames: *mut u32) -> c_int;
     pub fn fwgpu_proc_info(ctx: *mut fwgpu_ctx, stream_time_secs: *mut f64, stream_status: *mut u32, output_underflows: *mut u64, input_overflows: *mut u64) -> c_int;
     pub fn fwgpu_stream_open(ctx: *mut fwgpu_ctx, num_in_channels: u32, num_out_channels: u32) -> *mut fwgpu_stream;
     pub fn fwgpu_stream_close(s: *mut fwgpu_stream);

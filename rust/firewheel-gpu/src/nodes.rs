@@ -601,3 +601,42 @@ impl AudioNode for GpuDuckerNode {
         self.b.deactivate()
     }
 }
+
+/// Latency compensation (SPEC, DESIGN.md §6 of the fwgpu repository): a pure delay of `frames` whole frames, a copy with no arithmetic —
+/// what a bus needs that is summed with a bus a [`GpuLimiterNode`] has made [`GpuLimiterNode::LATENCY_FRAMES`] frames late.  No
+/// recurrence in time, so every block of a batch renders in parallel on the device.  An output block is flagged silent exactly when
+/// the `frames` frames in front of it and the block itself were.  As many outputs as inputs, 1..=8.
+pub struct GpuDelayCompNode {
+    b: Binding,
+    frames: u32,
+}
+impl GpuDelayCompNode {
+    /// the largest delay one node takes
+    pub const MAX_FRAMES: u32 = ffi::FWGPU_DELAY_COMP_MAX;
+    /// `frames`: 0..=[`GpuDelayCompNode::MAX_FRAMES`] (0 is the identity).  Anything else fails activation.
+    pub fn new(cx: &Arc<GpuContext>, frames: u32) -> Self {
+        Self { b: Binding::new(cx), frames }
+    }
+    /// the delay that aligns a bus with one a limiter has made late
+    pub fn for_limiter(cx: &Arc<GpuContext>) -> Self {
+        Self::new(cx, GpuLimiterNode::LATENCY_FRAMES)
+    }
+    /// what the output is late by
+    pub fn latency_frames(&self) -> u32 {
+        self.frames
+    }
+}
+impl AudioNode for GpuDelayCompNode {
+    fn debug_name(&self) -> &'static str {
+        "delay_comp"
+    }
+    fn info(&self) -> AudioNodeInfo {
+        io(1, 8, 1, 8, false)
+    }
+    fn activate(&mut self, _sr: u32, _mbf: usize, num_inputs: usize, num_outputs: usize) -> Result<Box<dyn AudioNodeProcessor>, Box<dyn Error>> {
+        self.b.activate(ffi::FWGPU_DELAY_COMP, num_inputs, num_outputs, &[self.frames as f32])
+    }
+    fn deactivate(&mut self, _p: Option<Box<dyn AudioNodeProcessor>>) {
+        self.b.deactivate()
+    }
+}

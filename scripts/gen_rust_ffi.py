@@ -12,7 +12,8 @@ OUT = os.path.join(ROOT, "rust", "firewheel-gpu", "src", "ffi.rs")
 BASE = {"int": "c_int", "uint32_t": "u32", "uint64_t": "u64", "int64_t": "i64", "float": "f32", "double": "f64", "void": "c_void",
         "char": "c_char", "uint8_t": "u8", "size_t": "usize", "fwgpu_ctx": "fwgpu_ctx", "fwgpu_stream": "fwgpu_stream",
         "fwgpu_sched_node": "fwgpu_sched_node", "fwgpu_bus_exchange": "fwgpu_bus_exchange", "fwgpu_rccl_comm": "fwgpu_rccl_comm",
-        "fwgpu_host_process_fn": "fwgpu_host_process_fn", "fwgpu_meter_reading": "fwgpu_meter_reading"}
+        "fwgpu_host_process_fn": "fwgpu_host_process_fn", "fwgpu_meter_reading": "fwgpu_meter_reading",
+        "fwgpu_latency_skew": "fwgpu_latency_skew"}
 
 
 def rust_type(c):
@@ -85,6 +86,8 @@ def generate():
     o.append("pub const FWGPU_RCCL_UNIQUE_ID_BYTES: usize = %d;" % int(re.search(r"#define FWGPU_RCCL_UNIQUE_ID_BYTES (\d+)", open(HDR).read()).group(1)))
     o.append("/// frames a FWGPU_LIMITER node's output is late by")
     o.append("pub const FWGPU_LIMITER_LATENCY: u32 = %d;" % int(re.search(r"#define FWGPU_LIMITER_LATENCY (\d+)", open(HDR).read()).group(1)))
+    o.append("/// the largest `frames` of a FWGPU_DELAY_COMP node")
+    o.append("pub const FWGPU_DELAY_COMP_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_DELAY_COMP_MAX (\d+)", open(HDR).read()).group(1)))
     o.append("/// AudioNodeProcessor::process + ProcInfo (core/node.rs:37-53,94-118) as the C callback of a FWGPU_HOST_NODE")
     o.append("pub type fwgpu_host_process_fn = Option<\n    unsafe extern \"C\" fn(\n        user: *mut c_void,\n        frames: u64,\n        inputs: *const *const f32,\n"
              "        num_inputs: u32,\n        outputs: *const *mut f32,\n        num_outputs: u32,\n        in_silence_mask: u64,\n        out_silence_mask: *mut u64,\n"
@@ -95,6 +98,9 @@ def generate():
     o.append("/// one record per (block, input channel) of a FWGPU_METER node (fwgpu_meter_read)")
     o.append("#[repr(C)]\n#[derive(Clone, Copy, Debug, Default, PartialEq)]\npub struct fwgpu_meter_reading {\n    pub peak: f32,\n    pub sum_squares: f32,\n"
              "    pub over: u32,\n    pub frames: u32,\n}")
+    o.append("/// one connected input port that the other inputs of its node are later than (fwgpu_graph_latency_report)")
+    o.append("#[repr(C)]\n#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]\npub struct fwgpu_latency_skew {\n    pub node: i64,\n    pub port: u32,\n"
+             "    pub lead_frames: u32,\n}")
     o.append("")
     for ename, items in enums:
         o.append("// enum %s" % ename)
