@@ -195,14 +195,21 @@ int fwgpu_bus_allgather_ordered(fwgpu_rccl_comm* m, const float* d_bus, const ui
     const uint32_t n_blocks = (uint32_t)((n_floats + per - 1) / per);
     const size_t n_sil = ((size_t)n_blocks * n_channels + 15) & ~(size_t)15;  // (16-byte slots: every rank's flags start aligned)
     const size_t W = (size_t)m->world;
-    if (m->gathered.cap < W * n_floats * sizeof(float) || m->gathered_sil.cap < W * n_sil || m->zero_sil.cap < n_sil) {
+    if (m->gathered.cap < W * n_floats * sizeof(float) || m->gathered_sil.cap < W * n_sil) {
         RtHold hold(c);  // (first call of this size only)
         HIPC(c, hipStreamSynchronize(c->stream));
         HIPC(c, m->gathered.ensure_n("rccl_gathered", W * n_floats * sizeof(float)));
         HIPC(c, m->gathered_sil.ensure_n("rccl_gathered_sil", W * n_sil));
-        HIPC(c, m->zero_sil.ensure_n("rccl_zero_sil", n_sil));
-        HIPC(c, hipMemsetAsync(m->zero_sil.p, 0, n_sil, c->stream));
         HIPC(c, hipMemsetAsync(m->gathered_sil.p, 0, W * n_sil, c->stream));
+    }
+    // zero_sil is sent, never written: cleared over its WHOLE capacity whenever it is (re)allocated, and tested on its own — DevBuf
+    // allocates with headroom, so a later call with more blocks may fit every capacity, and whatever it sends must be zeros too
+    // (a non-zero byte read as a flag clears a block, or drops a port from the n-port sum).  A size seen before costs one compare.
+    if (m->zero_sil.cap < n_sil) {
+        RtHold hold(c);
+        HIPC(c, hipStreamSynchronize(c->stream));
+        HIPC(c, m->zero_sil.ensure_n("rccl_zero_sil", n_sil));
+        HIPC(c, hipMemsetAsync(m->zero_sil.p, 0, m->zero_sil.cap, c->stream));
     }
     int rc = g_api.AllGather(d_bus, m->gathered.p, (size_t)n_floats, NCCL_FLOAT32, m->comm, c->stream);
     if (rc) return nccl_fail(c, rc, "ncclAllGather(bus)");

@@ -213,6 +213,8 @@ __global__ __launch_bounds__(256) void k_bus_reduce(char* __restrict__ base, Exc
             for (int p = 1; p < g.world; ++p)
                 if (!(blk_floats && masked && silent(p, b, c))) a = a + part(p)[j];
             out[j] = all ? 0.f : a;
+            // (a block's first frame can lie in the tail — one-frame blocks, 9 x 1 x 2 floats: its flags are written here then)
+            if (out_sil && blk_floats && j % blk_floats < n_ch) out_sil[(size_t)b * n_ch + c] = all ? 1 : (g.world == 1 ? (silent(0, b, c) ? 1 : 0) : 0);
         }
 }
 
@@ -247,6 +249,7 @@ __global__ __launch_bounds__(256) void k_bus_sum_ordered(BusParts bp, SilView sv
             for (int p = 1; p < bp.n; ++p)
                 if (!(blk_floats && masked && silent(p, b, c))) a = a + bp.part[p][j];
             out[j] = all ? 0.f : a;
+            if (out_sil && blk_floats && j % blk_floats < n_ch) out_sil[(size_t)b * n_ch + c] = all ? 1 : (bp.n == 1 ? (silent(0, b, c) ? 1 : 0) : 0);
         }
 }
 

@@ -1,5 +1,6 @@
 // TEST DOUBLE (see fakehip/hip/hip_runtime_api.h): the kernel launch wrappers of fwgpu_kernels.hip as counted no-ops.
-// Nothing is computed; the harness only lets the host half of libfwgpu run on the CPU tier.
+// No audio is computed (one exception: launch_bus_sum_ordered, the mix-bus SumNode, restated in scalar C++); the harness only lets the
+// host half of libfwgpu run on the CPU tier.
 #include "../../firewheel_amd/csrc/fwgpu_launch.h"
 #include "../../firewheel_amd/csrc/fwgpu_graph.h"  // PortInts (self-test below)
 
@@ -496,6 +497,46 @@ int launch_bus_sum_ordered(hipStream_t, const BusParts& bp, const uint8_t* const
         for (int r = 0; r < bp.n; ++r)
             if (sil[r]) touch(sil[r], (size_t)n_blocks * n_ch);
         if (d_out_sil) touch(d_out_sil, (size_t)n_blocks * n_ch);
+    }
+    // ... and this one launch IS computed: the top-level R-port SumNode (nodes/sum.rs:41-136 as include/fwgpu.h quotes it), block by
+    // block and channel by channel in scalar f32 — a second statement of the node, written without the kernel's header, so that the
+    // CPU tier can compare what the host code around it (slot offsets, staged flags, missing flags) hands to the launch.
+    if (bp.n <= 0 || n_floats == 0) return 0;
+    const int R = bp.n;
+    const size_t per = sil ? (size_t)frames * n_ch : 0;
+    if (!per) {  // no flags anywhere: nothing is silent, nothing is reported — every port added in port order
+        for (size_t i = 0; i < n_floats; ++i) {
+            float acc = bp.part[0][i];
+            for (int r = 1; r < R; ++r) acc = acc + bp.part[r][i];
+            d_out[i] = acc;
+        }
+        return 0;
+    }
+    for (size_t b = 0; b < n_blocks; ++b) {
+        const size_t lo = b * per, hi = lo + per < n_floats ? lo + per : n_floats;
+        auto silent = [&](int r, uint32_t c) { return sil[r] != nullptr && sil[r][b * n_ch + c] != 0; };
+        bool all_silent = true;
+        for (int r = 0; r < R; ++r)
+            for (uint32_t c = 0; c < n_ch; ++c) all_silent = all_silent && silent(r, c);
+        for (uint32_t c = 0; c < n_ch; ++c) {
+            uint8_t flag = 0;
+            if (all_silent) {  // :52-56 every input channel silent: clear, flag every output
+                for (size_t i = lo + c; i < hi; i += n_ch) d_out[i] = 0.f;
+                flag = 1;
+            } else if (R == 1) {  // :58-65 one port: copy, the mask passes through
+                for (size_t i = lo + c; i < hi; i += n_ch) d_out[i] = bp.part[0][i];
+                flag = silent(0, c) ? 1 : 0;
+            } else {
+                const bool masked = R > 4;  // :67-110 two, three, four ports add unmasked; :111-133 the n-port path skips silent ports
+                for (size_t i = lo + c; i < hi; i += n_ch) {
+                    float acc = bp.part[0][i];
+                    for (int r = 1; r < R; ++r)
+                        if (!(masked && silent(r, c))) acc = acc + bp.part[r][i];
+                    d_out[i] = acc;
+                }
+            }
+            if (d_out_sil) d_out_sil[b * n_ch + c] = flag;
+        }
     }
     return 0;
 }

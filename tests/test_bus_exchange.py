@@ -87,6 +87,23 @@ def random_buses(rng, world, blocks, frames, n_ch=2, ragged=0):
     return parts, sils
 
 
+# (world, blocks, frames, ragged[, n_ch]).  The first list: whole quads inside one block, stereo.  QUAD_CASES: frames * n_ch is no
+# multiple of 4, so a quad of four floats holds the end of one block and the start of the next — or, with one-frame blocks, two
+# (stereo) or four (mono) whole blocks, whose flags one thread writes; 9 x 1 x 2 = 18 floats leaves the LAST block's only frame
+# to the scalar tail; 37-frame stereo blocks (74 floats) straddle in every other block; mono and three channels move f % n_ch
+# off the stereo pattern (21 floats per block: no multiple of 4 nor of 2).
+SUM_CASES = [(1, 3, 64, 0), (2, 4, 64, 0), (3, 5, 48, 2), (4, 4, 256, 0), (5, 6, 64, 3), (8, 8, 100, 1), (64, 2, 32, 0)]
+QUAD_CASES_STEREO = [(1, 9, 1, 0, 2), (5, 9, 1, 0, 2), (3, 7, 37, 0, 2), (8, 7, 37, 2, 2), (5, 6, 3, 0, 2)]
+QUAD_CASES = QUAD_CASES_STEREO + [(2, 8, 5, 0, 1), (6, 8, 1, 0, 1), (5, 4, 7, 0, 3), (4, 4, 7, 1, 3)]
+
+
+def test_quad_cases_do_cross_block_boundaries_inside_a_quad():
+    for world, blocks, frames, ragged, n_ch in QUAD_CASES:
+        per, n = frames * n_ch, blocks * frames * n_ch - ragged
+        assert per % 4 and any((4 * q) // per != (4 * q + 3) // per for q in range(n // 4)), (world, blocks, frames, ragged, n_ch)
+    assert (9 * 1 * 2) % 4 == 2 and (9 * 1 * 2) // 4 * 4 == 8 * 2  # block 8's first (only) frame is the scalar tail of the 9 x 1 x 2 cases
+
+
 def test_model_masked_and_unmasked_paths_differ_only_in_the_sign_of_zero():
     rng = np.random.default_rng(5)
     parts, sils = random_buses(rng, 5, 6, 32)
@@ -260,16 +277,59 @@ def test_bus_sum_ordered_flags_contract_on_the_host_harness():
     from firewheel_amd import FwgpuError
 
     a = hostonly_cx()
-    bufs = [(C.c_float * 512)() for _ in range(3)]
-    sil = [(C.c_uint8 * 8)() for _ in range(3)]
+    # (the harness's launch stub computes this node — a scalar restatement of sum.rs of its own: the values below check the stub, and
+    #  with it what the CPU tier's RCCL tests compare)
+    parts, sils = random_buses(np.random.default_rng(41), 3, 4, 64)
+    bufs = [(C.c_float * 512)(*p) for p in parts]
+    sil = [(C.c_uint8 * 8)(*s.reshape(-1)) for s in sils]
     out = (C.c_float * 512)()
     osil = (C.c_uint8 * 8)()
     pp = [C.addressof(x) for x in bufs]
+
+    def got():
+        return np.frombuffer(out, dtype=np.float32).copy().view(np.uint32), np.frombuffer(osil, dtype=np.uint8).copy().reshape(4, 2)
+
+    def poison():
+        C.memset(out, 0xFF, C.sizeof(out))  # NaNs
+        C.memset(osil, 9, C.sizeof(osil))
+
+    poison()
     a.bus_sum_ordered(pp, C.addressof(out), 512)
+    want, _ = topsum_model(parts, None, 64)
+    assert np.array_equal(got()[0], want.view(np.uint32)) and (got()[1] == 9).all()  # no flags in: none reported
+    poison()
     a.bus_sum_ordered(pp, C.addressof(out), 512, [C.addressof(x) for x in sil], C.addressof(osil), 64, 2)
+    want, want_sil = topsum_model(parts, sils, 64)
+    assert want_sil.any() and np.array_equal(got()[0], want.view(np.uint32)) and np.array_equal(got()[1], want_sil)
+    poison()
     a.bus_sum_ordered(pp, C.addressof(out), 512, [C.addressof(sil[0]), None, None], None, 64, 2)
+    want, _ = topsum_model(parts, [sils[0], None, None], 64)
+    assert np.array_equal(got()[0], want.view(np.uint32)) and (got()[1] == 9).all()
     with pytest.raises(FwgpuError, match="block geometry"):
         a.bus_sum_ordered(pp, C.addressof(out), 512, [C.addressof(x) for x in sil], None, 0, 2)
+    assert a.L.fwh_violation() == b""
+    a.close()
+
+
+@pytest.mark.parametrize("world,blocks,frames,ragged,n_ch", [c + (2,) for c in SUM_CASES if c[0] <= 8] + QUAD_CASES + [(17, 3, 5, 0, 2)])
+def test_host_harness_bus_sum_stub_equals_the_model(world, blocks, frames, ragged, n_ch):
+    """the stub's restatement of the node against the model at the GPU tier's shapes: 1 port, 2..4 ports, the masked n-port path,
+    ragged last blocks, one and three channels"""
+    import ctypes as C
+
+    a = hostonly_cx()
+    parts, sils = random_buses(np.random.default_rng(100 * world + frames), world, blocks, frames, n_ch=n_ch, ragged=ragged)
+    n = parts[0].size
+    want, want_sil = topsum_model(parts, sils, frames, n_ch)
+    flat = [np.ascontiguousarray(s.reshape(-1)) for s in sils]
+    out = np.full(n, np.nan, dtype=np.float32)
+    osil = np.full(blocks * n_ch, 9, dtype=np.uint8)
+    a.bus_sum_ordered([p.ctypes.data for p in parts], out.ctypes.data, n, [s.ctypes.data for s in flat], osil.ctypes.data, frames, n_ch)
+    assert np.array_equal(out.view(np.uint32), want.view(np.uint32))
+    assert np.array_equal(osil.reshape(blocks, n_ch), want_sil)
+    blind, _ = topsum_model(parts, None, frames, n_ch)
+    a.bus_sum_ordered([p.ctypes.data for p in parts], out.ctypes.data, n)
+    assert np.array_equal(out.view(np.uint32), blind.view(np.uint32))
     assert a.L.fwh_violation() == b""
     a.close()
 
@@ -280,37 +340,39 @@ def _dev(torch, a):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world,blocks,frames,ragged", [(1, 3, 64, 0), (2, 4, 64, 0), (3, 5, 48, 2), (4, 4, 256, 0), (5, 6, 64, 3),
-                                                        (8, 8, 100, 1), (64, 2, 32, 0)])
-def test_bus_sum_ordered_flags_kernel_equals_the_model(world, blocks, frames, ragged):
+@pytest.mark.parametrize("world,blocks,frames,ragged,n_ch", [pytest.param(*c, 2, id="-".join(map(str, c))) for c in SUM_CASES] +
+                         [pytest.param(*c, id="-".join(map(str, c))) for c in QUAD_CASES])
+def test_bus_sum_ordered_flags_kernel_equals_the_model(world, blocks, frames, ragged, n_ch):
     import torch
 
     rng = np.random.default_rng(100 * world + frames)
-    parts, sils = random_buses(rng, world, blocks, frames, ragged=ragged)
-    want, want_sil = topsum_model(parts, sils, frames)
+    parts, sils = random_buses(rng, world, blocks, frames, n_ch=n_ch, ragged=ragged)
+    want, want_sil = topsum_model(parts, sils, frames, n_ch)
     e = GpuEngine(max_block_frames=64)
     dp = [_dev(torch, p) for p in parts]
     ds = [_dev(torch, s) for s in sils]
     out = torch.full((parts[0].size,), float("nan"), dtype=torch.float32, device="cuda")
-    osil = torch.full((blocks * 2,), 9, dtype=torch.uint8, device="cuda")
+    osil = torch.full((blocks * n_ch,), 9, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
-    e.cx.bus_sum_ordered([p.data_ptr() for p in dp], out.data_ptr(), out.numel(), [s.data_ptr() for s in ds], osil.data_ptr(), frames, 2)
+    e.cx.bus_sum_ordered([p.data_ptr() for p in dp], out.data_ptr(), out.numel(), [s.data_ptr() for s in ds], osil.data_ptr(), frames, n_ch)
     e.cx.synchronize()
     assert np.array_equal(out.cpu().numpy().view(np.uint32), want.view(np.uint32))
-    assert np.array_equal(osil.cpu().numpy().reshape(blocks, 2), want_sil)
+    assert np.array_equal(osil.cpu().numpy().reshape(blocks, n_ch), want_sil)
     # the flag-less form treats no port as silent (what round 2 shipped): the model without masks
-    blind, _ = topsum_model(parts, None, frames)
+    blind, _ = topsum_model(parts, None, frames, n_ch)
     e.cx.bus_sum_ordered([p.data_ptr() for p in dp], out.data_ptr(), out.numel())
     e.cx.synchronize()
     assert np.array_equal(out.cpu().numpy().view(np.uint32), blind.view(np.uint32))
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world,blocks,frames,ragged", [(2, 4, 64, 0), (3, 3, 48, 2), (5, 6, 64, 0), (8, 16, 256, 0), (17, 2, 32, 1)])
+@pytest.mark.parametrize("world,blocks,frames,ragged", [(2, 4, 64, 0), (3, 3, 48, 2), (5, 6, 64, 0), (8, 16, 256, 0), (17, 2, 32, 1)] +
+                         [c[:4] for c in QUAD_CASES_STEREO])
 def test_exchange_virtual_ranks_in_one_process_equal_the_model_on_every_rank(world, blocks, frames, ragged):
     """N contexts on the one device, their exchanges connected by pointer; every rank pushes, then every rank reduces (one
     host thread drives all ranks here; separate hosts simply call step).  Three steps: both data parities and the reuse of
-    the first."""
+    the first.  (k_bus_reduce shares the quad routine of k_bus_sum_ordered but addresses its flags itself: the stereo quad cases
+    run here too.)"""
     import torch
 
     rng = np.random.default_rng(7 * world + blocks)
