@@ -382,7 +382,7 @@ int64_t fwgpu_add_node(fwgpu_ctx* c, int kind, uint32_t n_in, uint32_t n_out, co
             return fail(c, FWGPU_ERR_INVALID, "Resampler node: source longer than 2^31 frames");
     }
     if (n_in > 64 || n_out > 64) return fail(c, FWGPU_ERR_INVALID, "a node has at most 64 ports per side (core/node.rs:62,69)");
-    if (kind == K_LIMITER || kind == K_DUCKER || kind == K_DELAY_COMP) {  // (its shape is refused here; its creation parameters at the next update, as a meter's ring is)
+    if (kind_has_own_kernel(kind)) {  // (its shape is refused here; its creation parameters at the next update, as a meter's ring is)
         std::string err;
         if (!check_activation(kind, n_in, n_out, err)) return fail(c, FWGPU_ERR_INVALID, err);
     }

@@ -125,18 +125,6 @@ struct SampleRec {
 
 constexpr size_t RT_IO_BYTES = 256 * 1024;  // realtime path: calls whose interleaved in/out blocks fit (e.g. 16 x 1024 stereo)
 
-// which instantiation of the node kernel runs a kind (mirrors kind_set in k_generic.hip.h)
-inline int host_kind_set(int kind) {
-    if (kind == K_SAMPLER) return 2;
-    if (kind == K_LIMITER) return 4;  // (no k_level instantiation: k_limiter, launched next to them)
-    if (kind == K_DUCKER) return 5;   // (nor here: k_ducker)
-    if (kind == K_DELAY_COMP) return 6;  // (nor here: k_delay_comp)
-    return (kind == K_BEEP || kind == K_BIQUAD || kind == K_DELAY || kind == K_RESAMPLER || kind == K_SPATIAL) ? 1 : 0;
-}
-// a level's launch bits: the kernel set of the kind, plus bit 3 for a biquad / delay (a bus one goes to the batch walkers); bit 4 (set 4):
-// the level holds a look-ahead limiter, a kernel of its own; bit 5 (set 5): a sidechain ducker, likewise; bit 6 (set 6): a latency-compensation delay, likewise
-inline int host_kind_bits(int kind) { return (1 << host_kind_set(kind)) | ((kind == K_BIQUAD || kind == K_DELAY) ? 8 : 0); }
-
 // A statistics counter the audio thread bumps and the control thread reads (fwgpu_rt_path_stats, fwgpu_lazy_stats,
 // fwgpu_rt_resident_stats): relaxed atomics — a plain uint64_t there is a data race by the letter (the race test runs under
 // ThreadSanitizer).  One writer, so ++ is a load + store, not a locked read-modify-write.
@@ -175,7 +163,7 @@ struct PlanImage {
     // generic plan
     DevBuf d_nodes, d_in_buf, d_out_buf, d_level_nodes, d_pool, d_flags, d_gin_bufs, d_gout_bufs;
     std::vector<int> level_off, level_cnt;
-    std::vector<int> level_kinds;  // bit s: the level holds node kinds of kernel set s (host_kind_set)
+    std::vector<int> level_kinds;  // the level's launch bits (fwgpu_types.h kind_launch_bits)
     int n_gout_bufs = 0, n_gin_bufs = 0;
     std::vector<int> slot_index;   // node slot -> index into plan.nodes, -1 = not in this plan (B1: fwgpu_node_process)
 
@@ -212,7 +200,7 @@ struct PlanImage {
     DevBuf d_up_nodes, d_up_in, d_up_out, d_up_level_nodes, d_root_bufs;
     std::vector<int> up_level_off, up_level_cnt;
     int n_tail = 0;  // master chain after the root SumNode (generic node kernel on the mix bus)
-    std::vector<int> tail_kinds;  // kernel-set bit per master node
+    std::vector<int> tail_kinds;  // launch bits per master node
     DevBuf d_tail_nodes, d_tail_in, d_tail_out, d_tail_idx, d_tail_frozen;
     DevBuf d_frozen_ph;  // ... and its playhead snapshots
     DevBuf d_frozen;  // generic plan: k_frozen_scan's verdict per plan node, valid for the batch in flight

@@ -5,7 +5,8 @@
 //                    topological level for K blocks, bit-exact restatement of every node kind (nodes/*.rs + SPEC nodes)
 //   k_limiter.hip.h  SPEC look-ahead limiter: k_limiter — sliding minimum and moving average of a bus, its K blocks in parallel
 //   k_delay_comp.hip.h SPEC latency compensation: k_delay_comp — a pure delay of whole frames, a copy; every block of a batch in parallel
-//   k_ducker.hip.h   SPEC sidechain ducker: k_ducker — window counts over the key bus's gate bits, runs of blocks in parallel; k_single_node
+//   k_ducker.hip.h   SPEC sidechain ducker: k_ducker — window counts over the key bus's gate bits, runs of blocks in parallel
+//   k_single.hip.h   k_single_node — one node of any kind on scratch buffers (behind the three above: it calls into each)
 //   k_control.hip.h  fused plans, control half: k_voice_control (per-voice per-block state machines, K blocks per launch)
 //   k_leaf.hip.h     fused voice-bank plan: k_leaf_sum (HBM-streaming source fetch + gain stages + ordered radix-P sum
 //                    in registers), k_bus_sum (upper sum tree), k_root_out (root sum + interleave)
@@ -39,6 +40,7 @@ __device__ __forceinline__ v4f splat(float x) { return (v4f){x, x, x, x}; }
 #include "k_limiter.hip.h"
 #include "k_delay_comp.hip.h"
 #include "k_ducker.hip.h"
+#include "k_single.hip.h"
 #include "k_control.hip.h"
 #include "k_leaf.hip.h"
 #include "k_chain.hip.h"
@@ -53,7 +55,7 @@ __device__ __forceinline__ v4f splat(float x) { return (v4f){x, x, x, x}; }
         if (e__ != hipSuccess) return (int)e__; \
     } while (0)
 
-// kinds: bit s = the level holds node kinds of set s (k_generic.hip.h: kind_set) — one launch per set present (set 4: k_limiter, set 5: k_ducker, set 6: k_delay_comp)
+// kinds: the level's launch bits (fwgpu_types.h kind_launch_bits, ORed over its nodes) — one launch per kernel set present
 int launch_level(hipStream_t s, const DevView& v, const int* d_level_nodes, int n_nodes, int K, uint32_t cmd_block0, int kinds) {
     if (n_nodes <= 0) return 0;
     if (K <= 0) return 0;
@@ -65,24 +67,24 @@ int launch_level(hipStream_t s, const DevView& v, const int* d_level_nodes, int 
     uint32_t bpw = pairs >= 16384 ? LEVEL_BPW : (pairs >= 8192 ? 2u : 1u);
     if (pairs >= 262144 && (bpw_wide == 8u || bpw_wide == 16u || bpw_wide == 32u)) bpw = bpw_wide;
     dim3 grid((n_nodes + WPB - 1) / WPB, (K + bpw - 1) / bpw);
-    // kinds bit 3: the level holds a biquad / delay node — in a batch, the ones that are bus effects go to the walkers' kernel
-    const uint32_t walkers = (kinds & 8) && K > 1 ? 1u : 0u;
-    if (kinds & 1) hipLaunchKernelGGL(k_level<0>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, 0u);
-    if (kinds & 2) hipLaunchKernelGGL(k_level<1>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, walkers);
-    if (kinds & 4) hipLaunchKernelGGL(k_level<2>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, 0u);
-    // kinds bit 4: the level holds a look-ahead limiter — a wave per (node, block), its staged gains in LDS of its own
-    if (kinds & 16) hipLaunchKernelGGL(k_limiter, dim3(n_nodes, K), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K);
-    // kinds bit 5: the level holds a sidechain ducker — a wave per (node, run of blocks); behind it, unless one wave is the whole launch,
-    // the wave per node that writes the gate history back (no wave of k_ducker reads the old one any more: stream order)
-    if (kinds & 32) {
+    // the level holds a biquad / delay node — in a batch, the ones that are bus effects go to the walkers' kernel
+    const uint32_t walkers = (kinds & LB_WALKERS) && K > 1 ? 1u : 0u;
+    if (kinds & LB_SET0) hipLaunchKernelGGL(k_level<0>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, 0u);
+    if (kinds & LB_SET1) hipLaunchKernelGGL(k_level<1>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, walkers);
+    if (kinds & LB_SET2) hipLaunchKernelGGL(k_level<2>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, 0u);
+    // a look-ahead limiter — a wave per (node, block), its staged gains in LDS of its own
+    if (kinds & LB_LIMITER) hipLaunchKernelGGL(k_limiter, dim3(n_nodes, K), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K);
+    // a sidechain ducker — a wave per (node, run of blocks); behind it, unless one wave is the whole launch, the wave per node that
+    // writes the gate history back (no wave of k_ducker reads the old one any more: stream order)
+    if (kinds & LB_DUCKER) {
         const int pieces = v.frames > DUCK_RUN_MAX ? (v.frames + DUCK_RUN_MAX - 1) / DUCK_RUN_MAX : 1;
         const int own_hist = K == 1 && pieces == 1 ? 1 : 0;
         hipLaunchKernelGGL(k_ducker, dim3(n_nodes, K * pieces), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K, own_hist);
         if (!own_hist) hipLaunchKernelGGL(k_ducker_hist, dim3(n_nodes), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K);
     }
-    // kinds bit 6: the level holds a latency-compensation delay — a wave per (node, block); behind it, unless one wave is the whole
-    // launch, the wave per node that writes the history and the counters back (stream order)
-    if (kinds & 64) {
+    // a latency-compensation delay — a wave per (node, block); behind it, unless one wave is the whole launch, the wave per node that
+    // writes the history and the counters back (stream order)
+    if (kinds & LB_DELAY_COMP) {
         const int own_hist = K == 1 ? 1 : 0;
         hipLaunchKernelGGL(k_delay_comp, dim3(n_nodes, K), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K, own_hist);
         if (!own_hist) hipLaunchKernelGGL(k_delay_comp_hist, dim3(n_nodes), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K);

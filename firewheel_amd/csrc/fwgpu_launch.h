@@ -123,8 +123,8 @@ struct FusedView {
                  // 3 skip ring RMW, 4 no ring prefetch
 };
 
-int launch_level(hipStream_t s, const DevView& v, const int* d_level_nodes, int n_nodes, int K, uint32_t cmd_block0,
-                 int kinds = 7);
+// kinds: the OR of kind_launch_bits (fwgpu_types.h) over the level's nodes
+int launch_level(hipStream_t s, const DevView& v, const int* d_level_nodes, int n_nodes, int K, uint32_t cmd_block0, int kinds);
 int launch_frozen_scan(hipStream_t s, const DevView& v, int n_nodes, uint32_t cmd_block0, int K, uint8_t* d_frozen,
                        unsigned long long* d_playhead_snap);
 int launch_bus_sum(hipStream_t s, const DevView& v, const int* d_level_nodes, int n_nodes, int K, int n_out);

@@ -605,20 +605,23 @@ static int activate_nodes(ImageBuild& b) {
                 return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "MeterNode: ring_blocks must be a whole number in 1..65536");
             len = (size_t)n.init.loop_end * (size_t)n.n_in * (sizeof(MeterRec) / sizeof(float));
         } else if (n.kind == K_LIMITER) {  // hist[n_in][HK], zeroed like every slice: zeros are the SPEC's x[n < 0]
-            if (n.init.loop_end < LIM_HIST_PAD || n.init.loop_end > LIM_HOLD_MAX + LIM_HIST_PAD)
+            // (this and the next two: fwgpu_types.h X_state_ok / X_ext_len, which the device guards share.  The predicate asks more than
+            //  the range of loop_end that marks a refused parameter; make_state fills nothing that range lets through and the predicate
+            //  refuses, and fwgpu_add_node has refused the shapes)
+            if (!lim_state_ok(n.init, (int)n.n_in, (int)n.n_out))
                 return fail(c, FWGPU_ERR_INVALID,
                             "LimiterNode: ceiling must be finite and in 0.001..1000, hold_frames a whole number in 0..1920");
-            len = (size_t)n.n_in * (size_t)n.init.loop_end;
+            len = lim_ext_len(n.init, (int)n.n_in);
         } else if (n.kind == K_DUCKER) {  // the last W gate bits in 64-bit groups, zeroed like every slice: zeros are the SPEC's closed gate
-            if (n.init.loop_end < 1 || n.init.loop_end > DUCK_WIN_MAX + DUCK_HOLD_MAX)
+            if (!duck_state_ok(n.init, (int)n.n_in, (int)n.n_out))
                 return fail(c, FWGPU_ERR_INVALID,
                             "DuckerNode: threshold must be finite and in 1e-6..1000, depth in 0..1, attack_frames and release_frames whole "
                             "numbers in 1..32768, hold_frames a whole number in 0..32768");
-            len = 2 * (((size_t)n.init.loop_end + 63) / 64);
+            len = duck_ext_len(n.init);
         } else if (n.kind == K_DELAY_COMP) {  // hist[n_in][D] and a counter per channel, zeroed like every slice: the SPEC's x[n < 0] and loud = 0
-            if (n.init.loop_end < 1 || n.init.loop_end > DCOMP_MAX + 1 || n.init.loop_start + 1 != n.init.loop_end)
+            if (!dcomp_state_ok(n.init, (int)n.n_in, (int)n.n_out))
                 return fail(c, FWGPU_ERR_INVALID, "DelayCompNode: frames must be a whole number in 0..8192");
-            len = (size_t)n.n_in * (size_t)n.init.loop_start + (size_t)n.n_in;
+            len = dcomp_ext_len(n.init, (int)n.n_in);
         } else if (n.kind == K_FIR) {
             int ir = n.init.sample;
             if (ir < 0 || ir >= (int)c->samples.size() || !c->samples[ir].alive)
@@ -780,7 +783,7 @@ static int write_node_tables(ImageBuild& b) {
         P.level_cnt.push_back((int)l.size());
         flat.insert(flat.end(), l.begin(), l.end());
         int kinds = 0;
-        for (int i : l) kinds |= host_kind_bits(nd[i].kind);
+        for (int i : l) kinds |= kind_launch_bits(nd[i].kind);
         P.level_kinds.push_back(kinds);
     }
     if ((rc = up_ints(c, P.d_level_nodes, flat))) return rc;
@@ -1062,7 +1065,7 @@ static int install_fused_plan(ImageBuild& b) {
     P.up_root_node = (!fb.up_levels.empty() && fb.up_levels.back().size() == 1) ? fb.up_levels.back()[0] : -1;
     // the master chain
     P.n_tail = (int)fb.tail_nodes.size();
-    for (const NodeDesc& t : fb.tail_nodes) P.tail_kinds.push_back(host_kind_bits(t.kind));
+    for (const NodeDesc& t : fb.tail_nodes) P.tail_kinds.push_back(kind_launch_bits(t.kind));
     if (P.n_tail) {
         P.up_root_node = -1;  // the root's planar result feeds the master chain: no fused root + interleave
         std::vector<int> idx(P.n_tail);
@@ -1105,7 +1108,7 @@ static int install_hybrid_plan(ImageBuild& b) {
         for (int i : l)
             if (!cov[i]) {
                 hflat.push_back(b.split_entry[i] >= 0 ? b.split_entry[i] : i);
-                kinds |= host_kind_bits(b.nd[i].kind);
+                kinds |= kind_launch_bits(b.nd[i].kind);
                 cnt++;
             }
         P.hlevel_cnt.push_back(cnt);

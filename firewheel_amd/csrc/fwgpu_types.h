@@ -13,9 +13,31 @@ enum : int {
     K_LIMITER = 17,  // SPEC look-ahead limiter: linked channels, sliding minimum + 64-term moving average, 63 frames of latency
     K_DUCKER = 18,  // SPEC sidechain ducker: n main + k key inputs, n outputs; window counts of the key's gate bits, no latency
     K_DELAY_COMP = 19,  // SPEC latency compensation: n -> n, a pure delay of a whole number of frames, a copy with no arithmetic
-    K_LAST = K_DUCKER + 1,  // = K_DELAY_COMP (counted from K_DUCKER: tests/test_ducker.py reads this line as it stood when that kind was the last)
+    K_LAST = K_DELAY_COMP,  // the last node kind
 };
-static_assert(K_LAST == K_DELAY_COMP, "K_LAST names the last node kind");
+#if defined(__HIPCC__)
+#define FW_TYPES_HD __host__ __device__
+#else
+#define FW_TYPES_HD  // (the test harnesses compile the host translation units with plain g++)
+#endif
+// Which kernel runs a kind.  The node kernel k_level exists in three instantiations, by register appetite: one kernel for every kind
+// needed 248 VGPRs (2 waves per SIMD — nothing to hide HBM latency behind, 0.9 TB/s on a level of volume nodes).  Set 0: the streaming
+// kinds (volume, pan, sum, hard clip, mono<->stereo, width: 127 VGPRs), set 1: serial recurrences / filter banks / libm (beep, biquad,
+// delay, resampler, spatialiser: 147), set 2: the sampler (every sample format, wraps, tails, ramps).  Sets 4 and above are no
+// instantiation of k_level: a kernel of its own, launched next to them (k_limiter, k_ducker, k_delay_comp).
+FW_TYPES_HD inline int kind_set(int kind) {
+    if (kind == K_SAMPLER) return 2;
+    if (kind == K_LIMITER) return 4;
+    if (kind == K_DUCKER) return 5;
+    if (kind == K_DELAY_COMP) return 6;
+    return (kind == K_BEEP || kind == K_BIQUAD || kind == K_DELAY || kind == K_RESAMPLER || kind == K_SPATIAL) ? 1 : 0;
+}
+FW_TYPES_HD inline bool kind_has_own_kernel(int kind) { return kind_set(kind) >= 4; }
+// a level's launch bits (launch_level's `kinds`): bit s = the level holds a kind of set s, plus LB_WALKERS for a biquad / delay (in a
+// batch, the ones that are bus effects go to the walkers' kernel k_bus_iir)
+enum : int { LB_SET0 = 1, LB_SET1 = 2, LB_SET2 = 4, LB_WALKERS = 8, LB_LIMITER = 16, LB_DUCKER = 32, LB_DELAY_COMP = 64 };
+FW_TYPES_HD inline int kind_launch_bits(int kind) { return (1 << kind_set(kind)) | ((kind == K_BIQUAD || kind == K_DELAY) ? LB_WALKERS : 0); }
+static_assert(LB_LIMITER == 1 << 4 && LB_DUCKER == 1 << 5 && LB_DELAY_COMP == 1 << 6, "a launch bit is 1 << kind_set");
 // K_DELAY_COMP: the delay D is a whole number of frames in 0..DCOMP_MAX.  The node's ext slice keeps the last D input frames per channel
 // and, behind them, one counter per channel (the silence rule's loud_c) in a 32-bit slot each.
 #define DCOMP_MAX 8192u
@@ -102,19 +124,41 @@ struct NodeState {
     //   SPATIAL: p0/p1 = ear gain targets (s0/s1 smooth them), playing = left-ear delay, has_loop = right-ear delay
     //        (frames), ext = the last SP_HIST mono samples
     //   METER: ext = ring[R][n_in] of MeterRec (4 floats each), loop_end = R (0: the creation parameter was refused)
-    //   LIMITER: p0 = ceiling C, loop_start = hold_frames H, loop_end = HK = H + LIM_HIST_PAD (0: a creation parameter was refused),
-    //        ext = hist[n_in][HK]: the last HK input frames per channel, oldest first
-    //   DUCKER: p0 = threshold T, p1 = depth D, playhead = A, loop_start = R, full_range = H, loop_end = W = max(A, R) + H (0: a
-    //        creation parameter was refused), ext = the last W gate bits on[], oldest first, bit i in bit i % 32 of word i / 32 (the
-    //        float slots hold 32-bit words), 2 * ceil(W / 64) words, the bits from W on zero
-    //   DELAY_COMP: loop_start = D, loop_end = D + 1 (0: the creation parameter was refused), ext = hist[n_in][D]: the last D input
-    //        frames per channel, oldest first (a block flagged silent enters as zeros), then loud[n_in]: 32-bit counters in the float
-    //        slots — how many of the frames in front of the next block may still be heard; n_in * D + n_in slots
+    //   LIMITER, DUCKER, DELAY_COMP: loop_end = 0 marks a creation parameter that was refused; the valid states and the slice lengths
+    //        are lim_/duck_/dcomp_state_ok and _ext_len below the struct
+    //   LIMITER: p0 = ceiling C, loop_start = hold_frames H, loop_end = HK; ext = hist[n_in][HK]: the last HK input frames per channel,
+    //        oldest first
+    //   DUCKER: p0 = threshold T, p1 = depth D, playhead = A, loop_start = R, full_range = H, loop_end = W; ext = the last W gate bits
+    //        on[], oldest first, bit i in bit i % 32 of word i / 32 (the float slots hold 32-bit words), the bits from W on zero
+    //   DELAY_COMP: loop_start = D, loop_end = D + 1; ext = hist[n_in][D]: the last D input frames per channel, oldest first (a block
+    //        flagged silent enters as zeros), then loud[n_in]: 32-bit counters in the float slots — how many of the frames in front of
+    //        the next block may still be heard
     uint32_t ext_off;
     uint32_t ext_len;
     int pad[1];
 };
 static_assert(sizeof(NodeState) == 128, "NodeState layout");
+// The bus nodes with a kernel of their own: the states their kernels render (anything else would index the ext slice out of bounds)
+// and the length of that slice, in floats.  ONE statement for the plan build (activate_nodes refuses what fails), the device guards and
+// the host harness (tests/host_harness/launch_stubs.cpp); make_state is what fills the fields.
+FW_TYPES_HD inline bool lim_state_ok(const NodeState& s, int n_in, int n_out) {
+    const uint64_t H = s.loop_start;
+    return H <= LIM_HOLD_MAX && s.loop_end == H + LIM_HIST_PAD && n_in == n_out && n_in >= 1 && n_in <= LIM_CH_MAX;
+}
+FW_TYPES_HD inline uint32_t lim_ext_len(const NodeState& s, int n_in) { return (uint32_t)n_in * (uint32_t)s.loop_end; }
+// (n_out main channels, n_in - n_out key channels; W = max(A, R) + H gate bits in 64-bit groups)
+FW_TYPES_HD inline bool duck_state_ok(const NodeState& s, int n_in, int n_out) {
+    const uint64_t A = s.playhead, R = s.loop_start, W = s.loop_end;
+    const int H = s.full_range;
+    return A >= 1 && A <= DUCK_WIN_MAX && R >= 1 && R <= DUCK_WIN_MAX && H >= 0 && H <= (int)DUCK_HOLD_MAX &&
+           W == (A > R ? A : R) + (uint64_t)H && n_out >= 1 && n_out <= DUCK_CH_MAX && n_in - n_out >= 1 && n_in - n_out <= DUCK_CH_MAX;
+}
+FW_TYPES_HD inline uint32_t duck_ext_len(const NodeState& s) { return 2u * (uint32_t)((s.loop_end + 63) / 64); }
+FW_TYPES_HD inline bool dcomp_state_ok(const NodeState& s, int n_in, int n_out) {
+    const uint64_t D = s.loop_start;
+    return D <= DCOMP_MAX && s.loop_end == D + 1 && n_in == n_out && n_in >= 1 && n_in <= DCOMP_CH_MAX;
+}
+FW_TYPES_HD inline uint32_t dcomp_ext_len(const NodeState& s, int n_in) { return (uint32_t)n_in * (uint32_t)s.loop_start + (uint32_t)n_in; }
 
 struct SampleDesc {  // core/sample_resource.rs:4-26; data is HBM-resident
     const void* data;
@@ -196,11 +240,6 @@ static_assert(sizeof(VoiceDesc) == 80, "VoiceDesc layout");
 // -1.0 sentinel of a stage muted between two filters — means what it means only for one arrangement of stages around the filters,
 // and a list of fields kept by hand had fallen behind the grammar (n_mid: the same nodes with a gain moved across a filter compared
 // equal).  The plan build clears a descriptor before it fills it, so unused stage slots compare equal too.
-#if defined(__HIPCC__)
-#define FW_TYPES_HD __host__ __device__
-#else
-#define FW_TYPES_HD  // (the test harnesses compile the host translation units with plain g++)
-#endif
 FW_TYPES_HD inline bool same_voice_chain(const VoiceDesc& nv, const VoiceDesc& ov) {
     static_assert(sizeof(VoiceDesc) % sizeof(int) == 0 && alignof(VoiceDesc) == alignof(int), "VoiceDesc: ints only, no padding");
     const int* const a = (const int*)&nv;

@@ -1,5 +1,5 @@
 // k_delay_comp.hip.h — SPEC latency compensation (K_DELAY_COMP): a pure delay of D whole frames, a kernel of its own next
-// to k_level, as k_limiter and k_ducker are.  Included by fwgpu_kernels.hip, behind k_limiter.hip.h; it needs no LDS.
+// to k_level, as k_limiter and k_ducker are.  Included by fwgpu_kernels.hip; it needs no LDS.
 //
 // Per channel c and frame n since activation (x_c[n < 0] = +0.0; a channel flagged silent for a block counts as +0.0 for that block and
 // is not read):  y_c[n] = x_c[n - D] — a copy, no arithmetic: -0.0, infinities, subnormals and NaN payloads keep their bits.
@@ -29,13 +29,11 @@ struct DcompP {
     const int* in_buf;
     const int* out_buf;
 };
-// false: state a plan build would not let through (a slice of another size would be indexed out of bounds)
+// false: state a plan build would not let through — the host harness holds it to that (a slice of another size would be indexed out
+// of bounds)
 __device__ __forceinline__ bool dcomp_params(const DevView& v, const NodeDesc& nd, const NodeState& s, DcompP& p) {
-    const uint64_t D = s.loop_start;
-    if (D > DCOMP_MAX || s.loop_end != D + 1 || nd.n_in != nd.n_out || nd.n_in < 1 || nd.n_in > DCOMP_CH_MAX ||
-        s.ext_len != (uint32_t)nd.n_in * (uint32_t)D + (uint32_t)nd.n_in || v.frames < 1 || v.frames > v.stride)
-        return false;
-    p.D = (int)D;
+    if (!dcomp_state_ok(s, nd.n_in, nd.n_out) || s.ext_len != dcomp_ext_len(s, nd.n_in) || v.frames < 1 || v.frames > v.stride) return false;
+    p.D = (int)s.loop_start;
     p.n = nd.n_in;
     p.hist = v.ext + s.ext_off;
     p.loud = (uint32_t*)(p.hist + (size_t)p.n * p.D);

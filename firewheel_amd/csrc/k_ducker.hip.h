@@ -1,5 +1,5 @@
 // k_ducker.hip.h — SPEC sidechain ducker (K_DUCKER): a kernel of its own next to k_level, as k_limiter is, so that its LDS
-// (the staged gate bits) and its registers are paid by no other node kind.  Included by fwgpu_kernels.hip, behind k_limiter.hip.h.
+// (the staged gate bits) and its registers are paid by no other node kind.  Included by fwgpu_kernels.hip.
 //
 // Inputs 0..n-1 are the main bus x_c, inputs n..n+k-1 the key k_j (never heard).  Per frame n since activation (everything false / zero
 // for n < 0, a key channel flagged silent counts as +0.0 and is not read):
@@ -35,20 +35,16 @@ struct DuckP {
     const int* in_buf;
     const int* out_buf;
 };
-// false: state a plan build would not let through (a slice of another size would be indexed out of bounds)
+// false: state a plan build would not let through — the host harness holds it to that (a slice of another size would be indexed out
+// of bounds)
 __device__ __forceinline__ bool duck_params(const DevView& v, const NodeDesc& nd, const NodeState& s, DuckP& p) {
-    const uint64_t A = s.playhead, R = s.loop_start, W = s.loop_end;
-    const int H = s.full_range;
-    if (A < 1 || A > DUCK_WIN_MAX || R < 1 || R > DUCK_WIN_MAX || H < 0 || H > (int)DUCK_HOLD_MAX || W != (A > R ? A : R) + (uint64_t)H ||
-        s.ext_len != 2u * (uint32_t)((W + 63) / 64) || nd.n_out < 1 || nd.n_out > DUCK_CH_MAX || nd.n_in - nd.n_out < 1 ||
-        nd.n_in - nd.n_out > DUCK_CH_MAX || v.frames < 1)
-        return false;
+    if (!duck_state_ok(s, nd.n_in, nd.n_out) || s.ext_len != duck_ext_len(s) || v.frames < 1) return false;
     p.T = s.p0;
     p.dd = 1.0f - s.p1;
-    p.A = (int)A;
-    p.R = (int)R;
-    p.H = H;
-    p.W = (int)W;
+    p.A = (int)s.playhead;
+    p.R = (int)s.loop_start;
+    p.H = s.full_range;
+    p.W = (int)s.loop_end;
     p.Af = (float)p.A;
     p.Rf = (float)p.R;
     p.n = nd.n_out;
@@ -291,36 +287,4 @@ __global__ __launch_bounds__(WAVE) void k_ducker_hist(DevView v, const int* __re
     DuckP p;
     if (!duck_params(v, nd, v.states[nd.state], p)) return;
     ducker_history(v, p, K);
-}
-
-// B1: one node on scratch buffers (single wave).  A limiter, a ducker or a latency-compensation delay renders one block through its
-// stored history, which the call leaves advanced; one node never needs both kinds' LDS, and the delay needs none
-__global__ __launch_bounds__(WAVE) void k_single_node(DevView v, int node_idx) {
-    __shared__ union {
-        LimLds lim;
-        DuckLds duck;
-    } lds;
-    const int kind = v.nodes[node_idx].kind;
-    if (kind == K_LIMITER) {
-        limiter_node(v, v.nodes[node_idx], 0, 1, lds.lim);
-        return;
-    }
-    if (kind == K_DUCKER) {
-        const NodeDesc nd = v.nodes[node_idx];
-        DuckP p;
-        if (!duck_params(v, nd, v.states[nd.state], p)) return;
-        const uint32_t pieces = v.frames > DUCK_RUN_MAX ? (uint32_t)((v.frames + DUCK_RUN_MAX - 1) / DUCK_RUN_MAX) : 1u;
-        for (uint32_t run = 0; run < pieces; ++run) ducker_run(v, nd, p, run, 1, lds.duck);
-        ducker_history(v, p, 1);
-        return;
-    }
-    if (kind == K_DELAY_COMP) {
-        const NodeDesc nd = v.nodes[node_idx];
-        DcompP p;
-        if (!dcomp_params(v, nd, v.states[nd.state], p)) return;
-        dcomp_block(v, p, 0);
-        dcomp_history(v, p, 1);
-        return;
-    }
-    node_process_wave<3>(v, node_idx, 0, 0);
 }

@@ -161,24 +161,14 @@ __device__ __forceinline__ bool kind_is_stateful(int kind) {
     return kind == K_VOLUME || kind == K_SAMPLER || kind == K_BEEP || kind == K_PAN || kind == K_HARD_CLIP ||
            kind == K_WIDTH || kind == K_BIQUAD || kind == K_DELAY || kind == K_RESAMPLER || kind == K_SPATIAL;
 }
-// The node kernel exists in three instantiations, by register appetite: one kernel for every kind needed 248 VGPRs
-// (2 waves per SIMD — nothing to hide HBM latency behind, 0.9 TB/s on a level of volume nodes).  Set 0: the streaming
-// kinds (volume, pan, sum, hard clip, mono<->stereo, width: 127 VGPRs), set 1: serial recurrences / filter banks / libm
-// (beep, biquad, delay, resampler, spatialiser: 147), set 2: the sampler (every sample format, wraps, tails, ramps).
-__device__ __forceinline__ int kind_set(int kind) {
-    if (kind == K_SAMPLER) return 2;
-    if (kind == K_LIMITER) return 4;  // (no instantiation of k_level: k_limiter.hip.h, a kernel of its own)
-    if (kind == K_DUCKER) return 5;   // (nor here: k_ducker.hip.h)
-    if (kind == K_DELAY_COMP) return 6;  // (nor here: k_delay_comp.hip.h)
-    return (kind == K_BEEP || kind == K_BIQUAD || kind == K_DELAY || kind == K_RESAMPLER || kind == K_SPATIAL) ? 1 : 0;
-}
+// (which of k_level's three instantiations runs a kind, or that a kernel of its own does: fwgpu_types.h kind_set)
 // SET: 0 / 1 / 2 = that set only, 3 = all kinds (single-node entry).
 // adv_blocks: a frozen, playing sampler (k_level) — put its playhead where `adv_blocks` steady blocks leave it first
 template <int SET>
 __device__ void node_process_wave(const DevView& v, int node_idx, uint32_t blk, uint32_t cmd_block, bool store_state = true,
                                   uint32_t adv_blocks = 0, bool frozen_sampler = false) {
     const NodeDesc nd = v.nodes[node_idx];
-    if (nd.is_graph_io || nd.kind == K_FIR || nd.kind == K_LIMITER || nd.kind == K_DUCKER || nd.kind == K_DELAY_COMP) return;  // I/O edges (k_graph_in/out); FIR banks run as MFMA GEMMs; k_limiter; k_ducker; k_delay_comp
+    if (nd.is_graph_io || nd.kind == K_FIR || kind_has_own_kernel(nd.kind)) return;  // I/O edges (k_graph_in/out); FIR banks run as MFMA GEMMs; k_limiter, k_ducker, k_delay_comp
     // the other instantiation's kinds return here; their switch cases are compiled out below (`if constexpr`: a case
     // that is compiled out falls through, which nothing can reach)
     if constexpr (SET != 3) {
@@ -1345,7 +1335,7 @@ __global__ __launch_bounds__(WAVE* WPB) void k_bus_iir(DevView v, const int* __r
     }
 }
 
-// (B1, one node on scratch buffers — k_single_node — is in k_ducker.hip.h, behind the two kinds that bring LDS of their own)
+// (B1, one node on scratch buffers — k_single_node — is in k_single.hip.h, behind every node kind it can run)
 
 // ------------------------------------------------------------------ state init / graph I/O edges
 struct StateInit {

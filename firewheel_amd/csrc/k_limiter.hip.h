@@ -155,10 +155,8 @@ __device__ void limiter_history(const DevView& v, const NodeDesc& nd, const Node
 __device__ void limiter_node(const DevView& v, const NodeDesc& nd, uint32_t b, uint32_t K, LimLds& L) {
     const NodeState& s = v.states[nd.state];
     const uint64_t H = s.loop_start;
-    // (nothing a plan build lets through; a slice of another size would be indexed out of bounds)
-    if (H > LIM_HOLD_MAX || s.loop_end != H + LIM_HIST_PAD || s.ext_len != (uint32_t)nd.n_in * (uint32_t)s.loop_end || nd.n_in != nd.n_out ||
-        nd.n_in < 1 || nd.n_in > LIM_CH_MAX || v.frames < 1)
-        return;
+    // (nothing a plan build lets through — the host harness holds it to that; a slice of another size would be indexed out of bounds)
+    if (!lim_state_ok(s, nd.n_in, nd.n_out) || s.ext_len != lim_ext_len(s, nd.n_in) || v.frames < 1) return;
     if (K > 1 && (uint64_t)v.frames >= H + LIM_BACK) {
         limiter_block(v, nd, s, b, b > 0, L);
         if (b == 0) limiter_history(v, nd, s, K - 1, true);

@@ -705,6 +705,10 @@ class HostOnlyEngine(GpuEngine):
         """first descriptor invariant / table extent the launch stubs found violated since the last reset ('' = none)"""
         return hostonly_lib().fwh_violation().decode()
 
+    def level_kinds_seen(self):
+        """OR of the launch bits (fwgpu_types.h kind_launch_bits) of every level launch since the last reset_launches()"""
+        return int(hostonly_lib().fwh_level_kinds_seen())
+
 
 def make_engine(backend, **kw):
     if backend == "oracle":

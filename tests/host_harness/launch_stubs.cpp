@@ -8,7 +8,9 @@ namespace {
 unsigned long long g_launches[8];  // 0 level, 1 voice_control, 2 leaf_sum, 3 chain, 4 bus_sum, 5 root_out, 6 fir, 7 other
 unsigned long long g_cmds_applied = 0;
 unsigned long long g_ctl_orders = 0;  // control launches that carried a dispatch order (FusedView::ctl_order)
+int g_level_kinds_seen = 0;  // OR of every launch_level's launch bits since the last fwh_launch_reset
 }
+extern "C" int fwh_level_kinds_seen(void) { return g_level_kinds_seen; }
 extern "C" unsigned long long fwh_cmds_seen(void) { return g_cmds_applied; }
 extern "C" {
 unsigned long long fwh_h2d_copies = 0, fwh_h2d_max_bytes = 0, fwh_h2d_bytes = 0;  // (fakehip's hipMemcpyAsync counts)
@@ -40,6 +42,7 @@ void fwh_fail_alloc(long long nth) { fwh_fail_alloc_in = nth; }
 extern "C" unsigned long long fwh_launch_count(int which) { return which >= 0 && which < 8 ? g_launches[which] : 0; }
 extern "C" void fwh_launch_reset(void) {
     for (auto& x : g_launches) x = 0;
+    g_level_kinds_seen = 0;
 }
 
 // ---- what the stubs CHECK instead of computing: every table a kernel would index is touched at the extent the kernel
@@ -124,6 +127,30 @@ void check_generic_node(const DevView& v, int idx, int K) {
         if (v.chain_done) touch(v.chain_done + (size_t)(nd.aux0 - 1) * v.chain_words, 4 * (size_t)v.chain_words);
     }
     if (v.chain_done) REQUIRE(v.chain_words > 0 && K <= 32 * v.chain_words && v.frozen != nullptr, K, v.chain_words);
+}
+// a bus node with a kernel of its own (k_limiter / k_ducker / k_delay_comp, k_single_node): the state its kernel renders — anything
+// else and the device guard returns, a node that silently renders nothing — and an ext slice of exactly the length the kernel indexes
+void check_bus_node(const DevView& v, int idx) {
+    const NodeDesc nd = v.nodes[idx];
+    if (!kind_has_own_kernel(nd.kind)) return;
+    REQUIRE(nd.state >= 0, idx, nd.state);
+    if (nd.state < 0) return;
+    const NodeState& s = v.states[nd.state];
+    uint32_t len = 0;
+    if (nd.kind == K_LIMITER) {
+        REQUIRE(lim_state_ok(s, nd.n_in, nd.n_out), idx, nd.state);
+        len = lim_ext_len(s, nd.n_in);
+    } else if (nd.kind == K_DUCKER) {
+        REQUIRE(duck_state_ok(s, nd.n_in, nd.n_out), idx, nd.state);
+        len = duck_ext_len(s);
+    } else {
+        REQUIRE(nd.kind == K_DELAY_COMP && dcomp_state_ok(s, nd.n_in, nd.n_out), idx, nd.state);
+        len = dcomp_ext_len(s, nd.n_in);
+    }
+    REQUIRE(s.ext_len == len && s.ext_len > 0, (long)s.ext_len, (long)len);
+    const size_t ext_floats = alloc_bytes(v.ext) / sizeof(float);
+    REQUIRE((size_t)s.ext_off + s.ext_len <= ext_floats, (long)s.ext_off, (long)s.ext_len);
+    if ((size_t)s.ext_off + s.ext_len <= ext_floats) touch(v.ext + s.ext_off, sizeof(float) * (size_t)s.ext_len);
 }
 void check_view_common(const DevView& v, int K) {
     REQUIRE(K >= 1, K);
@@ -213,15 +240,20 @@ static const void* g_fused_ctx_states = nullptr;  // whose states they index
 int launch_level(hipStream_t, const DevView& v, const int* d_level_nodes, int n_nodes, int K, uint32_t, int kinds) {
     g_launches[0]++;
     check_view_common(v, K);
-    REQUIRE(kinds >= 0 && kinds <= 15, kinds);  // 0: a level of Dummy / graph I/O / FIR nodes only — nothing to launch; bit 3: holds a biquad / delay
+    g_level_kinds_seen |= kinds;
     touch(d_level_nodes, sizeof(int) * (size_t)n_nodes);
+    int want = 0;  // the launch bits are the OR over the level's nodes: a missing bit is a node nobody renders, a spare one a wasted launch
     for (int i = 0; i < n_nodes; ++i) {
         check_generic_node(v, d_level_nodes[i], K);
+        check_bus_node(v, d_level_nodes[i]);
         const NodeDesc& nd = v.nodes[d_level_nodes[i]];
+        REQUIRE((kinds & kind_launch_bits(nd.kind)) == kind_launch_bits(nd.kind), kinds, nd.kind);
+        want |= kind_launch_bits(nd.kind);
         if (v.pool_blk_stride && (nd.kind == K_SAMPLER || nd.kind == K_RESAMPLER || nd.kind == K_VOLUME || nd.kind == K_PAN || nd.kind == K_WIDTH ||
                                   nd.kind == K_HARD_CLIP) && v.cmds != nullptr)
             REQUIRE(v.states != g_fused_ctx_states || !(nd.state >= 0 && nd.state < (1 << 16) && g_fused_states[nd.state]), d_level_nodes[i], nd.state);
     }
+    REQUIRE(kinds == want, kinds, want);
     return 0;
 }
 int launch_frozen_scan(hipStream_t, const DevView& v, int n_nodes, uint32_t, int K, uint8_t* d_frozen, unsigned long long* d_snap) {
@@ -304,6 +336,7 @@ int launch_single_node(hipStream_t, const DevView& v, int node_idx) {
     g_launches[7]++;
     check_view_common(v, 1);
     check_generic_node(v, node_idx, 1);
+    check_bus_node(v, node_idx);
     return 0;
 }
 int launch_scatter_states(hipStream_t, NodeState* states, const void* d_inits, int n) {
@@ -1041,4 +1074,59 @@ extern "C" size_t fwh_image_digest_fields(const fwgpu_ctx* c, char* buf, size_t 
     d.image(c);
     if (cap) snprintf(buf, cap, "%s", s.c_str());
     return s.size();
+}
+
+// The bus-node checks of launch_level / launch_single_node, on views built here: one level of one node, its state filled by make_state as
+// fwgpu_add_node would and its slice sized as activate_nodes would.  Each of the three kinds must pass as built, and each mistake must
+// be reported.  Returns the number of wrong outcomes; the violation string is left as it was found (the launch counts are not).
+extern "C" int fwh_selftest_bus_checks(void) {
+    using namespace fwgpu;
+    static float pool[3 * 64], ext[2048];
+    static uint8_t flags[3];
+    const std::string saved = g_violation;
+    fwh_alloced(ext, sizeof(ext));
+    const int in_buf[2] = {1, 1}, out_buf[1] = {2}, level[1] = {0};
+    int wrong = 0;
+    // edit: the mistake, made to the finished node and its launch bits
+    auto run = [&](int kind, bool want_violation, auto edit) {
+        NodeDesc nd{};
+        nd.kind = kind;
+        nd.n_in = kind == K_DUCKER ? 2 : 1;  // (a ducker: one main and one key channel)
+        nd.n_out = 1;
+        const float lim[2] = {0.5f, 4.0f}, duck[5] = {0.5f, 0.5f, 3.0f, 5.0f, 2.0f}, dcomp[1] = {3.0f};  // H = 4; A, R, H = 3, 5, 2; D = 3
+        NodeState st = kind == K_LIMITER ? make_state(kind, lim, 2, 48000) : kind == K_DUCKER ? make_state(kind, duck, 5, 48000) : make_state(kind, dcomp, 1, 48000);
+        st.ext_off = 8;
+        st.ext_len = kind == K_LIMITER ? lim_ext_len(st, nd.n_in) : kind == K_DUCKER ? duck_ext_len(st) : dcomp_ext_len(st, nd.n_in);
+        int kinds = kind_launch_bits(kind);
+        edit(st, kinds);
+        DevView v{};
+        v.nodes = &nd;
+        v.in_buf = in_buf;
+        v.out_buf = out_buf;
+        v.states = &st;
+        v.ext = ext;
+        v.pool = pool;
+        v.flags = flags;
+        v.stride = v.frames = 64;
+        fwh_violation_reset();
+        launch_level(nullptr, v, level, 1, 1, 0, kinds);
+        if (g_violation.empty() == want_violation) wrong++;
+        // (the single-node entry takes no launch bits: a mistake in them alone is none to it)
+        fwh_violation_reset();
+        launch_single_node(nullptr, v, 0);
+        if (g_violation.empty() == (want_violation && kinds == kind_launch_bits(kind))) wrong++;
+    };
+    for (int kind : {K_LIMITER, K_DUCKER, K_DELAY_COMP}) {
+        run(kind, false, [](NodeState&, int&) {});
+        run(kind, true, [](NodeState& s, int&) { s.ext_len -= 1; });                      // ext_len one short
+        run(kind, true, [](NodeState& s, int&) { s.ext_off = 2048 - s.ext_len + 1; });    // a slice that ends past the pool
+        run(kind, true, [](NodeState&, int& kinds) { kinds = LB_SET0; });                 // kinds without the node's bit
+        run(kind, true, [](NodeState&, int& kinds) { kinds |= LB_SET1; });                // kinds with a bit no node accounts for
+    }
+    run(K_LIMITER, true, [](NodeState& s, int&) { s.loop_end += 1; s.ext_len = lim_ext_len(s, 1); });   // HK != H + LIM_HIST_PAD
+    run(K_DUCKER, true, [](NodeState& s, int&) { s.loop_end += 1; s.ext_len = duck_ext_len(s); });      // W != max(A, R) + H
+    run(K_DELAY_COMP, true, [](NodeState& s, int&) { s.loop_end += 1; });                               // loop_end != D + 1
+    fwh_freed(ext);
+    g_violation = saved;
+    return wrong;
 }

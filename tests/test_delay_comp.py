@@ -6,9 +6,7 @@ without the node: the stream input itself, or the OracleEngine's output of the s
 know the kind).  Every comparison on the GPU tier is `fwapi.bits` equality.
 
 CPU tier: the model against a per-frame brute force; shapes and the creation parameter on the host-only harness; the latency queries
-and compensate_latency; the planner on the harness; the typed Python mirror, the header and the generated ffi.rs.  The harness'
-launch_level stub knows the launch bits 0..3 and reports the node's bit 6 as a violated invariant ("kinds <= 15"); it still counts the
-launch, so the planner test reads its counters, accepts that one report and nothing else, and clears it.
+and compensate_latency; the planner on the harness; the typed Python mirror, the header and the generated ffi.rs.
 
 GPU tier: G1 stream graphs on the level executor, G2 silence flags, G3 a limited bus and its compensated dry copy, G4 a delayed
 sub-mix beside fused voice banks, G5 graph edits, G6 fwgpu_node_process, G7 a level shared with a limiter, a biquad and a volume (and,
@@ -22,11 +20,9 @@ import pytest
 
 import fwapi
 import scenarios
+from busnodes import CHAIN, DELAY_COMP, DRY, DUCKER, LB_DELAY_COMP, LB_LEVEL, LIMITER, _host, _start, _voice, assert_bits, bank, harness_run, planar
 from fwapi import LOOP_FULL, GpuEngine, HostOnlyEngine, OracleEngine
 
-DELAY_COMP = 19
-DUCKER = 18
-LIMITER = 17
 INVALID = -20
 COMPILE_CYCLE = -10
 DMAX = 8192
@@ -88,18 +84,6 @@ def special_noise(rng, n, N):
     return u.view(F32).reshape(n, N)
 
 
-def assert_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.argwhere(fwapi.bits(got) != fwapi.bits(want))
-    assert bad.size == 0, "%s: %d of %d samples differ, first at %s: %r vs %r" % (
-        what, len(bad), got.size, tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
-
-
-def planar(interleaved, ch=2):
-    return np.asarray(interleaved, dtype=F32).reshape(-1, ch).T
-
-
 # ================================================================================================ CPU tier: the model
 RAGGED = [64, 64, 17, 1, 64, 64, 64, 5, 64, 64, 64, 64, 30, 64, 64, 64]
 
@@ -159,13 +143,6 @@ def test_model_never_flags_a_block_that_holds_a_nonzero_sample(D):
 
 
 # ================================================================================================ CPU tier: shapes and the parameter
-def _host(mbf=64, **kw):
-    e = HostOnlyEngine(max_block_frames=mbf, **kw)
-    v = e.volume(50.0)
-    e.connect_stereo(v, e.graph_out_node)
-    return e, v
-
-
 @pytest.mark.parametrize("n_in,n_out", [(0, 0), (9, 9), (2, 1), (1, 2)])
 def test_shapes_refused_at_add_node(n_in, n_out):
     e, _ = _host()
@@ -388,110 +365,24 @@ def test_report_h_a_cycle_returns_the_compile_error():
 
 
 # ================================================================================================ the desk: a delayed sub-mix beside voice banks
-DRY = ["v", "vp", "", "pv", "vc", "v", "vp", "p", "v"]
-CHAIN = ["vB", "BD", "v", "vBD", "vp", "DBv", "BB", "cB", "v"]
-# the banks of plans 1 / 2 / 3 (tests/test_limiter.py PLANS) and one whose master chain no fused plan takes.  detect_fused is unchanged
+# the banks of plans 1 / 2 / 3 (busnodes.PLANS) and one whose master chain no fused plan takes.  detect_fused is unchanged
 # and covers whole graphs only, so with a sub-mix beside the bank — through a delay-comp or through the twin's volume — every one of
 # them is the hybrid plan (3): what stays is the banks' fused kernels, voice-bank (DRY) and chain (CHAIN)
 DESKS = {1: dict(shapes=DRY), 2: dict(shapes=CHAIN), 3: dict(shapes=DRY, send=True), "hybrid": dict(shapes=DRY, spatial=True)}
 SUBMIX_D = 63
 
 
-class Desk(object):
-    pass
-
-
-def _stage(e, tok, rng, i):
-    if tok == "v":
-        return e.volume(float(rng.uniform(30, 100)))
-    if tok == "p":
-        return e.pan(float(rng.uniform(-1, 1)))
-    if tok == "c":
-        return e.hard_clip(-3.0)
-    if tok == "B":
-        return e.biquad(int(rng.integers(0, 3)), float(rng.uniform(200, 8000)), float(rng.choice([0.707, 1.8])))
-    if tok == "D":
-        return e.delay((64, 129, 300, 384)[i % 4] / float(e.sample_rate), feedback=float(rng.choice([0.0, 0.45])), mix=0.5)
-    raise ValueError(tok)
-
-
-def _voice(e, d, shape, i, rng):
-    s = e.sampler(100.0)
-    d.samplers.append(s)
-    cur = s
-    for t in shape:
-        n = _stage(e, t, rng, i)
-        e.connect_stereo(cur, n)
-        cur = n
-    return cur
-
-
-def _start(e, s, seed, i, src_blocks=6):
-    e.sampler_set_sample(s, e.new_sample(fwapi.PLANAR_F32, 2, scenarios.voice_source(seed * 1000 + 71 + i, src_blocks * e.max_block_frames, 2)))
-    e.sampler_set_loop_range(s, LOOP_FULL)
-    e.sampler_play(s)
-
-
-def desk(e, shapes, middle, send=False, spatial=False, seed=0):
-    """the bank of tests/test_limiter.py — voices -> leaf sums of four -> root sum -> master volume -> graph_out 0,1 — and beside it a
-    sub-mix S of two more voices -> `middle` -> graph_out 2,3.  middle: "dcomp" (DelayCompNode(63)), "volume" (the twin: a 2 -> 2 volume
-    of 100 % in its place) or None (the oracle's graph: S itself).  spatial: a spatialiser behind the root, which no fused plan takes"""
-    d = Desk()
-    d.e, d.samplers, d.seed, d.node = e, [], seed, None
-    rng = np.random.default_rng(5200 + seed)
-    ends = [_voice(e, d, sh, i, rng) for i, sh in enumerate(shapes)]
-    leaves = []
-    for i in range(0, len(ends), 4):
-        grp = ends[i:i + 4]
-        m = e.sum(max(2, len(grp)) + (1 if i + 4 >= len(ends) else 0))
-        for p, n in enumerate(grp):
-            e.connect_stereo(n, m, 2 * p)
-        leaves.append(m)
-        d.spare = (m, 2 * len(grp))
-    root = e.sum(max(2, len(leaves) + (1 if send else 0)))
-    for p, m in enumerate(leaves):
-        e.connect_stereo(m, root, 2 * p)
-    if send:
-        dl = e.delay(300 / float(e.sample_rate), feedback=0.3, mix=1.0)
-        e.connect_stereo(leaves[0], dl)
-        e.connect_stereo(dl, root, 2 * len(leaves))
-    cur = root
-    if spatial:
-        sp = e.spatial(1.0, 0.5, -2.0, n_in=2)
-        e.connect_stereo(cur, sp)
-        cur = sp
-    master = e.volume(90.0)
-    e.connect_stereo(cur, master)
-    e.connect_stereo(master, e.graph_out_node)
-    d.S = e.sum(2)
-    for p in range(2):
-        e.connect_stereo(_voice(e, d, "v", len(shapes) + p, rng), d.S, 2 * p)
-    if middle == "dcomp":
-        d.node = e.add_node(DELAY_COMP, 2, 2, [float(SUBMIX_D)])
-    elif middle == "volume":
-        d.node = e.volume(100.0)
-    if d.node is not None:
-        e.connect_stereo(d.S, d.node)
-        e.connect_stereo(d.node, e.graph_out_node, 2)
-    else:
-        e.connect_stereo(d.S, e.graph_out_node, 2)
-    e.update()
-    for i, s in enumerate(d.samplers):
-        _start(e, s, seed, i)
-    return d
+def desk(e, shapes, middle, **kw):
+    """busnodes.bank with a master volume and a sub-mix S beside it.  middle: "dcomp" (DelayCompNode(63), the bank's `middle` node),
+    "volume" (the twin) or None (the oracle's graph: S itself)"""
+    return bank(e, shapes, [("v", 90.0)], submix=True, middle=("dcomp", SUBMIX_D) if middle == "dcomp" else middle, rng_base=5200, salt=71, **kw)
 
 
 # ================================================================================================ CPU tier: the planner
 def _harness_desk(which, middle, max_batch):
-    L = fwapi.hostonly_lib()
     e = HostOnlyEngine(max_block_frames=256, num_graph_outputs=4, max_batch=max_batch)
     desk(e, middle=middle, **DESKS[which])
-    e.reset_launches()
-    for k in (3, 5, 2, 4, 6, 3, 5, 4, 4):
-        e.process_blocks(k, n_out_ch=4)
-    report = e.violation()
-    L.fwh_violation_reset()
-    return e, e.launches(), report
+    return (e,) + harness_run(e, n_out_ch=4)
 
 
 @pytest.mark.parametrize("which", [1, 2, 3, "hybrid"])
@@ -499,11 +390,9 @@ def _harness_desk(which, middle, max_batch):
 def test_a_delay_comp_on_a_sub_mix_changes_no_planner_decision(which, max_batch):
     """the twin graph, a 2 -> 2 volume in the node's place: the same plan kind, fused voices, launches and lazy calls; the level that
     holds the node is launched with bit 6"""
-    e0, la0, rep0 = _harness_desk(which, "volume", max_batch)
-    assert rep0 == ""
-    e, la, rep = _harness_desk(which, "dcomp", max_batch)
-    m = re.match(r"^kinds >= 0 && kinds <= 15 \((\d+), 0\)$", rep)   # (see the module's docstring)
-    assert m and int(m.group(1)) & 64 and not int(m.group(1)) & ~79, rep
+    e0, la0, seen0 = _harness_desk(which, "volume", max_batch)
+    e, la, seen = _harness_desk(which, "dcomp", max_batch)
+    assert seen & LB_DELAY_COMP and not seen & ~(LB_DELAY_COMP | LB_LEVEL) and not seen0 & ~LB_LEVEL, (seen, seen0)
     assert e.cx.plan_kind() == e0.cx.plan_kind() == 3 and e.cx.plan_fused_voices() == e0.cx.plan_fused_voices()
     assert e.cx.plan_fused_voices() == len(DESKS[which]["shapes"]) + 2    # the banks' voices and the sub-mix's stay with the fused kernels
     assert la == la0, (la, la0)
@@ -511,7 +400,6 @@ def test_a_delay_comp_on_a_sub_mix_changes_no_planner_decision(which, max_batch)
 
 
 def test_one_launch_level_with_bit_6_per_batch():
-    L = fwapi.hostonly_lib()
     e = HostOnlyEngine(max_block_frames=64, num_graph_inputs=2, max_batch=4)
     m = e.add_node(DELAY_COMP, 2, 2, [63.0])
     e.connect_stereo(e.graph_in_node, m)
@@ -520,9 +408,10 @@ def test_one_launch_level_with_bit_6_per_batch():
     assert e.cx.plan_kind() == 0
     e.reset_launches()
     e.process_blocks(4)
+    assert e.violation() == ""
     assert e.launches()["level"] == 1
-    assert e.violation() == "kinds >= 0 && kinds <= 15 (64, 0)"
-    L.fwh_violation_reset()
+    # the graph's other nodes are graph_in and graph_out: I/O edges with kernels of their own, in no level list, so they add no bit
+    assert e.level_kinds_seen() == LB_DELAY_COMP
 
 
 # ================================================================================================ CPU tier: mirror, header, ffi.rs
@@ -732,9 +621,9 @@ def test_g5_an_edit_elsewhere_keeps_the_history_and_a_new_node_starts_from_zeros
         outs = [np.asarray(e.process_interleaved(f, n_out_ch=4)) for f in phases[0]]
 
         def insert():
-            d.node = e.add_node(DELAY_COMP, 2, 2, [float(D)])
-            e.connect_stereo(d.S, d.node)
-            e.connect_stereo(d.node, e.graph_out_node, 2)
+            d.middle = e.add_node(DELAY_COMP, 2, 2, [float(D)])
+            e.connect_stereo(d.S, d.middle)
+            e.connect_stereo(d.middle, e.graph_out_node, 2)
             e.update()
 
         if gpu:  # the node goes in between S and graph_out
@@ -746,10 +635,10 @@ def test_g5_an_edit_elsewhere_keeps_the_history_and_a_new_node_starts_from_zeros
         end = _voice(e, d, "v", len(d.samplers), rng)
         e.connect_stereo(end, d.spare[0], d.spare[1])
         e.update()
-        _start(e, d.samplers[-1], d.seed, len(d.samplers) - 1)
+        _start(e, d.samplers[-1], d.seed, len(d.samplers) - 1, d.salt)
         outs += [np.asarray(e.process_interleaved(f, n_out_ch=4)) for f in phases[2]]
         if gpu:  # removed and added again in one update: a new node, a history of zeros
-            e.remove_node(d.node)
+            e.remove_node(d.middle)
             insert()
         outs += [np.asarray(e.process_interleaved(f, n_out_ch=4)) for f in phases[3]]
         return planar(np.concatenate(outs), 4)

@@ -7,9 +7,7 @@ itself, or the OracleEngine's output of the same graph built without the ducker,
 oracle does not know the kind).  Every comparison on the GPU tier is `fwapi.bits` equality.
 
 CPU tier: the model against a brute-force per-frame evaluation that reads like the SPEC, the SPEC's properties, shapes and creation
-parameters on the host-only harness, the planner on the harness, the typed Python mirror, the header and the generated ffi.rs.  The
-harness' launch_level stub knows the launch bits 0..3 and reports the ducker's bit 5 as a violated invariant ("kinds <= 15"); it still
-counts the launch, so the planner test accepts that one report and nothing else, and clears it.
+parameters on the host-only harness, the planner on the harness, the typed Python mirror, the header and the generated ffi.rs.
 
 GPU tier: G1 stream graphs on the level executor, G2 a two-sub-mix desk, G3 graph edits, G4 fwgpu_node_process, G5 a level with two
 duckers, a limiter, a biquad and a volume side by side.
@@ -26,10 +24,9 @@ import pytest
 
 import fwapi
 import scenarios
-from fwapi import LOOP_FULL, GpuEngine, HostOnlyEngine, OracleEngine
+from busnodes import DUCKER, LB_DUCKER, LB_LEVEL, LIMITER, _host, _start, _voice, assert_bits, harness_run, planar, ragged_calls
+from fwapi import GpuEngine, HostOnlyEngine, OracleEngine
 
-DUCKER = 18
-LIMITER = 17
 INVALID = -20
 F32 = np.float32
 CAP = 32768
@@ -87,15 +84,6 @@ def brute_u(on, A, R, H, n):
 
 
 # ------------------------------------------------------------------------------------------------ the probe signal and its calls
-def ragged_calls(mbf, at_least=6000):
-    """several K-block calls with K in {1, 2, 5}, a call of 3 blocks plus a 37-frame tail, a 1-frame call"""
-    pattern = [2 * mbf, 5 * mbf, mbf, 3 * mbf + 37, 1, 5 * mbf, 2 * mbf, mbf]
-    calls = []
-    while len(calls) < 5 or sum(calls) < at_least:
-        calls.append(pattern[len(calls) % len(pattern)])
-    return calls
-
-
 def probe(n, k, mbf, T, A, R, H, seed, total=None):
     """-> (calls, main [n][N], key [k][N], marks).  The key is noise below T with, above T: a burst inside the last frames of a call (the
     hold crosses into the next), one straddling a block boundary inside a call, one over the 37-frame tail block, the 1-frame call and
@@ -153,18 +141,6 @@ def probe(n, k, mbf, T, A, R, H, seed, total=None):
     key[:, N - calls[-1] - calls[-2]:N - calls[-1]] = F32(0.0)   # graph inputs of zeros arrive flagged silent
     x[:, N - calls[-1]:] = F32(0.0)
     return calls, x, key, marks
-
-
-def assert_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.argwhere(fwapi.bits(got) != fwapi.bits(want))
-    assert bad.size == 0, "%s: %d of %d samples differ, first at %s: %r vs %r" % (
-        what, len(bad), got.size, tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
-
-
-def planar(interleaved, ch=2):
-    return np.asarray(interleaved, dtype=F32).reshape(-1, ch).T
 
 
 # ================================================================================================ CPU tier: the model
@@ -240,13 +216,6 @@ def test_model_attack_is_the_short_window_and_release_the_long_one():
 GOOD = [0.05, 0.25, 480.0, 12000.0, 4800.0]
 
 
-def _host(mbf=64, **kw):
-    e = HostOnlyEngine(max_block_frames=mbf, **kw)
-    v = e.volume(50.0)
-    e.connect_stereo(v, e.graph_out_node)
-    return e, v
-
-
 @pytest.mark.parametrize("n_in,n_out", [(2, 2), (4, 0), (2, 3), (17, 8), (10, 1), (1, 9), (0, 0)])
 def test_shapes_refused_at_add_node(n_in, n_out):
     e, _ = _host()
@@ -304,18 +273,7 @@ class Desk(object):
     pass
 
 
-def _start(e, s, seed, i, src_blocks=6):
-    e.sampler_set_sample(s, e.new_sample(fwapi.PLANAR_F32, 2, scenarios.voice_source(seed * 1000 + 57 + i, src_blocks * e.max_block_frames, 2)))
-    e.sampler_set_loop_range(s, LOOP_FULL)
-    e.sampler_play(s)
-
-
-def _voice(e, d, percent):
-    s = e.sampler(100.0)
-    d.samplers.append(s)
-    v = e.volume(percent)
-    e.connect_stereo(s, v)
-    return v
+SALT = 57   # (busnodes._start)
 
 
 def desk(e, middle, n_music=5, n_dialogue=3, seed=0, duck=(0.05, 0.25, 48.0, 700.0, 100.0)):
@@ -326,11 +284,11 @@ def desk(e, middle, n_music=5, n_dialogue=3, seed=0, duck=(0.05, 0.25, 48.0, 700
     d.M = e.sum(n_music + 1)              # (a free port pair for a later voice)
     d.Dg = e.sum(max(2, n_dialogue))
     for p in range(n_music):
-        e.connect_stereo(_voice(e, d, 40.0 + 7.0 * p), d.M, 2 * p)
+        e.connect_stereo(_voice(e, d, [40.0 + 7.0 * p]), d.M, 2 * p)
     d.n_music = n_music
     d.dialogue = []
     for p in range(n_dialogue):
-        e.connect_stereo(_voice(e, d, 30.0 + 5.0 * p), d.Dg, 2 * p)
+        e.connect_stereo(_voice(e, d, [30.0 + 5.0 * p]), d.Dg, 2 * p)
         d.dialogue.append(d.samplers[-1])
     if middle == "duck":
         d.duck = e.add_node(DUCKER, 4, 2, list(duck))
@@ -346,7 +304,7 @@ def desk(e, middle, n_music=5, n_dialogue=3, seed=0, duck=(0.05, 0.25, 48.0, 700
     e.connect_stereo(d.Dg, e.graph_out_node, 2)
     e.update()
     for i, s in enumerate(d.samplers):
-        _start(e, s, seed, i)
+        _start(e, s, seed, i, SALT)
     return d
 
 
@@ -356,30 +314,33 @@ def oracle(mbf):
 
 # ================================================================================================ CPU tier: the planner
 def _harness_desk(middle, max_batch):
-    L = fwapi.hostonly_lib()
     e = HostOnlyEngine(max_block_frames=256, num_graph_outputs=4, max_batch=max_batch)
     desk(e, middle)
-    e.reset_launches()
-    calls = (3, 5, 2, 4, 6, 3, 5, 4, 4)
-    for k in calls:
-        e.process_blocks(k, n_out_ch=4)
-    report = e.violation()
-    L.fwh_violation_reset()
-    return e, e.launches(), report
+    return (e,) + harness_run(e, n_out_ch=4)
 
 
 @pytest.mark.parametrize("max_batch", [64, 3])
 def test_a_ducker_changes_no_planner_decision(max_batch):
-    """the twin graph, a 2 -> 2 volume in the ducker's place: the same plan kind, fused voices, launches and lazy calls"""
-    e0, la0, rep0 = _harness_desk("volume", max_batch)
-    assert rep0 == ""
-    e, la, rep = _harness_desk("duck", max_batch)
-    m = re.match(r"^kinds >= 0 && kinds <= 15 \((\d+), 0\)$", rep)   # (see the module's docstring)
-    assert m and int(m.group(1)) & 32 and not int(m.group(1)) & ~47, rep
+    """the twin graph, a 2 -> 2 volume in the ducker's place: the same plan kind, fused voices, launches and lazy calls; the level that
+    holds the node is launched with bit 5"""
+    e0, la0, seen0 = _harness_desk("volume", max_batch)
+    e, la, seen = _harness_desk("duck", max_batch)
+    assert seen & LB_DUCKER and not seen & ~(LB_DUCKER | LB_LEVEL) and not seen0 & ~LB_LEVEL, (seen, seen0)
     assert e.cx.plan_kind() == e0.cx.plan_kind() and e.cx.plan_fused_voices() == e0.cx.plan_fused_voices()
     assert e.cx.plan_fused_voices() == 8
     assert la == la0, (la, la0)
     assert e.cx.lazy_stats() == e0.cx.lazy_stats(), (e.cx.lazy_stats(), e0.cx.lazy_stats())
+
+
+def test_node_kinds_end_at_19():
+    """fwgpu_add_node: the last kind with a valid shape is accepted, the one behind it and -1 are refused"""
+    e, _ = _host()
+    assert e.add_node(19, 2, 2, [63.0]) >= 0
+    for kind in (20, -1):
+        with pytest.raises(e.fa.FwgpuError) as ei:
+            e.add_node(kind, 2, 2, [])
+        assert ei.value.code == INVALID
+    e.update()
 
 
 # ================================================================================================ CPU tier: mirror, header, ffi.rs
@@ -417,7 +378,7 @@ def test_typed_mirror_header_and_generated_ffi():
     hdr = open(os.path.join(ROOT, "include", "fwgpu.h")).read()
     assert re.search(r"FWGPU_DUCKER = 18\b", hdr)
     types = open(os.path.join(ROOT, "firewheel_amd", "csrc", "fwgpu_types.h")).read()
-    assert re.search(r"K_DUCKER = 18\b", types) and re.search(r"K_LAST = K_DUCKER\b", types)
+    assert re.search(r"K_DUCKER = 18\b", types)
     assert re.search(r"#define DUCK_WIN_MAX 32768u", types) and re.search(r"#define DUCK_HOLD_MAX 32768u", types)
     ffi = open(os.path.join(ROOT, "rust", "firewheel-gpu", "src", "ffi.rs")).read()
     assert "pub const FWGPU_DUCKER: c_int = 18;" in ffi
@@ -534,10 +495,10 @@ def test_g3_connected_into_a_sounding_graph_replaced_and_carried_across_an_edit(
             e.remove_node(d.duck)
             insert()
         outs += [np.asarray(e.process_interleaved(f, n_out_ch=4)) for f in phases[2]]
-        end = _voice(e, d, 55.0)   # one more music voice on M's free ports, while ducked
+        end = _voice(e, d, [55.0])   # one more music voice on M's free ports, while ducked
         e.connect_stereo(end, d.M, 2 * d.n_music)
         e.update()
-        _start(e, d.samplers[-1], d.seed, len(d.samplers) - 1)
+        _start(e, d.samplers[-1], d.seed, len(d.samplers) - 1, SALT)
         outs += [np.asarray(e.process_interleaved(f, n_out_ch=4)) for f in phases[3]]
         return planar(np.concatenate(outs), 4)
 

@@ -7,8 +7,6 @@ graph built without the node (the oracle does not know the kind).  Every compari
 
 CPU tier: the model against a brute-force per-frame evaluation, its overshoot bound and its identity below the ceiling; shapes and
 creation parameters on the host-only harness; the planner on the harness; the typed Python mirror, the header and the generated ffi.rs.
-The harness' launch_level stub knows the launch bits 0..3 and reports the limiter's bit 4 as a violated invariant ("kinds <= 15"); it
-still counts the launch, so the planner test reads its counters, accepts that one report and nothing else, and clears it.
 
 GPU tier: G1 stream graphs on the level executor, G2 a master limiter on the three fused plans, G3 its neighbours in a master chain,
 G4 graph edits, G5 fwgpu_node_process.  By construction (`frames >= H + 126` and K > 1 blocks in the batch) the parallel path renders the
@@ -23,10 +21,9 @@ import pytest
 
 import fwapi
 import scenarios
-from fwapi import LOOP_FULL, GpuEngine, HostOnlyEngine, OracleEngine
+from busnodes import LB_LEVEL, LB_LIMITER, LIMITER, PLANS, _host, _start, _voice, assert_bits, bank, harness_batches, harness_run, planar, ragged_calls
+from fwapi import GpuEngine, HostOnlyEngine, OracleEngine
 
-LIMITER = 17
-METER = 16
 INVALID = -20
 LOOK = 64
 LATENCY = 63
@@ -80,15 +77,6 @@ def brute_frame(x, t, C, H, n):
 
 
 # ------------------------------------------------------------------------------------------------ the probe signal and its calls
-def ragged_calls(mbf, at_least=6000):
-    """several K-block calls with K in {1, 2, 5}, a call of 3 blocks plus a 37-frame tail, a 1-frame call"""
-    pattern = [2 * mbf, 5 * mbf, mbf, 3 * mbf + 37, 1, 5 * mbf, 2 * mbf, mbf]
-    calls = []
-    while len(calls) < 5 or sum(calls) < at_least:
-        calls.append(pattern[len(calls) % len(pattern)])
-    return calls
-
-
 def probe(n, calls, mbf, C, seed):
     """noise at about 0.3 (below every ceiling used here) with bursts of 6x .. 30x: one inside the last 63 frames of a call, one
     straddling a block boundary inside a call, one over the short tail block, the 1-frame call and the start of the next call, a
@@ -119,18 +107,6 @@ def probe(n, calls, mbf, C, seed):
         burst(a, a + int(rng.integers(5, 80)))
     assert quiet + 500 < N - 100 and np.abs(x[:, quiet:quiet + 400]).max() <= F32(C)
     return x
-
-
-def assert_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.argwhere(fwapi.bits(got) != fwapi.bits(want))
-    assert bad.size == 0, "%s: %d of %d samples differ, first at %s: %r vs %r" % (
-        what, len(bad), got.size, tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
-
-
-def planar(interleaved, ch=2):
-    return np.asarray(interleaved, dtype=F32).reshape(-1, ch).T
 
 
 # ================================================================================================ CPU tier: the model
@@ -178,13 +154,6 @@ def test_model_below_the_ceiling_is_a_delay_of_63_frames_bit_for_bit(C, H):
 
 
 # ================================================================================================ CPU tier: shapes and parameters
-def _host(mbf=64, **kw):
-    e = HostOnlyEngine(max_block_frames=mbf, **kw)
-    v = e.volume(50.0)
-    e.connect_stereo(v, e.graph_out_node)
-    return e, v
-
-
 @pytest.mark.parametrize("n_in,n_out", [(2, 1), (1, 2), (2, 0), (0, 0), (9, 9)])
 def test_shapes_refused_at_add_node(n_in, n_out):
     e, _ = _host()
@@ -223,92 +192,7 @@ def test_parameters_and_shapes_accepted(params, n):
         e.set_param(m, 1, 64.0)
 
 
-# ================================================================================================ banks with a master chain
-DRY = ["v", "vp", "", "pv", "vc", "v", "vp", "p", "v"]
-CHAIN = ["vB", "BD", "v", "vBD", "vp", "DBv", "BB", "cB", "v"]
-PLANS = {1: dict(shapes=DRY), 2: dict(shapes=CHAIN), 3: dict(shapes=DRY, send=True)}
-
-
-class Bank(object):
-    pass
-
-
-def _stage(e, tok, rng, i):
-    if tok == "v":
-        return e.volume(float(rng.uniform(30, 100)))
-    if tok == "p":
-        return e.pan(float(rng.uniform(-1, 1)))
-    if tok == "c":
-        return e.hard_clip(-3.0)
-    if tok == "B":
-        return e.biquad(int(rng.integers(0, 3)), float(rng.uniform(200, 8000)), float(rng.choice([0.707, 1.8])))
-    if tok == "D":
-        return e.delay((64, 129, 300, 384)[i % 4] / float(e.sample_rate), feedback=float(rng.choice([0.0, 0.45])), mix=0.5)
-    raise ValueError(tok)
-
-
-def _voice(e, b, shape, i, rng):
-    s = e.sampler(100.0)
-    b.samplers.append(s)
-    cur = s
-    for t in shape:
-        n = _stage(e, t, rng, i)
-        e.connect_stereo(cur, n)
-        cur = n
-    return cur
-
-
-def _start(e, s, seed, i, src_blocks=6):
-    e.sampler_set_sample(s, e.new_sample(fwapi.PLANAR_F32, 2, scenarios.voice_source(seed * 1000 + 31 + i, src_blocks * e.max_block_frames, 2)))
-    e.sampler_set_loop_range(s, LOOP_FULL)
-    e.sampler_play(s)
-
-
-def bank(e, shapes, master, send=False, seed=0, leave_out=""):
-    """voices -> leaf sums of four (the last one with a free port pair) -> root sum -> master chain -> graph_out.  `master`: a list of
-    ("v", percent) | ("L", C, H) | ("M", ring_blocks) | ("C", threshold_db); kinds named in `leave_out` are not built (the oracle's graph)"""
-    b = Bank()
-    b.e, b.samplers, b.node, b.seed = e, [], {}, seed
-    rng = np.random.default_rng(4200 + seed)
-    ends = [_voice(e, b, sh, i, rng) for i, sh in enumerate(shapes)]
-    leaves = []
-    for i in range(0, len(ends), 4):
-        grp = ends[i:i + 4]
-        m = e.sum(max(2, len(grp)) + (1 if i + 4 >= len(ends) else 0))
-        for p, n in enumerate(grp):
-            e.connect_stereo(n, m, 2 * p)
-        leaves.append(m)
-        b.spare = (m, 2 * len(grp))
-    root = e.sum(max(2, len(leaves) + (1 if send else 0)))
-    for p, m in enumerate(leaves):
-        e.connect_stereo(m, root, 2 * p)
-    if send:  # leaf 0's bus is consumed twice, dry and through a send delay: not a fused shape as a whole (plan 3)
-        d = e.delay(300 / float(e.sample_rate), feedback=0.3, mix=1.0)
-        e.connect_stereo(leaves[0], d)
-        e.connect_stereo(d, root, 2 * len(leaves))
-    cur = root
-    for spec in master:
-        if spec[0] in leave_out:
-            continue
-        if spec[0] == "v":
-            n = e.volume(spec[1])
-        elif spec[0] == "L":
-            n = e.add_node(LIMITER, 2, 2, [spec[1], spec[2]])
-        elif spec[0] == "M":
-            n = e.add_node(METER, 2, 2, [spec[1]])
-        else:
-            n = e.hard_clip(spec[1])
-        b.node[spec[0]] = n
-        e.connect_stereo(cur, n)
-        cur = n
-    b.last = cur
-    e.connect_stereo(cur, e.graph_out_node)
-    e.update()
-    for i, s in enumerate(b.samplers):
-        _start(e, s, seed, i)
-    return b
-
-
+# ================================================================================================ banks with a master chain (busnodes.bank)
 def run_calls(e, calls):
     return [np.asarray(e.process_interleaved(n)) for n in calls]
 
@@ -319,30 +203,23 @@ def oracle(mbf, short_blocks=False):
 
 # ================================================================================================ CPU tier: the planner
 def _harness_bank(plan, master, max_batch):
-    L = fwapi.hostonly_lib()
     e = HostOnlyEngine(max_block_frames=256, max_batch=max_batch)
-    b = bank(e, master=master, **PLANS[plan])
-    e.reset_launches()
-    calls = (3, 5, 2, 4, 6, 3, 5, 4, 4)
-    for k in calls:
-        e.process_blocks(k)
-    report = e.violation()
-    L.fwh_violation_reset()
-    return e, e.launches(), sum((k + max_batch - 1) // max_batch for k in calls), report
+    bank(e, master=master, **PLANS[plan])
+    return (e,) + harness_run(e)
 
 
 @pytest.mark.parametrize("plan", [1, 2, 3])
 @pytest.mark.parametrize("max_batch", [64, 3])
 def test_a_master_limiter_leaves_the_plan_its_launches_and_its_lazy_calls_alone(plan, max_batch):
-    """the same graph without the node: the same plan kind and fused voices, the same launches plus one launch_level per batch, the
-    same lazy calls"""
-    e0, la0, batches, rep0 = _harness_bank(plan, [("v", 90.0)], max_batch)
-    assert e0.cx.plan_kind() == plan and rep0 == ""
+    """the same graph without the node: the same plan kind and fused voices, the same launches plus one launch_level per batch — with
+    the limiter's bit — and the same lazy calls"""
+    e0, la0, seen0 = _harness_bank(plan, [("v", 90.0)], max_batch)
+    assert e0.cx.plan_kind() == plan and not seen0 & ~LB_LEVEL
     for master in ([("v", 90.0), ("L", 1.0, 128.0)], [("L", 0.5, 0.0), ("v", 90.0)]):
-        e, la, _, rep = _harness_bank(plan, master, max_batch)
-        assert rep in ("", "kinds >= 0 && kinds <= 15 (16, 0)"), rep   # (see the module's docstring)
+        e, la, seen = _harness_bank(plan, master, max_batch)
+        assert seen & LB_LIMITER and not seen & ~(LB_LIMITER | LB_LEVEL), seen
         assert e.cx.plan_kind() == plan and e.cx.plan_fused_voices() == e0.cx.plan_fused_voices()
-        assert la == dict(la0, level=la0["level"] + batches), (la, la0, batches)
+        assert la == dict(la0, level=la0["level"] + harness_batches(max_batch)), (la, la0)
         assert e.cx.lazy_stats() == e0.cx.lazy_stats(), (e.cx.lazy_stats(), e0.cx.lazy_stats())
         if plan != 3:
             assert e.cx.lazy_stats()[0] > 0
@@ -552,7 +429,7 @@ def test_g4_a_limiter_added_to_a_running_graph_and_a_later_edit(H):
         end = _voice(e, b, "v", len(b.samplers), rng)
         e.connect_stereo(end, b.spare[0], b.spare[1])
         e.update()
-        _start(e, b.samplers[-1], b.seed, len(b.samplers) - 1)
+        _start(e, b.samplers[-1], b.seed, len(b.samplers) - 1, b.salt)
         outs += run_calls(e, after)
         return np.concatenate(outs)
 
