@@ -17,6 +17,7 @@ from .graph import (  # noqa: F401
     FirReverbNode,
     FirewheelGpuCtx,
     DelayCompNode,
+    CrossfadeNode,
     DuckerNode,
     HardClipNode,
     HostNode,
@@ -37,6 +38,6 @@ from .graph import (  # noqa: F401
 
 __all__ = [
     "FirewheelGpuCtx", "HostNode", "VolumeNode", "SumNode", "SamplerNode", "BeepTestNode", "HardClipNode", "MonoToStereoNode",
-    "StereoToMonoNode", "DummyAudioNode", "StereoPanNode", "StereoWidthNode", "BiquadNode", "DelayNode", "FirReverbNode", "ResamplerNode", "SpatialNode", "MeterNode", "LimiterNode", "DuckerNode", "DelayCompNode", "LoopRange", "SampleFormat", "AddEdgeError",
+    "StereoToMonoNode", "DummyAudioNode", "StereoPanNode", "StereoWidthNode", "BiquadNode", "DelayNode", "FirReverbNode", "ResamplerNode", "SpatialNode", "MeterNode", "LimiterNode", "DuckerNode", "CrossfadeNode", "DelayCompNode", "LoopRange", "SampleFormat", "AddEdgeError",
     "CompileGraphError", "FwgpuError", "load_library", "build_library", "LIB_PATH",
 ]

@@ -382,7 +382,7 @@ int64_t fwgpu_add_node(fwgpu_ctx* c, int kind, uint32_t n_in, uint32_t n_out, co
             return fail(c, FWGPU_ERR_INVALID, "Resampler node: source longer than 2^31 frames");
     }
     if (n_in > 64 || n_out > 64) return fail(c, FWGPU_ERR_INVALID, "a node has at most 64 ports per side (core/node.rs:62,69)");
-    if (kind_has_own_kernel(kind)) {  // (its shape is refused here; its creation parameters at the next update, as a meter's ring is)
+    if (kind_has_own_kernel(kind) || kind == K_CROSSFADE) {  // (its shape is refused here; its creation parameters at the next update, as a meter's ring is)
         std::string err;
         if (!check_activation(kind, n_in, n_out, err)) return fail(c, FWGPU_ERR_INVALID, err);
     }
@@ -799,6 +799,40 @@ int fwgpu_ext_pool_floats(fwgpu_ctx* c, uint64_t* in_use, uint64_t* capacity) {
     return 0;
 }
 
+// SPEC crossfader: one CMD_XF_TO — the target in f0, frames and shape in i0 / i1, the control values as float bits in
+// d0 = (x1, y1) and d1 = (x2, y2), packed as CMD_SET_COEFS packs (a1, a2)
+int fwgpu_crossfade_to(fwgpu_ctx* c, int64_t node, float position, uint32_t frames, int shape, float x1, float y1, float x2, float y2,
+                       uint32_t at_block) {
+    static_assert(FWGPU_CROSSFADE_FRAMES_MAX == XF_FRAMES_MAX && FWGPU_CROSSFADE_CH_MAX == XF_CH_MAX, "the header's crossfader caps");
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    HostNode* n = c->graph.get(node);
+    if (!n) return fail(c, FWGPU_ERR_INVALID, "unknown node id");
+    if (n->kind != K_CROSSFADE) return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: the node is not a CrossfadeNode");
+    if (!(position >= 0.0f && position <= 1.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: position must be in 0..1");
+    if (frames > FWGPU_CROSSFADE_FRAMES_MAX) return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: at most 2^24 frames");
+    if (shape != XF_SHAPE_LINEAR && shape != XF_SHAPE_BEZIER) return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: shape must be 0 (linear) or 1 (Bezier)");
+    if (!(x1 >= 0.0f && x1 <= 1.0f && x2 >= 0.0f && x2 <= 1.0f))
+        return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: x1 and x2 must be in 0..1");
+    if (!(y1 >= -1.0f && y1 <= 2.0f && y2 >= -1.0f && y2 <= 2.0f))
+        return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: y1 and y2 must be in -1..2");
+    Cmd m;
+    memset(&m, 0, sizeof(m));
+    m.block = at_block;
+    m.type = CMD_XF_TO;
+    m.f0 = position;
+    m.i0 = (int)frames;
+    m.i1 = shape;
+    const float lo[2] = {x1, x2}, hi[2] = {y1, y2};
+    double* const d[2] = {&m.d0, &m.d1};
+    for (int k = 0; k < 2; ++k) {
+        uint32_t l, h;
+        memcpy(&l, &lo[k], 4);
+        memcpy(&h, &hi[k], 4);
+        const uint64_t u = ((uint64_t)h << 32) | l;
+        memcpy(d[k], &u, 8);
+    }
+    return push_cmd(c, node, K_CROSSFADE, m, false);
+}
 int fwgpu_node_set_param(fwgpu_ctx* c, int64_t node, int param, float value, uint32_t at_block) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
     HostNode* n = c->graph.get(node);
@@ -906,6 +940,9 @@ int fwgpu_node_set_param(fwgpu_ctx* c, int64_t node, int param, float value, uin
             m.i1 = dr;
             return push_cmd(c, node, -1, m, false);
         }
+        case K_CROSSFADE:  // param 0 = position: a jump (fwgpu_crossfade_to with frames 0)
+            if (param != 0) return fail(c, FWGPU_ERR_INVALID, "unknown param");
+            return fwgpu_crossfade_to(c, node, value, 0, XF_SHAPE_LINEAR, 0.0f, 0.0f, 1.0f, 1.0f, at_block);
         case K_LIMITER:  // ceiling and hold are fixed at construction (a moving ceiling would need a smoother: out of scope)
             return fail(c, FWGPU_ERR_INVALID, "LimiterNode has no runtime params: ceiling and hold_frames are set at add_node");
         case K_DUCKER:  // threshold, depth and the three times are fixed at construction (moving ones: out of scope)

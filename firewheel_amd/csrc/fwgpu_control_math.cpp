@@ -237,6 +237,16 @@ NodeState make_state(int kind, const float* params, int n_params, uint32_t sampl
             s.loop_end = ok ? (uint64_t)d + 1 : 0;
             break;
         }
+        case K_CROSSFADE: {  // params: position (0..1, default 0: all A), law (0 linear, 1 equal power; default 1)
+            const float pos = p(0, 0.0f), law = p(1, (float)XF_LAW_EQUAL_POWER);
+            // anything else — NaN, out of range, another law — leaves loop_end 0, and the node fails activation at the next update
+            const bool ok = pos >= 0.0f && pos <= 1.0f && (law == (float)XF_LAW_LINEAR || law == (float)XF_LAW_EQUAL_POWER);
+            s.p0 = s.p1 = ok ? pos : 0.0f;  // at rest at `position`: dur (full_range) 0, t0 (loop_start) 0, node time (playhead) 0
+            s.playing = ok ? (int)law : XF_LAW_EQUAL_POWER;
+            s.has_loop = XF_SHAPE_LINEAR;
+            s.loop_end = ok ? 1 : 0;
+            break;
+        }
         default:
             break;
     }

@@ -324,6 +324,13 @@ bool check_activation(int kind, uint32_t n_in, uint32_t n_out, std::string& err)
                 return false;
             }
             return true;
+        case K_CROSSFADE:  // SPEC: bus A and bus B of n channels each in, n out, n in 1..8
+            if (n_out < 1 || n_out > XF_CH_MAX || n_in != 2 * n_out) {
+                err = "CrossfadeNode needs 1..8 outputs and twice as many inputs (bus A, then bus B). Got num_inputs: " + std::to_string(n_in) +
+                      ", num_outputs: " + std::to_string(n_out);
+                return false;
+            }
+            return true;
         case K_MONO_TO_STEREO:
             if (n_in < 1 || n_out < 2) {
                 err = "MonoToStereoNode needs 1 input and 2 outputs.";

@@ -622,6 +622,9 @@ static int activate_nodes(ImageBuild& b) {
             if (!dcomp_state_ok(n.init, (int)n.n_in, (int)n.n_out))
                 return fail(c, FWGPU_ERR_INVALID, "DelayCompNode: frames must be a whole number in 0..8192");
             len = dcomp_ext_len(n.init, (int)n.n_in);
+        } else if (n.kind == K_CROSSFADE) {  // no slice: the whole state is the NodeState (xf_state_ok, which the device guard shares)
+            if (!xf_state_ok(n.init, (int)n.n_in, (int)n.n_out))
+                return fail(c, FWGPU_ERR_INVALID, "CrossfadeNode: position must be in 0..1, law 0 (linear) or 1 (equal power)");
         } else if (n.kind == K_FIR) {
             int ir = n.init.sample;
             if (ir < 0 || ir >= (int)c->samples.size() || !c->samples[ir].alive)

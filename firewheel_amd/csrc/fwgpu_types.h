@@ -13,7 +13,8 @@ enum : int {
     K_LIMITER = 17,  // SPEC look-ahead limiter: linked channels, sliding minimum + 64-term moving average, 63 frames of latency
     K_DUCKER = 18,  // SPEC sidechain ducker: n main + k key inputs, n outputs; window counts of the key's gate bits, no latency
     K_DELAY_COMP = 19,  // SPEC latency compensation: n -> n, a pure delay of a whole number of frames, a copy with no arithmetic
-    K_LAST = K_DELAY_COMP,  // the last node kind
+    K_CROSSFADE = 20,  // SPEC crossfader: 2n -> n, two buses blended along an automated curve of the node's frame count; k_level<0> renders it
+    K_LAST = K_CROSSFADE,  // the last node kind
 };
 #if defined(__HIPCC__)
 #define FW_TYPES_HD __host__ __device__
@@ -38,6 +39,15 @@ FW_TYPES_HD inline bool kind_has_own_kernel(int kind) { return kind_set(kind) >=
 enum : int { LB_SET0 = 1, LB_SET1 = 2, LB_SET2 = 4, LB_WALKERS = 8, LB_LIMITER = 16, LB_DUCKER = 32, LB_DELAY_COMP = 64 };
 FW_TYPES_HD inline int kind_launch_bits(int kind) { return (1 << kind_set(kind)) | ((kind == K_BIQUAD || kind == K_DELAY) ? LB_WALKERS : 0); }
 static_assert(LB_LIMITER == 1 << 4 && LB_DUCKER == 1 << 5 && LB_DELAY_COMP == 1 << 6, "a launch bit is 1 << kind_set");
+// K_CROSSFADE: n output channels (bus A on inputs 0..n-1, bus B on n..2n-1), the longest segment in frames (2^24: k and dur convert to
+// f32 exactly), the bisection steps of the Bezier solver, and the two laws / shapes
+#define XF_CH_MAX 8
+#define XF_FRAMES_MAX 16777216u
+#define XF_ITERS 24
+#define XF_LAW_LINEAR 0
+#define XF_LAW_EQUAL_POWER 1
+#define XF_SHAPE_LINEAR 0
+#define XF_SHAPE_BEZIER 1
 // K_DELAY_COMP: the delay D is a whole number of frames in 0..DCOMP_MAX.  The node's ext slice keeps the last D input frames per channel
 // and, behind them, one counter per channel (the silence rule's loud_c) in a 32-bit slot each.
 #define DCOMP_MAX 8192u
@@ -133,9 +143,12 @@ struct NodeState {
     //   DELAY_COMP: loop_start = D, loop_end = D + 1; ext = hist[n_in][D]: the last D input frames per channel, oldest first (a block
     //        flagged silent enters as zeros), then loud[n_in]: 32-bit counters in the float slots — how many of the frames in front of
     //        the next block may still be heard
+    //   CROSSFADE: no ext slice.  playhead = node time T (frames rendered since activation), p0 = P0, p1 = P1, loop_start = t0,
+    //        full_range = dur (0: at rest at P1), has_loop = shape (XF_SHAPE_*), phasor, phasor_inc, gain, aux = x1, y1, x2, y2,
+    //        playing = law (XF_LAW_*), loop_end = 1 (0: a creation parameter was refused); the valid states are xf_state_ok
     uint32_t ext_off;
     uint32_t ext_len;
-    int pad[1];
+    float aux;  // CROSSFADE: y2; every other kind: 0
 };
 static_assert(sizeof(NodeState) == 128, "NodeState layout");
 // The bus nodes with a kernel of their own: the states their kernels render (anything else would index the ext slice out of bounds)
@@ -159,6 +172,16 @@ FW_TYPES_HD inline bool dcomp_state_ok(const NodeState& s, int n_in, int n_out) 
     return D <= DCOMP_MAX && s.loop_end == D + 1 && n_in == n_out && n_in >= 1 && n_in <= DCOMP_CH_MAX;
 }
 FW_TYPES_HD inline uint32_t dcomp_ext_len(const NodeState& s, int n_in) { return (uint32_t)n_in * (uint32_t)s.loop_start + (uint32_t)n_in; }
+
+// K_CROSSFADE (rendered by k_level<0>, no ext slice): the states its case renders.  T never runs behind t0: a message sets t0 = T
+FW_TYPES_HD inline bool xf_state_ok(const NodeState& s, int n_in, int n_out) {
+    const auto unit = [](float x) { return x >= 0.0f && x <= 1.0f; };  // (false for a NaN)
+    const auto ctl_y = [](float y) { return y >= -1.0f && y <= 2.0f; };
+    return s.loop_end == 1 && n_out >= 1 && n_out <= XF_CH_MAX && n_in == 2 * n_out && unit(s.p0) && unit(s.p1) && s.full_range >= 0 &&
+           (uint32_t)s.full_range <= XF_FRAMES_MAX && (s.has_loop == XF_SHAPE_LINEAR || s.has_loop == XF_SHAPE_BEZIER) &&
+           (s.playing == XF_LAW_LINEAR || s.playing == XF_LAW_EQUAL_POWER) && unit(s.phasor) && unit(s.gain) && ctl_y(s.phasor_inc) &&
+           ctl_y(s.aux) && s.playhead >= s.loop_start;
+}
 
 struct SampleDesc {  // core/sample_resource.rs:4-26; data is HBM-resident
     const void* data;
@@ -188,6 +211,7 @@ enum : int {
     CMD_RS_STEP = 20,  // resampler: d0 bits = u64 32.32 step
     CMD_RS_SEEK = 21,  // resampler: d0 bits = u64 source frame
     CMD_SP_ITD = 22,   // spatialiser: i0 / i1 = left / right ear delay in frames
+    CMD_XF_TO = 23,    // crossfader: f0 = target position, i0 = frames, i1 = shape; d0 bits = (x1, y1), d1 bits = (x2, y2) as float bits
 };
 struct Cmd {
     int state;

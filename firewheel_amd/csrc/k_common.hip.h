@@ -95,6 +95,72 @@ __device__ __forceinline__ uint64_t sat_round_u64(double x) {  // `(x).round() a
     return (uint64_t)r;
 }
 
+// ------------------------------------------------------------------ K_CROSSFADE (SPEC): position and gains
+// ONE statement of the curve for the message (CMD_XF_TO takes P0 from it: W = 1) and for the render case of node_process_wave (W = 4:
+// the four consecutive frames a lane renders).  Every operation is a separately rounded f32 operation (-ffp-contract=off), the
+// division and the square roots are IEEE.  B(t; a, d) = ((q*t + b)*t + c)*t, the cubic Bezier coordinate through 0, a, d, 1
+struct XfCubic {
+    float q, b, c;
+};
+__device__ __forceinline__ XfCubic xf_cubic(float a, float d) {
+    const float c = 3.0f * a;
+    const float b = (3.0f * (d - a)) - c;
+    return XfCubic{(1.0f - c) - b, b, c};
+}
+__device__ __forceinline__ float xf_bezier(const XfCubic& k, float t) { return (((k.q * t) + k.b) * t + k.c) * t; }
+// the segment as the position rule reads it
+struct XfSeg {
+    float P0, P1, x1, y1, x2, y2;
+    uint64_t t0;
+    uint32_t dur;
+    int shape;
+};
+__device__ __forceinline__ XfSeg xf_seg(const NodeState& s) {
+    return XfSeg{s.p0, s.p1, s.phasor, s.phasor_inc, s.gain, s.aux, s.loop_start, (uint32_t)s.full_range, s.has_loop};
+}
+// the positions of frames n .. n + W - 1 (node time) under the segment.  The solver — XF_ITERS bisection steps on x(t) = u, then
+// y(t) — runs on the W frames at once, its loop rolled: the same trip count for every frame, nothing indexed by a variable
+template <int W>
+__device__ __forceinline__ void xf_positions(const XfSeg& g, uint64_t n, float (&p)[W]) {
+    const uint32_t dur = g.dur;
+    const uint64_t k0 = n - g.t0;
+#pragma unroll
+    for (int e = 0; e < W; ++e) p[e] = g.P1;
+    if (dur == 0u || k0 >= (uint64_t)dur) return;
+    const float fdur = (float)dur;  // (exact: dur <= 2^24; so is every k < dur)
+    float u[W], y[W];
+#pragma unroll
+    for (int e = 0; e < W; ++e) y[e] = u[e] = (float)((uint32_t)k0 + (uint32_t)e) / fdur;
+    if (g.shape == XF_SHAPE_BEZIER) {
+        const XfCubic kx = xf_cubic(g.x1, g.x2), ky = xf_cubic(g.y1, g.y2);
+        float lo[W], hi[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) lo[e] = 0.0f, hi[e] = 1.0f;
+#pragma unroll 1
+        for (int i = 0; i < XF_ITERS; ++i) {
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                const float m = (lo[e] + hi[e]) * 0.5f;
+                const bool below = xf_bezier(kx, m) < u[e];
+                lo[e] = below ? m : lo[e];
+                hi[e] = below ? hi[e] : m;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < W; ++e) y[e] = u[e] == 0.0f ? 0.0f : xf_bezier(ky, (lo[e] + hi[e]) * 0.5f);
+    }
+    const float span = g.P1 - g.P0;
+#pragma unroll
+    for (int e = 0; e < W; ++e)
+        if (k0 + (uint64_t)e < (uint64_t)dur)  // (the segment may end among the W frames)
+            p[e] = fminf(fmaxf(g.P0 + (span * y[e]), 0.0f), 1.0f);  // an overshooting curve is allowed; the position is clamped
+}
+__device__ __forceinline__ void xf_gains(int law, float p, float& a, float& b) {
+    const float q = 1.0f - p;
+    a = law == XF_LAW_LINEAR ? q : sqrtf(q);
+    b = law == XF_LAW_LINEAR ? p : sqrtf(p);
+}
+
 // first command of (state, block) in the (state, block, seq)-sorted list
 __device__ inline int chain_cmd_lower_bound(const Cmd* cmds, int n_cmds, int state_idx, uint32_t block) {
     int lo = 0, hi = n_cmds;
@@ -112,6 +178,8 @@ __device__ inline int chain_cmd_lower_bound(const Cmd* cmds, int n_cmds, int sta
 // nodes/sampler.rs:331-414 (ring drained at the top of process()), volume.rs:92 (atomic load per block).
 // ... from index `lo` (the lower bound of (state_idx, block), or anything in front of it that is not this node's);
 // returns the index behind the last message applied — the node's cursor for its next block
+// XF: CMD_XF_TO is compiled in (k_level<0> and k_single_node only: the curve's solver stays out of every other user of this function)
+template <bool XF = false>
 __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t block, const Cmd* cmds, int n_cmds, const SampleDesc* samples,
                                       int lo, float* ext = nullptr, bool ext_write = false) {
     int i = lo;
@@ -160,6 +228,21 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                 s.playing = c.i0;
                 s.has_loop = c.i1;
                 break;
+            case CMD_XF_TO: if constexpr (XF) {  // crossfader: a new segment from where the old one stands at this block's first frame (s.playhead = T)
+                float from[1];
+                xf_positions<1>(xf_seg(s), s.playhead, from);
+                s.p0 = from[0];
+                s.p1 = c.f0;
+                s.loop_start = s.playhead;
+                s.full_range = c.i0;
+                s.has_loop = c.i1;
+                const unsigned long long u0 = (unsigned long long)__double_as_longlong(c.d0), u1 = (unsigned long long)__double_as_longlong(c.d1);
+                s.phasor = __int_as_float((int)(u0 & 0xffffffffull));
+                s.phasor_inc = __int_as_float((int)(u0 >> 32));
+                s.gain = __int_as_float((int)(u1 & 0xffffffffull));
+                s.aux = __int_as_float((int)(u1 >> 32));
+            }
+                break;  // (compiled out: the message is ignored, it does not fall through)
             case CMD_SMP_SET_LOOP:  // :400-412 + ProcLoopRange::new :241-263
                 if (c.i0 == 0) {
                     s.has_loop = 0;
@@ -182,10 +265,11 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
     }
     return i;
 }
+template <bool XF = false>
 __device__ inline void apply_cmds(NodeState& s, int state_idx, uint32_t block, const Cmd* cmds, int n_cmds,
                                   const SampleDesc* samples, float* ext = nullptr, bool ext_write = false) {
     if (n_cmds == 0) return;
-    apply_cmds_from(s, state_idx, block, cmds, n_cmds, samples, chain_cmd_lower_bound(cmds, n_cmds, state_idx, block), ext, ext_write);
+    apply_cmds_from<XF>(s, state_idx, block, cmds, n_cmds, samples, chain_cmd_lower_bound(cmds, n_cmds, state_idx, block), ext, ext_write);
 }
 
 // The same lower bound by a whole wave (all 64 lanes active, arguments wave-uniform): 64 pivots per round instead of one —

@@ -156,16 +156,90 @@ __device__ __forceinline__ void meter_store(v4f* rec, const MeterAcc& m, const i
     if (lane == 0) *rec = (v4f){p, t, __uint_as_float(m.over), __uint_as_float((uint32_t)frames)};
 }
 
+// K_CROSSFADE (SPEC crossfader), the two paths that blend: at rest in between and inside a segment.
+// T: node time of the block's first frame; rest: the block is at rest (at P1)
+__device__ __forceinline__ void xf_mix(float* pool, const int* in_buf, const int* out_buf, int stride, int frames, int lane, int n, uint64_t amask,
+                                       uint64_t bmask, uint64_t T, bool rest, int law, const XfSeg& g) {
+    const float P1 = g.P1;
+    float ra = 0.f, rb = 0.f;
+    if (rest) xf_gains(law, P1, ra, rb);  // at rest in between: the gains once per wave
+    for (int f0 = lane * 4; f0 < frames; f0 += 256) {
+        v4f p = splat(P1), ga = splat(ra), gb = splat(rb);
+        if (!rest) {  // inside a segment: a lane works out p, a, b of its four frames (the segment may end among them)
+            float pe[4];
+            xf_positions<4>(g, T + (uint64_t)f0, pe);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float a, b;
+                p[e] = pe[e];
+                xf_gains(law, p[e], a, b);
+                ga[e] = a;
+                gb[e] = b;
+            }
+        }
+        // four channels at a time, every load of the group issued before its first store (in and out may alias for all the
+        // compiler knows); a flagged channel counts as +0.0 and is not read; both flagged: (+0 * a) + (+0 * b) = +0, the zero fill
+        for (int c0 = 0; c0 < n; c0 += 4) {
+            v4f xa[4], xb[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                xa[u] = xb[u] = splat(0.f);
+                if (c0 + u < n && !mask_bit(amask, c0 + u)) xa[u] = *(const v4f*)(pool + (size_t)in_buf[c0 + u] * stride + f0);
+                if (c0 + u < n && !mask_bit(bmask, c0 + u)) xb[u] = *(const v4f*)(pool + (size_t)in_buf[n + c0 + u] * stride + f0);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (c0 + u < n) {
+                    v4f y = (xa[u] * ga) + (xb[u] * gb);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) y[e] = p[e] == 0.0f ? xa[u][e] : (p[e] == 1.0f ? xb[u][e] : y[e]);  // the ends copy bit for bit
+                    *(v4f*)(pool + (size_t)out_buf[c0 + u] * stride + f0) = y;
+                }
+        }
+    }
+}
+
+// One block of a crossfader, by one wave: the body of node_process_wave's case (the state is loaded, the block's messages are applied
+// and the state and the flags are stored there, as for every stateful kind).  false: a state the plan build would not let through —
+// nothing may be touched.  adv_blocks, frozen: k_frozen_scan found no message for the node in the batch — the node time of block b is
+// the batch's snapshot + b blocks, as a playing sampler's playhead, and the wave of the last block stores the state while earlier
+// blocks' waves may not have read it yet: the store rewrites the segment with the values it has
+__device__ __forceinline__ bool xf_block(const DevView& v, const NodeDesc& nd, int node_idx, const WaveIO& io, uint64_t in_mask, NodeState& s,
+                                         uint32_t adv_blocks, bool frozen, uint64_t& out_mask) {
+    if (!xf_state_ok(s, nd.n_in, nd.n_out)) return false;
+    const int lane = io.lane, frames = io.frames, n = nd.n_out;
+    const uint64_t T = frozen ? v.frozen_playhead[node_idx] + (uint64_t)adv_blocks * (uint64_t)frames : s.playhead;
+    s.playhead = T + (uint64_t)frames;  // (time advances in every case)
+    const uint32_t dur = (uint32_t)s.full_range;
+    const bool rest = dur == 0u || T - s.loop_start >= (uint64_t)dur;
+    const uint64_t amask = in_mask & mask_all_silent_bits(n), bmask = (in_mask >> n) & mask_all_silent_bits(n);
+    if (rest && (s.p1 == 0.0f || s.p1 == 1.0f)) {  // at rest at an end: a copy of one bus, the other is never loaded
+        const int off = s.p1 == 0.0f ? 0 : n;
+        out_mask = off ? bmask : amask;
+        for (int c = 0; c < n; ++c) {
+            const bool sil = mask_bit(out_mask, c);
+            for (int f0 = lane * 4; f0 < frames; f0 += 256) *(v4f*)(io.out(c) + f0) = sil ? splat(0.f) : *(const v4f*)(io.in(off + c) + f0);
+        }
+        return true;
+    }
+    out_mask = amask & bmask;
+    xf_mix(io.pool, io.in_buf, io.out_buf, io.stride, frames, lane, n, amask, bmask, T, rest, s.playing, xf_seg(s));
+    return true;
+}
+
 // node kinds whose audio half carries state from block to block
 __device__ __forceinline__ bool kind_is_stateful(int kind) {
     return kind == K_VOLUME || kind == K_SAMPLER || kind == K_BEEP || kind == K_PAN || kind == K_HARD_CLIP ||
-           kind == K_WIDTH || kind == K_BIQUAD || kind == K_DELAY || kind == K_RESAMPLER || kind == K_SPATIAL;
+           kind == K_WIDTH || kind == K_BIQUAD || kind == K_DELAY || kind == K_RESAMPLER || kind == K_SPATIAL || kind == K_CROSSFADE;
 }
 // (which of k_level's three instantiations runs a kind, or that a kernel of its own does: fwgpu_types.h kind_set)
 // SET: 0 / 1 / 2 = that set only, 3 = all kinds (single-node entry).
-// adv_blocks: a frozen, playing sampler (k_level) — put its playhead where `adv_blocks` steady blocks leave it first
+// adv_blocks: a frozen, playing sampler (k_level) — put its playhead where `adv_blocks` steady blocks leave it first; a frozen
+// crossfader: its node time is the batch's snapshot + adv_blocks blocks
+// (always inlined, and so are spatial_finish and frozen_finish below, as they have been into every kernel that calls them: a kernel
+//  with a call in it hands its DevView over through scratch and is given the registers its launch bounds allow)
 template <int SET>
-__device__ void node_process_wave(const DevView& v, int node_idx, uint32_t blk, uint32_t cmd_block, bool store_state = true,
+__device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx, uint32_t blk, uint32_t cmd_block, bool store_state = true,
                                   uint32_t adv_blocks = 0, bool frozen_sampler = false) {
     const NodeDesc nd = v.nodes[node_idx];
     if (nd.is_graph_io || nd.kind == K_FIR || kind_has_own_kernel(nd.kind)) return;  // I/O edges (k_graph_in/out); FIR banks run as MFMA GEMMs; k_limiter, k_ducker, k_delay_comp
@@ -195,7 +269,7 @@ __device__ void node_process_wave(const DevView& v, int node_idx, uint32_t blk, 
     const bool stateful = kind_is_stateful(nd.kind);
     if (stateful) {
         s = v.states[nd.state];
-        apply_cmds(s, nd.state, cmd_block, v.cmds, v.n_cmds, v.samples, v.ext, lane == 0);
+        apply_cmds<SET == 0 || SET == 3>(s, nd.state, cmd_block, v.cmds, v.n_cmds, v.samples, v.ext, lane == 0);
         if (nd.kind == K_BIQUAD && v.n_cmds) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // lane 0's coefficient stores
     }
 
@@ -737,6 +811,11 @@ __device__ void node_process_wave(const DevView& v, int node_idx, uint32_t blk, 
             break;
         }
 
+        case K_CROSSFADE: if constexpr (SET == 0 || SET == 3) {  // SPEC crossfader: inputs 0..n-1 bus A, n..2n-1 bus B, n outputs
+            if (!xf_block(v, nd, node_idx, io, in_mask, s, adv_blocks, frozen_sampler, out_mask)) return;
+            break;
+        }
+
         default: break;
     }
 
@@ -762,7 +841,7 @@ __global__ void k_frozen_scan(DevView v, int n_nodes, uint32_t cmd_block0, uint3
     bool fz = false, adv = false;
     bool spat = false;
     if (!nd.is_graph_io && (nd.kind == K_VOLUME || nd.kind == K_PAN || nd.kind == K_WIDTH || nd.kind == K_HARD_CLIP ||
-                            nd.kind == K_SAMPLER || nd.kind == K_SPATIAL)) {
+                            nd.kind == K_SAMPLER || nd.kind == K_SPATIAL || nd.kind == K_CROSSFADE)) {
         bool has_cmd = false;
         if (v.n_cmds) {
             const int c = chain_cmd_lower_bound(v.cmds, v.n_cmds, nd.state, cmd_block0);
@@ -788,6 +867,9 @@ __global__ void k_frozen_scan(DevView v, int n_nodes, uint32_t cmd_block0, uint3
                     }
                     break;
                 case K_HARD_CLIP: fz = true; break;
+                // SPEC crossfader: the position is a function of the node time, and block b's is the snapshot + b blocks — frozen as a
+                // steadily playing sampler is, in a segment or at rest; the last block's wave stores the state, the time advanced
+                case K_CROSSFADE: adv = fz = true; break;
                 // SPEC spatialiser: with both gains at rest all that moves is the 64-frame mono history, and that is the
                 // tail of the previous block's input (needs a block of at least SP_HIST frames)
                 case K_SPATIAL: spat = fz = v.frames >= SP_HIST && smoother_at_rest(s.s0, s.p0) && smoother_at_rest(s.s1, s.p1); break;
@@ -801,12 +883,12 @@ __global__ void k_frozen_scan(DevView v, int n_nodes, uint32_t cmd_block0, uint3
     }
     if (v.chain_done)  // (this batch's "rendered upstream" bits: fz_links)
         for (int w = 0; w < v.chain_words; ++w) v.chain_done[(size_t)i * v.chain_words + w] = 0u;
-    frozen[i] = fz ? (adv ? 2 : (spat ? 3 : 1)) : 0;  // 2: a playing sampler — the last block's wave stores the state; 3: a spatialiser
+    frozen[i] = fz ? (adv ? 2 : (spat ? 3 : 1)) : 0;  // 2: a playing sampler or a crossfader — the last block's wave stores the state; 3: a spatialiser
     if (adv) playhead_snap[i] = v.states[nd.state].playhead;
 }
 // block-0 wave of a frozen spatialiser, after its own blocks (it alone reads the stored history): the history the batch
 // leaves behind is the tail of the LAST block's input
-__device__ void spatial_finish(const DevView& v, int node_idx, uint32_t K) {
+__device__ __forceinline__ void spatial_finish(const DevView& v, int node_idx, uint32_t K) {
     const NodeDesc nd = v.nodes[node_idx];
     const int lane = threadIdx.x & (WAVE - 1);
     const float* pool = v.pool + (size_t)(K - 1) * v.pool_blk_stride;
@@ -817,7 +899,7 @@ __device__ void spatial_finish(const DevView& v, int node_idx, uint32_t K) {
     (v.ext + v.states[nd.state].ext_off)[lane] = m;
 }
 // block-0 wave of a frozen node: if some block of the batch had every input silent, its smoothers were reset
-__device__ void frozen_finish(const DevView& v, int node_idx, uint32_t K) {
+__device__ __forceinline__ void frozen_finish(const DevView& v, int node_idx, uint32_t K) {
     const NodeDesc nd = v.nodes[node_idx];
     if (nd.kind == K_HARD_CLIP || nd.kind == K_SAMPLER) return;
     NodeState s = v.states[nd.state];

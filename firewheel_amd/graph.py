@@ -423,6 +423,51 @@ class DelayCompNode(_Node):
         return [float(self.frames)]
 
 
+class CrossfadeNode(_Node):
+    """SPEC node: crossfader — two buses blended along an automated curve.  add_node(node.num_inputs, channels,
+    CrossfadeNode(...)): inputs 0..channels-1 are bus A, inputs channels..2*channels-1 bus B, `channels` outputs, channels in 1..8.
+    `position` 0 is all A, 1 all B; `law` LAW_LINEAR (a = 1 - p, b = p) or EQUAL_POWER (a = sqrt(1 - p), b = sqrt(p)).  With bus B left
+    unconnected the node is a fader of bus A: crossfade_to(1.0, ...) is a fade-out, crossfade_to(0.0, ...) a fade-in.  The position is
+    a pure function of the node's frame count, so a fade in flight renders block-parallel and bit-exact against the numpy model of
+    tests/test_crossfade.py; at rest at 0 or 1 the output is a copy of one bus, bit for bit.  No latency."""
+    KIND = 20
+    LAW_LINEAR, EQUAL_POWER = 0, 1
+    SHAPE_LINEAR, SHAPE_BEZIER = 0, 1
+    FRAMES_MAX = 1 << 24
+    # curves: None / LINEAR, or the two inner control points (x1, y1, x2, y2) of a cubic Bezier easing from (0, 0) to (1, 1)
+    LINEAR = None
+    EASE_IN = (0.42, 0.0, 1.0, 1.0)
+    EASE_OUT = (0.0, 0.0, 0.58, 1.0)
+    EASE_IN_OUT = (0.42, 0.0, 0.58, 1.0)
+
+    def __init__(self, position=0.0, law=EQUAL_POWER, channels=2):
+        self.position = position
+        self.law = law
+        self.channels = channels
+
+    @property
+    def num_inputs(self):
+        return 2 * self.channels
+
+    def params(self):
+        return [float(self.position), float(self.law)]
+
+    def crossfade_to(self, position, frames, curve=None, at_block=0):
+        """from block `at_block` of the next process call on, move to `position` over `frames` frames (0: a jump) along `curve`"""
+        shape, (x1, y1, x2, y2) = (self.SHAPE_LINEAR, (0.0, 0.0, 1.0, 1.0)) if curve is None else (self.SHAPE_BEZIER, curve)
+        self.cx._check(self.cx.L.fwgpu_crossfade_to(self.cx.c, self.id, position, frames, shape, x1, y1, x2, y2, at_block))
+        self.position = position
+
+    def crossfade_to_secs(self, position, secs, curve=None, at_block=0):
+        """... over `secs` seconds, rounded to whole frames of the context's sample rate"""
+        self.crossfade_to(position, max(0, int(round(secs * self.cx.sample_rate))), curve, at_block)
+
+    def set_position(self, position, at_block=0):
+        """a jump (fwgpu_node_set_param 0)"""
+        self._set(0, position, at_block)
+        self.position = position
+
+
 class _RawNode(_Node):
     def __init__(self, kind, params):
         self.KIND = kind

@@ -63,8 +63,10 @@ enum fwgpu_node_kind {
     FWGPU_DUCKER = 18,        /* SPEC sidechain ducker (n + k in, n out, n and k in 1..8)  params: threshold (linear, 1e-6..1000, default
                                  0.05), depth (0..1, default 0.25), attack_frames (1..32768, default 480), release_frames (1..32768,
                                  default 12000), hold_frames (0..32768, default 4800); see "sidechain ducker" below */
-    FWGPU_DELAY_COMP = 19     /* SPEC latency compensation (n in, n out, n in 1..8)  params: frames (a whole number in
+    FWGPU_DELAY_COMP = 19,    /* SPEC latency compensation (n in, n out, n in 1..8)  params: frames (a whole number in
                                  0..FWGPU_DELAY_COMP_MAX, default 63); see "latency compensation" below */
+    FWGPU_CROSSFADE = 20      /* SPEC crossfader (2n in, n out, n in 1..8)  params: position (0..1, default 0 = all of bus A), law
+                                 (0 linear, 1 equal power; default 1); see "crossfader" below and fwgpu_crossfade_to */
 };
 
 /* sample formats — core/sample_resource.rs:28-335 */
@@ -258,7 +260,8 @@ int fwgpu_sample_retired(fwgpu_ctx* ctx, int sample);
 /* VolumeNode::set_percent_volume (volume.rs:28-34) / SamplerNode::set_percent_volume (sampler.rs:171-177):
  * param 0.  BeepTestNode::set_enabled (beep_test.rs:30-32): param 0.  SPEC nodes: StereoPan 0 = pan;
  * StereoWidth 0 = width; Biquad 1 = cutoff_hz, 2 = q; Delay 1 = feedback, 2 = mix; Resampler 1 = ratio,
- * 3 = playing, 4 = seek (source frame); Spatial 0/1/2 = x/y/z. */
+ * 3 = playing, 4 = seek (source frame); Spatial 0/1/2 = x/y/z; Crossfade 0 = position (a jump: fwgpu_crossfade_to with
+ * frames 0). */
 int fwgpu_node_set_param(fwgpu_ctx* ctx, int64_t node, int param, float value, uint32_t at_block);
 /* The same for `n` messages in one call, in order (hosts behind a foreign-function interface pay per call: bench.py's variant B
  * issues a hundred per step).  Stops at the first message that fails and returns its (negative) error; the ones in front of it
@@ -523,6 +526,44 @@ typedef struct fwgpu_latency_skew {
 int64_t fwgpu_graph_latency_report(fwgpu_ctx* ctx, fwgpu_latency_skew* out, uint32_t cap);
 /* the arrival latency at the graph output node, max over its connected ports (0 with none): what picture sync needs */
 int fwgpu_graph_output_latency(fwgpu_ctx* ctx, uint32_t* frames);
+
+/* ---- crossfader (FWGPU_CROSSFADE; SPEC).  Two buses blended along an automated curve: explore music into
+ * combat music over three seconds with an ease, one room's reverb return into another's, a fade to black — one message instead of
+ * one fwgpu_node_set_param per block.  n_out = n outputs and n_in = 2n inputs, n in 1..8: inputs 0..n-1 are bus A, inputs n..2n-1
+ * bus B; any other shape is refused at fwgpu_add_node.  With bus B left unconnected the node is a fader of bus A with the same
+ * curves.  Creation parameters: position (0 = all A, 1 = all B) and law; a position that is NaN or outside 0..1 and a law other than
+ * 0 or 1 fail activation at fwgpu_update (FWGPU_ERR_INVALID).  The state is the node time T — a 64-bit count of the frames rendered
+ * since activation, full and short blocks alike —, one segment {P0, P1, t0, dur, shape, x1, y1, x2, y2} and the law; dur == 0 means
+ * at rest at P1.  No smoother, no ext slice; kept across plan changes.  Every operation below is a separately rounded f32 operation,
+ * no FMA.  The position of frame n (node time), with k = n - t0:
+ *   dur == 0 or k >= dur:  p = P1
+ *   otherwise              u = (float)k / (float)dur                  (IEEE division; both conversions exact, dur <= 2^24)
+ *     shape 0 (linear):    y = u
+ *     shape 1 (cubic Bezier easing through (0,0), (x1,y1), (x2,y2), (1,1)):  y = 0 when u == 0, otherwise with
+ *                          c = 3*a; b = 3*(d - a) - c; q = (1 - c) - b;  B(t; a, d) = ((q*t + b)*t + c)*t:
+ *                            lo = 0, hi = 1;  24 times: m = (lo + hi) * 0.5f; if B(m; x1, x2) < u then lo = m else hi = m
+ *                            t = (lo + hi) * 0.5f;  y = B(t; y1, y2)
+ *     p = P0 + ((P1 - P0) * y), clamped: p = fminf(fmaxf(p, 0), 1)    (a curve may overshoot; the position does not)
+ * Gains: linear law a = 1.0f - p, b = p; equal-power law a = sqrtf(1.0f - p), b = sqrtf(p), correctly rounded.  Output:
+ *   p == 0:  y_c = A_c, a copy bit for bit        p == 1:  y_c = B_c, a copy bit for bit        otherwise  y_c = (A_c * a) + (B_c * b)
+ * An input channel flagged silent for the block (an unconnected input is one) counts as +0.0 and is not read.  A block is at rest
+ * when dur == 0 or T - t0 >= dur at its first frame.  Output channel c is zero-filled and flagged exactly when A_c and B_c are both
+ * flagged, or the block is at rest at p == 0 and A_c is flagged, or the block is at rest at p == 1 and B_c is flagged; otherwise it is
+ * written and not flagged.  Time advances in every case.  No latency.  The position is a pure function of the node time, so the
+ * blocks of a batch that carries no message for the node render in parallel; only the batch in which a message lands is walked in
+ * order.  The level executor renders the node (inside k_level); the voice banks in front of it keep their fused kernels.
+ * fwgpu_node_process renders it block by block with the node time kept between calls.
+ *
+ * fwgpu_crossfade_to: from the start of block `at_block` of the next process call, move to `position` over `frames` frames along
+ * `shape` (0 linear, 1 Bezier with the control values x1, y1, x2, y2; they are ignored by shape 0).  Applied with T the node time of
+ * that block's first frame: P0 = the position the rule above gives frame T under the old segment — a retarget in mid-fade starts
+ * exactly where the old fade stands —, t0 = T, dur = frames, P1 = position.  frames == 0 is a jump.  Several messages for one block
+ * apply in order.  FWGPU_ERR_INVALID for a node of another kind, a position outside 0..1, frames > FWGPU_CROSSFADE_FRAMES_MAX, a
+ * shape other than 0 or 1, x1 or x2 outside 0..1, y1 or y2 outside -1..2, and any NaN. */
+#define FWGPU_CROSSFADE_FRAMES_MAX 16777216
+#define FWGPU_CROSSFADE_CH_MAX 8
+int fwgpu_crossfade_to(fwgpu_ctx* ctx, int64_t node, float position, uint32_t frames, int shape, float x1, float y1, float x2, float y2,
+                       uint32_t at_block);
 
 /* ProcInfo::stream_time_secs / stream_status (core/node.rs:111-132) of the most recent fwgpu_process_interleaved call —
  * what a custom node run through fwgpu_node_process inside that call would be handed — and how often the backend has

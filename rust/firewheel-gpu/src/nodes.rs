@@ -640,3 +640,76 @@ impl AudioNode for GpuDelayCompNode {
         self.b.deactivate()
     }
 }
+
+/// Crossfader (SPEC, DESIGN.md §6 of the fwgpu repository): two buses blended along an automated curve.  Inputs `0..n` are bus A,
+/// inputs `n..2n` bus B; `n` outputs, `n` in 1..=8.  Position 0 is all A, 1 all B.  The position is a pure function of the node's
+/// frame count, so a fade in flight renders block-parallel on the device; at rest at an end the output is a copy of one bus.  With
+/// bus B left unconnected the node is a fader of bus A with the same curves.
+pub struct GpuCrossfadeNode {
+    b: Binding,
+    position: f32,
+    law: CrossfadeLaw,
+}
+/// how the position becomes the two gains: `Linear` a = 1 - p, b = p; `EqualPower` a = sqrt(1 - p), b = sqrt(p)
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum CrossfadeLaw {
+    Linear = 0,
+    EqualPower = 1,
+}
+/// the shape of a segment: a straight line, or a cubic Bézier easing from (0, 0) to (1, 1) through (x1, y1) and (x2, y2)
+/// (x in 0..=1, y in -1..=2; the position itself is clamped to 0..=1)
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub enum CrossfadeCurve {
+    Linear,
+    Bezier(f32, f32, f32, f32),
+}
+impl CrossfadeCurve {
+    pub const EASE_IN: Self = Self::Bezier(0.42, 0.0, 1.0, 1.0);
+    pub const EASE_OUT: Self = Self::Bezier(0.0, 0.0, 0.58, 1.0);
+    pub const EASE_IN_OUT: Self = Self::Bezier(0.42, 0.0, 0.58, 1.0);
+}
+impl GpuCrossfadeNode {
+    /// the longest segment one message takes, in frames
+    pub const FRAMES_MAX: u32 = ffi::FWGPU_CROSSFADE_FRAMES_MAX;
+    /// `position`: 0..=1.  Anything else fails activation.
+    pub fn new(cx: &Arc<GpuContext>, position: f32, law: CrossfadeLaw) -> Self {
+        Self { b: Binding::new(cx), position, law }
+    }
+    /// the target of the last message (or the constructor's position)
+    pub fn position(&self) -> f32 {
+        self.position
+    }
+    /// From the next block on, move to `position` over `frames` frames (0: a jump) along `curve`; a retarget in mid-fade starts where
+    /// the old fade stands.  Before activation only the target is kept: the node then starts at rest there.
+    pub fn crossfade_to(&mut self, position: f32, frames: u32, curve: CrossfadeCurve) -> Result<(), GpuError> {
+        let (shape, x1, y1, x2, y2) = match curve {
+            CrossfadeCurve::Linear => (0, 0.0, 0.0, 1.0, 1.0),
+            CrossfadeCurve::Bezier(x1, y1, x2, y2) => (1, x1, y1, x2, y2),
+        };
+        if let Some(node) = self.b.node {
+            let _g = self.b.cx.control();
+            let rc = unsafe { ffi::fwgpu_crossfade_to(self.b.cx.as_ptr(), node, position, frames, shape, x1, y1, x2, y2, 0) };
+            self.b.cx.check(rc as i64)?;
+        }
+        self.position = position;
+        Ok(())
+    }
+    /// ... over `secs` seconds, rounded to whole frames of `sample_rate`
+    pub fn crossfade_to_secs(&mut self, position: f32, secs: f64, sample_rate: u32, curve: CrossfadeCurve) -> Result<(), GpuError> {
+        self.crossfade_to(position, (secs * sample_rate as f64).round().max(0.0) as u32, curve)
+    }
+}
+impl AudioNode for GpuCrossfadeNode {
+    fn debug_name(&self) -> &'static str {
+        "crossfade"
+    }
+    fn info(&self) -> AudioNodeInfo {
+        io(2, 16, 1, 8, false)
+    }
+    fn activate(&mut self, _sr: u32, _mbf: usize, num_inputs: usize, num_outputs: usize) -> Result<Box<dyn AudioNodeProcessor>, Box<dyn Error>> {
+        self.b.activate(ffi::FWGPU_CROSSFADE, num_inputs, num_outputs, &[self.position, self.law as i32 as f32])
+    }
+    fn deactivate(&mut self, _p: Option<Box<dyn AudioNodeProcessor>>) {
+        self.b.deactivate()
+    }
+}
