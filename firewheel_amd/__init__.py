@@ -34,10 +34,11 @@ from .graph import (  # noqa: F401
     StereoWidthNode,
     SumNode,
     VolumeNode,
+    doppler_ratio,
 )
 
 __all__ = [
     "FirewheelGpuCtx", "HostNode", "VolumeNode", "SumNode", "SamplerNode", "BeepTestNode", "HardClipNode", "MonoToStereoNode",
-    "StereoToMonoNode", "DummyAudioNode", "StereoPanNode", "StereoWidthNode", "BiquadNode", "DelayNode", "FirReverbNode", "ResamplerNode", "SpatialNode", "MeterNode", "LimiterNode", "DuckerNode", "CrossfadeNode", "DelayCompNode", "LoopRange", "SampleFormat", "AddEdgeError",
+    "StereoToMonoNode", "DummyAudioNode", "StereoPanNode", "StereoWidthNode", "BiquadNode", "DelayNode", "FirReverbNode", "ResamplerNode", "SpatialNode", "MeterNode", "LimiterNode", "DuckerNode", "CrossfadeNode", "DelayCompNode", "doppler_ratio", "LoopRange", "SampleFormat", "AddEdgeError",
     "CompileGraphError", "FwgpuError", "load_library", "build_library", "LIB_PATH",
 ]

@@ -833,6 +833,25 @@ int fwgpu_crossfade_to(fwgpu_ctx* c, int64_t node, float position, uint32_t fram
     }
     return push_cmd(c, node, K_CROSSFADE, m, false);
 }
+// SPEC resampler ratio glide: one CMD_RS_GLIDE — the step to reach as u64 bits in d0 (param 1's resampler_step), the
+// frames to reach it over in i0.  frames == 0 is param 1's message, a step.
+int fwgpu_resampler_glide(fwgpu_ctx* c, int64_t node, float ratio, uint32_t frames, uint32_t at_block) {
+    static_assert(FWGPU_RESAMPLER_GLIDE_FRAMES_MAX == RS_GLIDE_FRAMES_MAX, "the header's glide cap");
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    HostNode* n = c->graph.get(node);
+    if (!n) return fail(c, FWGPU_ERR_INVALID, "unknown node id");
+    if (n->kind != K_RESAMPLER) return fail(c, FWGPU_ERR_INVALID, "fwgpu_resampler_glide: the node is not a resampling source");
+    if (ratio != ratio) return fail(c, FWGPU_ERR_INVALID, "fwgpu_resampler_glide: ratio is NaN");
+    if (frames > FWGPU_RESAMPLER_GLIDE_FRAMES_MAX) return fail(c, FWGPU_ERR_INVALID, "fwgpu_resampler_glide: at most 2^24 frames");
+    Cmd m;
+    memset(&m, 0, sizeof(m));
+    m.block = at_block;
+    m.type = frames ? CMD_RS_GLIDE : CMD_RS_STEP;
+    m.i0 = (int)frames;
+    const uint64_t u = resampler_step(ratio);
+    memcpy(&m.d0, &u, 8);
+    return push_cmd(c, node, -1, m, false);
+}
 int fwgpu_node_set_param(fwgpu_ctx* c, int64_t node, int param, float value, uint32_t at_block) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
     HostNode* n = c->graph.get(node);

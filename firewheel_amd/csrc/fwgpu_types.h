@@ -130,7 +130,10 @@ struct NodeState {
     //   DELAY also uses p0 = feedback, p1 = mix, gain = dry (1-mix), playhead = ring position, loop_end = D
     //   FIR: ext = mirrored history ring[channels][2R]; playhead = ring position, loop_end = R, loop_start = T,
     //        sample = impulse-response sample id
-    //   RESAMPLER: sample = source, playhead = 32.32 source position, loop_start = 32.32 step, has_loop, playing
+    //   RESAMPLER: sample = source, playhead = 32.32 source position, loop_start = 32.32 step, has_loop, playing; a ratio glide
+    //        (CMD_RS_GLIDE): full_range = left (frames of the glide still to render, 0: none), loop_end = target (the
+    //        step behind the glide), enabled / ext_off = the low / high 32 bits of inc, the signed step change per frame (a
+    //        resampler has no ext slice: ext_len stays 0).  make_state leaves all four 0; the arithmetic is rs_glide_* below the struct
     //   SPATIAL: p0/p1 = ear gain targets (s0/s1 smooth them), playing = left-ear delay, has_loop = right-ear delay
     //        (frames), ext = the last SP_HIST mono samples
     //   METER: ext = ring[R][n_in] of MeterRec (4 floats each), loop_end = R (0: the creation parameter was refused)
@@ -173,6 +176,62 @@ FW_TYPES_HD inline bool dcomp_state_ok(const NodeState& s, int n_in, int n_out) 
 }
 FW_TYPES_HD inline uint32_t dcomp_ext_len(const NodeState& s, int n_in) { return (uint32_t)n_in * (uint32_t)s.loop_start + (uint32_t)n_in; }
 
+// K_RESAMPLER ratio glide (SPEC): ONE statement for the node kernels, the control kernel and the leaf kernel.  All in
+// wrapping u64 arithmetic; a signed inc travels as its two's-complement bits.
+#define RS_GLIDE_FRAMES_MAX 16777216u
+FW_TYPES_HD inline uint64_t rs_glide_inc(const NodeState& s) { return ((uint64_t)s.ext_off << 32) | (uint64_t)(uint32_t)s.enabled; }
+// the message, applied at a block's first frame: N frames from the step the node has reached to S1 (N == 0: a step)
+FW_TYPES_HD inline void rs_glide_start(NodeState& s, uint64_t S1, uint32_t N) {
+    // (N == 0 is the SPEC's step.  N > RS_GLIDE_FRAMES_MAX is NOT SPEC behaviour: fwgpu_resampler_glide refuses such a call, so only a
+    //  corrupted message gets here — a defensive branch that keeps `left` inside its 2^24 and the division's operands in range)
+    if (N == 0u || N > RS_GLIDE_FRAMES_MAX) {
+        s.loop_start = S1;
+        s.full_range = 0;
+        return;
+    }
+    const uint64_t inc = (uint64_t)((int64_t)(S1 - s.loop_start) / (int64_t)N);  // truncated toward zero
+    s.enabled = (int)(uint32_t)inc;
+    s.ext_off = (uint32_t)(inc >> 32);
+    s.full_range = (int)N;
+    s.loop_end = S1;
+}
+// 32.32 position of frame i of a run that starts at (pos0, step0) with `left` frames of the glide to go (left == 0: no glide, the
+// step is step0 throughout); frames behind the glide's end move by `target`
+FW_TYPES_HD inline uint64_t rs_glide_pos(uint64_t pos0, uint64_t step0, uint64_t inc, uint64_t left, uint64_t target, uint64_t i) {
+    const uint64_t m = i < left ? i : left;
+    const uint64_t tri = (m * (m - 1ull)) >> 1;  // m (m - 1) / 2 < 2^47 (m == 0: 0 x anything)
+    return pos0 + m * step0 + inc * tri + (i - m) * (left ? target : step0);
+}
+// the state behind a rendered block of `frames` frames (the position is rs_glide_pos(..., frames), taken BEFORE this)
+FW_TYPES_HD inline void rs_glide_advance(NodeState& s, uint32_t frames) {
+    const uint32_t left = (uint32_t)s.full_range;
+    if (left == 0u) return;
+    if (frames >= left) {
+        s.loop_start = s.loop_end;  // exactly the target
+        s.full_range = 0;
+    } else {
+        s.loop_start += (uint64_t)frames * rs_glide_inc(s);
+        s.full_range = (int)(left - frames);
+    }
+}
+// A VB_RS_GLIDE block's record (VoiceBlk): off0 / off1 = position / step of frame 0; src_r bits = inc in the low 41 bits (|inc| <
+// 2^40) and min(left, RS_GLIDE_LEFT_CAP) above them; n1 = the loop flag in bit 0 and, above it, target - (off1 + left x inc) + 2^24
+// — the remainder of the truncated division, below 2^24 in magnitude — from which a block the glide ends in rebuilds the target.
+// A block has fewer than RS_GLIDE_LEFT_CAP frames, so a capped `left` never ends inside one.
+#define RS_GLIDE_LEFT_CAP 0x7fffffu
+FW_TYPES_HD inline uint64_t rs_glide_pack(const NodeState& s) {
+    const uint32_t left = (uint32_t)s.full_range;
+    return (rs_glide_inc(s) & ((1ull << 41) - 1)) | ((uint64_t)(left < RS_GLIDE_LEFT_CAP ? left : RS_GLIDE_LEFT_CAP) << 41);
+}
+FW_TYPES_HD inline uint32_t rs_glide_rem(const NodeState& s) {
+    return (uint32_t)(s.loop_end - (s.loop_start + (uint64_t)(uint32_t)s.full_range * rs_glide_inc(s)) + (1ull << 24));
+}
+FW_TYPES_HD inline void rs_glide_unpack(uint64_t bits, uint32_t n1, uint64_t step0, uint64_t& inc, uint64_t& left, uint64_t& target) {
+    inc = (uint64_t)((int64_t)(bits << 23) >> 23);
+    left = bits >> 41;
+    target = step0 + left * inc + (uint64_t)(n1 >> 1) - (1ull << 24);
+}
+
 // K_CROSSFADE (rendered by k_level<0>, no ext slice): the states its case renders.  T never runs behind t0: a message sets t0 = T
 FW_TYPES_HD inline bool xf_state_ok(const NodeState& s, int n_in, int n_out) {
     const auto unit = [](float x) { return x >= 0.0f && x <= 1.0f; };  // (false for a NaN)
@@ -212,6 +271,7 @@ enum : int {
     CMD_RS_SEEK = 21,  // resampler: d0 bits = u64 source frame
     CMD_SP_ITD = 22,   // spatialiser: i0 / i1 = left / right ear delay in frames
     CMD_XF_TO = 23,    // crossfader: f0 = target position, i0 = frames, i1 = shape; d0 bits = (x1, y1), d1 bits = (x2, y2) as float bits
+    CMD_RS_GLIDE = 24,  // resampler: d0 bits = u64 32.32 step to reach, i0 = frames to reach it over (rs_glide_start)
 };
 struct Cmd {
     int state;
@@ -289,6 +349,8 @@ enum : uint32_t {
                           //   template FusedView::rs_tmpl[voice] — written once per call — with off0 = the 32.32 position carried in
                           //   VoiceRef::src_l; no VoiceBlk row is written for it (they were 75 MB per 768-block call of 1 024 voices,
                           //   and what the control kernel's 42 us went into)
+    VB_RS_GLIDE = 1u << 27,  // a VB_RESAMPLE block inside a ratio glide (VoiceBlk::flags only, never lean): the step changes by inc per frame —
+                          //   rs_glide_pack / rs_glide_rem above say where inc, left and the target sit; the frame-by-frame fetch renders it
     VB_FMT_SHIFT = 24,    // VB_RESAMPLE blocks: bits 24..26 = the sample's format (FMT_*), src_l = its data, pad = its frames (< 2^31)
                           //   — the leaf kernel needs no second dependent load for the sample table
     VB_RAMP_SHIFT = 8,    // bit (VB_RAMP_SHIFT + 2*stage + ch): that gain is a per-frame ramp (12 bits: 8..19)
@@ -300,7 +362,7 @@ enum : uint32_t {
 };
 struct VoiceBlk {
     uint32_t flags;
-    uint32_t n1;         // frames taken from off0
+    uint32_t n1;         // frames taken from off0 (VB_RESAMPLE: bit 0 = the source loops; VB_RS_GLIDE: rs_glide_rem above it)
     const float* src_l;  // frame 0 of channel 0 / 1 when the block's frames are contiguous planar f32
     const float* src_r;
     uint64_t off0;       // source frame of frame 0

@@ -222,7 +222,11 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
             case CMD_SMP_SET_PLAYHEAD:  // :392-399
                 s.playhead = sat_round_u64(c.d0 * (double)s.sample_rate);
                 break;
-            case CMD_RS_STEP: s.loop_start = (uint64_t)__double_as_longlong(c.d0); break;
+            case CMD_RS_STEP:  // (a step ends a glide in flight)
+                s.loop_start = (uint64_t)__double_as_longlong(c.d0);
+                s.full_range = 0;
+                break;
+            case CMD_RS_GLIDE: rs_glide_start(s, (uint64_t)__double_as_longlong(c.d0), (uint32_t)c.i0); break;
             case CMD_RS_SEEK: s.playhead = ((uint64_t)__double_as_longlong(c.d0)) << 32; break;
             case CMD_SP_ITD:
                 s.playing = c.i0;

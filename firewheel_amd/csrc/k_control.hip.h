@@ -1086,6 +1086,13 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
                 d.pad = (uint32_t)sd.frames;
                 if (sd.channels == 1) d.flags |= VB_MONO;
                 uint64_t np = ss.playhead + (uint64_t)frames * ss.loop_start;
+                if (ss.full_range != 0) {  // a ratio glide in flight (CMD_RS_GLIDE): the record carries inc, left and the target's remainder
+                    d.flags |= VB_RS_GLIDE;
+                    d.src_r = (const float*)rs_glide_pack(ss);
+                    d.n1 |= rs_glide_rem(ss) << 1;
+                    np = rs_glide_pos(ss.playhead, ss.loop_start, rs_glide_inc(ss), (uint64_t)(uint32_t)ss.full_range, ss.loop_end, (uint64_t)frames);
+                    rs_glide_advance(ss, (uint32_t)frames);
+                }
                 if (ss.has_loop) np %= (sd.frames << 32);
                 else if ((np >> 32) >= sd.frames + RS_TAPS / 2) ss.playing = 0;
                 ss.playhead = np;
@@ -1229,7 +1236,7 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
         if (ss.sample < 0 || !ss.playing || sd.data == nullptr || (vd.src_kind == 1 && sd.frames == 0)) {
             upstream_silent = true;  // frozen sampler: nothing moves
         } else if (vd.src_kind == 1) {  // resampling source: the position has a closed form while it keeps playing
-            if (cached_sample != ss.sample) steady = false;
+            if (cached_sample != ss.sample || ss.full_range != 0) steady = false;  // (a glide in flight: block by block, no lazy record)
             else if (ss.has_loop || rs_survives(ss.playhead, ss.loop_start, (uint64_t)frames, (uint64_t)(K - 1 - k), sd.frames)) mode = 3;
             else steady = false;  // the one-shot runs out inside this call: block by block
         } else {

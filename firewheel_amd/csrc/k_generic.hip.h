@@ -678,12 +678,14 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
                 break;
             }
             const uint64_t step = s.loop_start, pos = s.playhead;
+            // a ratio glide in flight (CMD_RS_GLIDE): the position is a quadratic in the frame index (fwgpu_types.h rs_glide_pos)
+            const uint64_t gl_left = (uint64_t)(uint32_t)s.full_range, gl_inc = rs_glide_inc(s), gl_target = s.loop_end;
             const bool loop = s.has_loop != 0;
             const int64_t len = (int64_t)sd.frames;
             const int sch = sd.channels;
             const int nfill = nd.n_out < sch ? nd.n_out : sch;
             for (int i = lane; i < frames; i += WAVE) {  // every output frame is independent
-                const uint64_t p = pos + (uint64_t)i * step;
+                const uint64_t p = gl_left ? rs_glide_pos(pos, step, gl_inc, gl_left, gl_target, (uint64_t)i) : pos + (uint64_t)i * step;
                 const int64_t idx = (int64_t)(p >> 32);
                 const float* hp = v.rs_table + ((uint32_t)(p >> 27) & (RS_PHASES - 1)) * RS_TAPS;
                 float first = 0.f;
@@ -712,7 +714,8 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
             }
             if (nd.n_out > sch && !(nd.n_out == 2 && sch == 1))
                 for (int c = sch; c < nd.n_out; ++c) out_mask |= (1ull << c);
-            uint64_t np = pos + (uint64_t)frames * step;
+            uint64_t np = gl_left ? rs_glide_pos(pos, step, gl_inc, gl_left, gl_target, (uint64_t)frames) : pos + (uint64_t)frames * step;
+            rs_glide_advance(s, (uint32_t)frames);
             if (loop) np %= ((uint64_t)len << 32);
             else if ((np >> 32) >= (uint64_t)len + RS_TAPS / 2) s.playing = 0;
             s.playhead = np;

@@ -100,12 +100,15 @@ __device__ __forceinline__ void voice_eval(const FusedView& fv, const VoiceBlk& 
         sd.channels = fv.samples[d.sample].channels;
         sd.format = fv.samples[d.sample].format;
         const int64_t len = (int64_t)sd.frames;
-        const bool loop = d.n1 != 0;
+        const bool loop = (d.n1 & 1u) != 0;
+        const bool glide = (d.flags & VB_RS_GLIDE) != 0;  // a ratio glide: the closed form of fwgpu_types.h rs_glide_pos
+        uint64_t gl_inc = 0ull, gl_left = 0ull, gl_target = 0ull;
+        if (glide) rs_glide_unpack((uint64_t)d.src_r, d.n1, d.off1, gl_inc, gl_left, gl_target);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float al = 0.f, ar = 0.f;
             if (f0 + j < frames) {
-                const uint64_t p = d.off0 + (uint64_t)(f0 + j) * d.off1;
+                const uint64_t p = glide ? rs_glide_pos(d.off0, d.off1, gl_inc, gl_left, gl_target, (uint64_t)(f0 + j)) : d.off0 + (uint64_t)(f0 + j) * d.off1;
                 const float* hp = fv.rs_table + ((uint32_t)(p >> 27) & (RS_PHASES - 1)) * RS_TAPS;
                 // index of tap 0.  A looping source keeps its position below len << 32 (len < 2^31) and a block adds less
                 // than 2^20 frames: the frame index fits 32 bits — ONE 32-bit remainder per frame, the taps wrap by
@@ -685,7 +688,8 @@ __device__ __forceinline__ RsPure rs_pure_lane(const FusedView& fv, const size_t
         const bool lean = (my_flags & VB_RS_LEAN) != 0;  // a steady voice: the call's template + this block's position from the record
         const VoiceBlk* b = lean ? fv.rs_tmpl + voice : fv.blks + row + lane;
         const uint32_t df = b->flags;
-        if ((df & VB_RESAMPLE) && !(df & VB_RAMP_MASK) && ((df >> VB_FMT_SHIFT) & 7u) == (uint32_t)FMT_P_F32) {
+        // (a VB_RS_GLIDE block is not pure: w_max and span below assume ONE step)
+        if ((df & VB_RESAMPLE) && !(df & (VB_RAMP_MASK | VB_RS_GLIDE)) && ((df >> VB_FMT_SHIFT) & 7u) == (uint32_t)FMT_P_F32) {
             const uint32_t len = b->pad;
             const uint64_t off0 = lean ? ref_pos : b->off0, step = b->off1;
             const bool loop = b->n1 != 0;
@@ -1151,7 +1155,8 @@ __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int lea
                 const int nfr = frames < 256 ? frames : 256;
                 const uint64_t w_max = (((uint64_t)nfr * step + 0xffffffffull) >> 32) + 1 + RS_TAPS;  // any piece of the block
                 const uint64_t i_end = (off0 + (uint64_t)frames * step) >> 32;
-                el = ((df >> VB_FMT_SHIFT) & 7u) == (uint32_t)FMT_P_F32 && w_max <= RS_WIN && (step >> 32) < 8 && i_end < (1ull << 30) && len < (1u << 30) &&
+                // (a VB_RS_GLIDE block takes the frame-by-frame fetch: the window below is sized for ONE step)
+                el = !(df & VB_RS_GLIDE) && ((df >> VB_FMT_SHIFT) & 7u) == (uint32_t)FMT_P_F32 && w_max <= RS_WIN && (step >> 32) < 8 && i_end < (1ull << 30) && len < (1u << 30) &&
                      len >= 1u && (!loop || len >= (uint32_t)RS_WIN + RS_TAPS);
                 if (el) {
                     my_l = b->src_l;

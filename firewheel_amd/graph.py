@@ -263,6 +263,24 @@ class ResamplerNode(_Node):  # SPEC node: resampling source — polyphase window
     def seek_frames(self, frame, at_block=0):
         self._set(4, float(frame), at_block)
 
+    GLIDE_FRAMES_MAX = 1 << 24
+
+    def glide_to(self, ratio, frames, at_block=0):
+        """from block `at_block` of the next process call on, move the ratio to `ratio` over `frames` output frames, linearly in the
+        32.32 step (0: a step, as set_ratio) — ONE message for a pitch that moves every frame (Doppler: see doppler_ratio).
+        `self.ratio` holds the TARGET from this call on, also while the node is still on its way there."""
+        self.cx._check(self.cx.L.fwgpu_resampler_glide(self.cx.c, self.id, ratio, frames, at_block))
+        self.ratio = ratio
+
+
+def doppler_ratio(base_ratio, radial_speed, speed_of_sound=343.0):
+    """the ratio of a source that moves at `radial_speed` along the line to the listener (same unit as `speed_of_sound`, > 0:
+    receding, the pitch drops): base_ratio * c / (c + v).  A source closing at the speed of sound or faster has no ratio."""
+    c, v = float(speed_of_sound), float(radial_speed)
+    if not c > 0.0 or not v > -c:
+        raise ValueError("doppler_ratio: radial_speed must be greater than -speed_of_sound (and speed_of_sound positive)")
+    return base_ratio * c / (c + v)
+
 
 class SpatialNode(_Node):  # SPEC node: 3D spatialiser — distance gain, equal-power pan, per-ear delay
     KIND = 14

@@ -565,6 +565,24 @@ int fwgpu_graph_output_latency(fwgpu_ctx* ctx, uint32_t* frames);
 int fwgpu_crossfade_to(fwgpu_ctx* ctx, int64_t node, float position, uint32_t frames, int shape, float x1, float y1, float x2, float y2,
                        uint32_t at_block);
 
+/* ---- resampling source: a ratio glide (Doppler) in one message (SPEC).
+ * fwgpu_resampler_glide: from the first frame of block `at_block` of the next process call, move the node's ratio to `ratio` over
+ * `frames` output frames, linearly in the 32.32 step.  With S the step the node has reached there (u64, 32.32), S1 the step param 1
+ * would set for `ratio` (clamped to [1/256, 256], rounded half away) and N = frames:
+ *   inc = (int64)(S1 - S) / (int64)N   (truncated toward zero; |S1 - S| < 2^40),   left = N,   target = S1
+ * Per rendered frame while left > 0: the frame is taken at pos; then pos += step; step += inc; left -= 1; when left reaches 0,
+ * step = target exactly.  Closed form for a run of m <= left frames from (pos0, step0), in wrapping u64 arithmetic:
+ *   step_i = step0 + i*inc,   pos_i = pos0 + i*step0 + inc * (i*(i-1)/2)
+ * Every step_i lies between the two ends, so the position never goes backwards.  Everything else is the resampler as it is: phase
+ * (p >> 27) & 31, the 16-tap fmaf chain ascending from +0.0, a loop takes pos %= len << 32 behind each block, a one-shot stops once
+ * (pos >> 32) >= len + 8, and a paused or sample-less source renders nothing and advances nothing, the glide included.
+ * frames == 0 is exactly param 1 (a step).  Param 1 during a glide ends it and sets the step; a second glide starts from the step the
+ * first has reached; a seek (param 4) and pause / play (param 3) leave the glide as it is; several messages for one block apply in
+ * send order.  A voice inside a glide is not steady: its calls run the control kernel, and lazy calls resume with the first call
+ * behind the glide.  FWGPU_ERR_INVALID for a node of another kind, a NaN ratio, or frames > FWGPU_RESAMPLER_GLIDE_FRAMES_MAX. */
+#define FWGPU_RESAMPLER_GLIDE_FRAMES_MAX 16777216
+int fwgpu_resampler_glide(fwgpu_ctx* ctx, int64_t node, float ratio, uint32_t frames, uint32_t at_block);
+
 /* ProcInfo::stream_time_secs / stream_status (core/node.rs:111-132) of the most recent fwgpu_process_interleaved call —
  * what a custom node run through fwgpu_node_process inside that call would be handed — and how often the backend has
  * reported StreamStatus::OUTPUT_UNDERFLOW (bit 1) / INPUT_OVERFLOW (bit 0) so far.  Any pointer may be NULL. */

@@ -446,6 +446,21 @@ impl GpuResamplerNode {
     pub fn seek(&mut self, source_frame: f32) {
         let _ = self.b.set_param(4, source_frame);
     }
+    /// the longest glide one message takes, in frames
+    pub const GLIDE_FRAMES_MAX: u32 = ffi::FWGPU_RESAMPLER_GLIDE_FRAMES_MAX;
+    /// From the next block on, move the ratio to `ratio` over `frames` output frames, linearly in the 32.32 step (0: a step, as
+    /// `set_ratio`) — one message for a pitch that moves every frame (Doppler).  A second glide starts from the step the first has
+    /// reached.  Before activation only the target is kept: the node then starts at that ratio.  The node's recorded ratio is the
+    /// TARGET from this call on, also while the glide is still in flight.
+    pub fn glide_to(&mut self, ratio: f32, frames: u32) -> Result<(), GpuError> {
+        if let Some(node) = self.b.node {
+            let _g = self.b.cx.control();
+            let rc = unsafe { ffi::fwgpu_resampler_glide(self.b.cx.as_ptr(), node, ratio, frames, 0) };
+            self.b.cx.check(rc as i64)?;
+        }
+        self.ratio = ratio;
+        Ok(())
+    }
 }
 impl AudioNode for GpuResamplerNode {
     fn debug_name(&self) -> &'static str {
