@@ -111,6 +111,7 @@ SIGNATURES = {
     "fwgpu_sampler_play": (ci, [vp, i64, u32]),
     "fwgpu_sampler_pause": (ci, [vp, i64, u32]),
     "fwgpu_sampler_stop": (ci, [vp, i64, u32]),
+    "fwgpu_sampler_fade": (ci, [vp, i64, f32, u32, ci, u32]),
     "fwgpu_sampler_set_playhead_secs": (ci, [vp, i64, f64, u32]),
     "fwgpu_sampler_set_loop_range": (ci, [vp, i64, ci, f64, f64, u32]),
     "fwgpu_process_interleaved": (ci, [vp, fp, fp, u32, u32, u64, f64, u32]),

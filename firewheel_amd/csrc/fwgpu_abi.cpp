@@ -1006,6 +1006,29 @@ static int simple_msg(fwgpu_ctx* c, int64_t node, int type, uint32_t at_block) {
 int fwgpu_sampler_play(fwgpu_ctx* c, int64_t node, uint32_t b) { return simple_msg(c, node, CMD_SMP_PLAY, b); }
 int fwgpu_sampler_pause(fwgpu_ctx* c, int64_t node, uint32_t b) { return simple_msg(c, node, CMD_SMP_PAUSE, b); }
 int fwgpu_sampler_stop(fwgpu_ctx* c, int64_t node, uint32_t b) { return simple_msg(c, node, CMD_SMP_STOP, b); }
+// SPEC sampler gain envelope: one CMD_SMP_FADE — the target in f0, the frames to reach it over in i0, what the sampler
+// does at the fade's end in i1
+int fwgpu_sampler_fade(fwgpu_ctx* c, int64_t node, float target, uint32_t frames, int then, uint32_t at_block) {
+    static_assert(FWGPU_SAMPLER_FADE_FRAMES_MAX == SMP_FADE_FRAMES_MAX, "the header's fade cap");
+    static_assert(FWGPU_FADE_NONE == SMP_FADE_NONE && FWGPU_FADE_PAUSE == SMP_FADE_PAUSE && FWGPU_FADE_STOP == SMP_FADE_STOP, "the header's fade ends");
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    HostNode* n = c->graph.get(node);
+    if (!n) return fail(c, FWGPU_ERR_INVALID, "unknown node id");
+    if (n->kind != K_SAMPLER) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_fade: the node is not a SamplerNode");
+    if (!(target >= 0.0f && target <= 1.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_fade: target must be in 0..1");
+    if (frames > FWGPU_SAMPLER_FADE_FRAMES_MAX) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_fade: at most 2^24 frames");
+    if (then < FWGPU_FADE_NONE || then > FWGPU_FADE_STOP) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_fade: then must be 0 (none), 1 (pause) or 2 (stop)");
+    if (frames == 0 && then != FWGPU_FADE_NONE)
+        return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_fade: a step (frames 0) has no end to pause or stop at: use fwgpu_sampler_pause / _stop");
+    Cmd m;
+    memset(&m, 0, sizeof(m));
+    m.block = at_block;
+    m.type = CMD_SMP_FADE;
+    m.f0 = target == 0.0f ? 0.0f : target;  // (-0.0 counts as +0.0)
+    m.i0 = (int)frames;
+    m.i1 = then;
+    return push_cmd(c, node, K_SAMPLER, m, true);
+}
 int fwgpu_sampler_set_playhead_secs(fwgpu_ctx* c, int64_t node, double secs, uint32_t at_block) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
     Cmd m;

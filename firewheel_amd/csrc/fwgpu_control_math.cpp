@@ -137,6 +137,7 @@ NodeState make_state(int kind, const float* params, int n_params, uint32_t sampl
         case K_SAMPLER:  // sampler.rs:55-64, :302-319
             s.p0 = percent_volume_to_raw_gain(fmaxf(p(0, 100.0f), 0.0f));
             s.s0 = make_smoother(s.p0, sample_rate);
+            if (kind == K_SAMPLER) smp_env_reset(s);  // SPEC gain envelope: a new sampler rests at 1.0f
             break;
         case K_BEEP: {  // beep_test.rs:15-24, :55-60
             float f = p(0, 440.0f);

@@ -130,6 +130,12 @@ struct NodeState {
     //   DELAY also uses p0 = feedback, p1 = mix, gain = dry (1-mix), playhead = ring position, loop_end = D
     //   FIR: ext = mirrored history ring[channels][2R]; playhead = ring position, loop_end = R, loop_start = T,
     //        sample = impulse-response sample id
+    //   SAMPLER also keeps its gain envelope (CMD_SMP_FADE) in fields it has no other use for: phasor = E0, gain = E1,
+    //        enabled = N in bits 0..24 and `then` (SMP_FADE_*) in bits 28..29, s1.status = k (frames of the fade rendered, k < N).
+    //        At rest: enabled == 0 and s1.status == 0, the value is E1 = gain.  make_state leaves a new sampler at rest at 1.0f; no
+    //        message but CMD_SMP_FADE reaches these fields (a sampler's only parameter is p0); a node's state keeps its slot over
+    //        a plan install (only the steady cache is carried, and a voice in a fade has none), and k_lazy_flush moves the playhead alone — a voice in a fade leaves no lazy record.  The arithmetic is
+    //        smp_env_* below the struct
     //   RESAMPLER: sample = source, playhead = 32.32 source position, loop_start = 32.32 step, has_loop, playing; a ratio glide
     //        (CMD_RS_GLIDE): full_range = left (frames of the glide still to render, 0: none), loop_end = target (the
     //        step behind the glide), enabled / ext_off = the low / high 32 bits of inc, the signed step change per frame (a
@@ -232,6 +238,91 @@ FW_TYPES_HD inline void rs_glide_unpack(uint64_t bits, uint32_t n1, uint64_t ste
     target = step0 + left * inc + (uint64_t)(n1 >> 1) - (1ull << 24);
 }
 
+// K_SAMPLER gain envelope (SPEC): ONE statement for the message (apply_cmds_from), the node kernels and the control
+// kernel.  E0 -> E1 over N frames, k of them rendered; at rest (N == 0) the value is E1.  Every operation below is a separately rounded
+// f32 operation (-ffp-contract=off), the division is IEEE, and (float)(k + j), (float)N are exact (both <= 2^24).
+#define SMP_FADE_FRAMES_MAX 16777216u
+#define SMP_FADE_NONE 0
+#define SMP_FADE_PAUSE 1
+#define SMP_FADE_STOP 2
+FW_TYPES_HD inline uint32_t smp_env_N(const NodeState& s) { return (uint32_t)s.enabled & 0x1ffffffu; }
+FW_TYPES_HD inline int smp_env_then(const NodeState& s) { return (s.enabled >> 28) & 3; }
+FW_TYPES_HD inline bool smp_env_at_rest(const NodeState& s) { return smp_env_N(s) == 0u; }
+// the envelope as a block's render loop reads it: a snapshot taken BEFORE the block's advance, d = E1 - E0 computed once
+struct SmpEnv {
+    float E0, E1, d, lo, hi;
+    uint32_t N, k;
+};
+FW_TYPES_HD inline SmpEnv smp_env_of(const NodeState& s) {
+    SmpEnv e;
+    e.E0 = s.phasor;
+    e.E1 = s.gain;
+    e.d = e.E1 - e.E0;
+    e.lo = e.E0 < e.E1 ? e.E0 : e.E1;
+    e.hi = e.E0 < e.E1 ? e.E1 : e.E0;
+    e.N = smp_env_N(s);
+    e.k = (uint32_t)s.s1.status;
+    return e;
+}
+// env(j): the value of the frame j frames ahead of the snapshot's position (the clamp: E0 + d can round one ulp past E1)
+FW_TYPES_HD inline float smp_env_value(const SmpEnv& e, uint32_t j) {
+    const uint32_t t = e.k + j;
+    if (e.N == 0u || t >= e.N) return e.E1;
+    const float v = e.E0 + (e.d * ((float)t / (float)e.N));
+    return v < e.lo ? e.lo : (v > e.hi ? e.hi : v);
+}
+FW_TYPES_HD inline void smp_env_reset(NodeState& s) {  // the envelope is a transient: at rest at 1.0f, then = NONE
+    s.gain = 1.0f;
+    s.enabled = 0;
+    s.s1.status = 0;
+}
+// the message, applied at a block's first frame: `frames` frames from where the envelope stands to `target` (frames == 0: a step)
+FW_TYPES_HD inline void smp_env_start(NodeState& s, float target, uint32_t frames, int then) {
+    // (frames > SMP_FADE_FRAMES_MAX or a `then` outside 0..2 is NOT SPEC behaviour: fwgpu_sampler_fade refuses such a call, so only a
+    //  corrupted message gets here — a defensive branch that keeps k and N inside their 2^24)
+    if (frames == 0u || frames > SMP_FADE_FRAMES_MAX || then < SMP_FADE_NONE || then > SMP_FADE_STOP) {
+        s.gain = target;
+        s.enabled = 0;
+        s.s1.status = 0;
+        return;
+    }
+    s.phasor = smp_env_value(smp_env_of(s), 0u);  // a retarget in mid-fade continues from where the fade stands
+    s.gain = target;
+    s.enabled = (int)(frames | ((uint32_t)then << 28));
+    s.s1.status = 0;
+}
+// CMD_SMP_PAUSE / CMD_SMP_STOP (sampler.rs:372-391), as messages and as what a fade's `then` asks for
+FW_TYPES_HD inline void smp_pause(NodeState& s) {
+    s.playing = 0;
+    smp_env_reset(s);
+}
+FW_TYPES_HD inline void smp_stop(NodeState& s) {
+    s.playhead = s.has_loop ? s.loop_start : 0;
+    s.playing = 0;
+    smp_env_reset(s);
+}
+// behind a rendered block of `frames` frames in which the gain smoother ran (the values are smp_env_value of a snapshot taken BEFORE
+// this): k += frames; a fade that is over comes to rest and its `then` takes effect; a sampler that no longer plays — paused or
+// stopped by `then`, or a one-shot that ended in this block — has its envelope back at rest at 1.0f
+FW_TYPES_HD inline void smp_env_behind_block(NodeState& s, uint32_t frames) {
+    const uint32_t N = smp_env_N(s);
+    if (N != 0u) {
+        const uint32_t k = (uint32_t)s.s1.status + frames;
+        if (k < N) {
+            s.s1.status = (int)k;
+        } else {
+            const int then = smp_env_then(s);
+            s.enabled = 0;
+            s.s1.status = 0;
+            if (then == SMP_FADE_PAUSE) smp_pause(s);
+            else if (then == SMP_FADE_STOP) smp_stop(s);
+        }
+    }
+    if (!s.playing) smp_env_reset(s);
+}
+// the sampler's constant gain while its smoother (value c) and its envelope rest: what every frozen / steady / lazy path multiplies by
+FW_TYPES_HD inline float smp_rest_gain(const NodeState& s, float c) { return c * s.gain; }
+
 // K_CROSSFADE (rendered by k_level<0>, no ext slice): the states its case renders.  T never runs behind t0: a message sets t0 = T
 FW_TYPES_HD inline bool xf_state_ok(const NodeState& s, int n_in, int n_out) {
     const auto unit = [](float x) { return x >= 0.0f && x <= 1.0f; };  // (false for a NaN)
@@ -267,6 +358,7 @@ enum : int {
     CMD_SET_COEFS = 4,  // biquad: f0,i0,i1 (as float bits) = b0,b1,b2; d0 bits = (a1,a2)
     CMD_SMP_SET_SAMPLE = 10, CMD_SMP_PLAY = 11, CMD_SMP_PAUSE = 12, CMD_SMP_STOP = 13,
     CMD_SMP_SET_PLAYHEAD = 14, CMD_SMP_SET_LOOP = 15,
+    CMD_SMP_FADE = 16,  // sampler: f0 = target gain (0..1), i0 = frames to reach it over, i1 = then (SMP_FADE_*) (smp_env_start)
     CMD_RS_STEP = 20,  // resampler: d0 bits = u64 32.32 step
     CMD_RS_SEEK = 21,  // resampler: d0 bits = u64 source frame
     CMD_SP_ITD = 22,   // spatialiser: i0 / i1 = left / right ear delay in frames

@@ -179,9 +179,12 @@ __device__ inline int chain_cmd_lower_bound(const Cmd* cmds, int n_cmds, int sta
 // ... from index `lo` (the lower bound of (state_idx, block), or anything in front of it that is not this node's);
 // returns the index behind the last message applied — the node's cursor for its next block
 // XF: CMD_XF_TO is compiled in (k_level<0> and k_single_node only: the curve's solver stays out of every other user of this function)
-template <bool XF = false>
+// SMP: the sampler's gain envelope (fwgpu_types.h smp_env_*) is compiled in (k_level<2>, k_single_node and the control wave: every
+// other kernel keeps the code it had); smp_env: the node IS a SamplerNode — its envelope takes CMD_SMP_FADE and goes to rest with
+// every pause and stop.  (A resampling source takes pause messages too and keeps a ratio glide in the same fields: never set for one.)
+template <bool XF = false, bool SMP = false>
 __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t block, const Cmd* cmds, int n_cmds, const SampleDesc* samples,
-                                      int lo, float* ext = nullptr, bool ext_write = false) {
+                                      int lo, float* ext = nullptr, bool ext_write = false, bool smp_env = false) {
     int i = lo;
     for (; i < n_cmds; ++i) {
         Cmd c = cmds[i];
@@ -211,13 +214,23 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                 if (c.i1) {  // stop_playback
                     s.playhead = s.has_loop ? s.loop_start : 0;
                     s.playing = 0;
+                    if (SMP && smp_env) smp_env_reset(s);
                 }
                 break;
-            case CMD_SMP_PLAY: s.playing = 1; break;   // :365-371
-            case CMD_SMP_PAUSE: s.playing = 0; break;  // :372-378
-            case CMD_SMP_STOP:                         // :379-391
+            case CMD_SMP_PLAY: s.playing = 1; break;  // :365-371
+            case CMD_SMP_PAUSE:                       // :372-378
+                s.playing = 0;
+                if (SMP && smp_env) smp_env_reset(s);
+                break;
+            case CMD_SMP_STOP:  // :379-391
                 s.playhead = s.has_loop ? s.loop_start : 0;
                 s.playing = 0;
+                if (SMP && smp_env) smp_env_reset(s);
+                break;
+            case CMD_SMP_FADE:  // SPEC gain envelope
+                if constexpr (SMP) {
+                    if (smp_env) smp_env_start(s, c.f0, (uint32_t)c.i0, c.i1);
+                }
                 break;
             case CMD_SMP_SET_PLAYHEAD:  // :392-399
                 s.playhead = sat_round_u64(c.d0 * (double)s.sample_rate);
@@ -269,11 +282,11 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
     }
     return i;
 }
-template <bool XF = false>
+template <bool XF = false, bool SMP = false>
 __device__ inline void apply_cmds(NodeState& s, int state_idx, uint32_t block, const Cmd* cmds, int n_cmds,
-                                  const SampleDesc* samples, float* ext = nullptr, bool ext_write = false) {
+                                  const SampleDesc* samples, float* ext = nullptr, bool ext_write = false, bool smp_env = false) {
     if (n_cmds == 0) return;
-    apply_cmds_from<XF>(s, state_idx, block, cmds, n_cmds, samples, chain_cmd_lower_bound(cmds, n_cmds, state_idx, block), ext, ext_write);
+    apply_cmds_from<XF, SMP>(s, state_idx, block, cmds, n_cmds, samples, chain_cmd_lower_bound(cmds, n_cmds, state_idx, block), ext, ext_write, smp_env);
 }
 
 // The same lower bound by a whole wave (all 64 lanes active, arguments wave-uniform): 64 pivots per round instead of one —

@@ -189,6 +189,29 @@ __device__ __forceinline__ int ramp_glide(Smoother& s, float target, int frames,
     return r[3];
 }
 
+// SPEC gain envelope (fwgpu_types.h smp_env_*): stage 0's two ramp rows of a block = s[i] * env(i), one f32 product.
+// s[i] is the smoother's ramp where ramp_emit has just written one into the rows (had_ramp: the rows are read back — other lanes stored
+// them, hence the fence) and the constant c elsewhere.  Behind a call, and only voices in a fade (or resting off 1.0 under a moving
+// smoother) take it: the control wave of every other voice — and the realtime kernels that inline that wave — pay one test.
+__device__ __attribute__((noinline)) void env_rows(float* row0, float* row1, const int frames, const int lane, const float c, const int had_ramp,
+                                                   const float E0, const float E1, const uint32_t N, const uint32_t k) {
+    SmpEnv e;
+    e.E0 = E0;
+    e.E1 = E1;
+    e.d = E1 - E0;
+    e.lo = E0 < E1 ? E0 : E1;
+    e.hi = E0 < E1 ? E1 : E0;
+    e.N = N;
+    e.k = k;
+    if (had_ramp) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    for (int i = lane; i < frames; i += WAVE) {
+        const float sv = had_ramp ? row0[i] : c;
+        const float g = sv * smp_env_value(e, (uint32_t)i);
+        row0[i] = g;
+        row1[i] = g;
+    }
+}
+
 // A smoother whose next set_and_process(target) returns the same constant and leaves its state untouched:
 // not Active, or Active but stalled at the f32 fixed point above settle_epsilon (Q28).
 __device__ __forceinline__ bool smoother_is_constant(const Smoother& s, float target) {
@@ -1042,7 +1065,7 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
         // vmcnt wait in the ramp code (with the lookups interleaved, every 64-frame ramp chunk store first drained the
         // previous one: loads and stores share the in-order vmcnt counter on gfx9).
         if (k <= last_cmd) {
-            cur_smp = apply_cmds_from(ss, vd.sampler_state, cb, fv.cmds, fv.n_cmds, fv.samples, cur_smp);
+            cur_smp = apply_cmds_from<false, true>(ss, vd.sampler_state, cb, fv.cmds, fv.n_cmds, fv.samples, cur_smp, nullptr, false, vd.src_kind != 1);
 #pragma unroll
             for (int j = 0; j < FW_MAX_STAGES - 1; ++j) {
                 if (j < vd.n_stages) {
@@ -1099,13 +1122,19 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
             }
         } else if (ss.sample >= 0 && ss.playing && sd.data != nullptr) {
             GainRun run = smoother_begin(ss.s0, ss.p0, frames);
+            // SPEC gain envelope: it moves with the smoother, in every block that gets here.  The values of THIS block
+            // come from the state as it stands here; the state moves on behind the block (smp_env_behind_block)
+            const float envE0 = ss.phasor, envE1 = ss.gain;
+            const uint32_t envN = smp_env_N(ss), envk = (uint32_t)ss.s1.status;
             if (!(!smoother_is_smoothing(ss.s0) && run.c < 0.00001f)) {
                 Fetch ft;
                 bool ok = sampler_advance(ss, sd.frames, (uint32_t)frames, ft);
+                bool had_ramp = false;
                 if (run.ramp) {
                     if (ramp_emit(run, frames, ramp_base, ramp_base + fv.stride, lane)) {
                         d.flags |= 3u << VB_RAMP_SHIFT;
                         ss.s0.last = run.prev;
+                        had_ramp = true;
                     }
                 }
                 if (ok) {
@@ -1118,8 +1147,15 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
                     if (ft.tail_zero) d.flags |= VB_TAIL_ZERO;
                     if (sd.channels == 1) d.flags |= VB_MONO;
                     d.g[0][0] = d.g[0][1] = run.c;
+                    if (envN != 0u || (had_ramp && envE1 != 1.0f)) {  // in a fade (or a ramp under an envelope resting off 1.0): per-frame gains
+                        env_rows(ramp_base, ramp_base + fv.stride, frames, lane, run.c, had_ramp ? 1 : 0, envE0, envE1, envN, envk);
+                        d.flags |= 3u << VB_RAMP_SHIFT;
+                    } else if (envE1 != 1.0f) {  // at rest at E1: a constant, as every path that keeps constants wants it
+                        d.g[0][0] = d.g[0][1] = run.c * envE1;
+                    }
                 }
             }
+            smp_env_behind_block(ss, (uint32_t)frames);
         }
         CTL_T(10);
         // a biquad / delay between the sampler and the gain stages never reports silence (SPEC nodes: out mask 0)
@@ -1241,6 +1277,9 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
             else steady = false;  // the one-shot runs out inside this call: block by block
         } else {
             if (!smoother_is_constant(ss.s0, ss.p0)) ramping = true;
+            // a fade in flight: block by block, no lazy record (as a ratio glide is); and the ramp continuation writes the smoother's
+            // values alone — a voice whose envelope rests anywhere but at 1.0f stays block by block while its smoother moves
+            if (!smp_env_at_rest(ss) || (ramping && ss.gain != 1.0f)) steady = false;
             if (!ramping && ss.s0.status == SM_INACTIVE && ss.s0.input < 0.00001f) upstream_silent = true;  // muted, frozen
             else if (ss.has_loop) {
                 uint64_t L = ss.loop_end - ss.loop_start;
@@ -1360,7 +1399,7 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
         if (!upstream_silent) {
             if (sd.channels == 1) job.flags |= VB_MONO;
             if (mode == 3) job.flags |= VB_RESAMPLE;
-            else job.g.g[0][0] = job.g.g[0][1] = ss.s0.status == SM_ACTIVE ? ss.s0.last : ss.s0.input;
+            else job.g.g[0][0] = job.g.g[0][1] = smp_rest_gain(ss, ss.s0.status == SM_ACTIVE ? ss.s0.last : ss.s0.input);
         }
 #pragma unroll
         for (int j = 0; j < FW_MAX_STAGES - 1; ++j) {

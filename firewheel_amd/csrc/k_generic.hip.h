@@ -269,7 +269,7 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
     const bool stateful = kind_is_stateful(nd.kind);
     if (stateful) {
         s = v.states[nd.state];
-        apply_cmds<SET == 0 || SET == 3>(s, nd.state, cmd_block, v.cmds, v.n_cmds, v.samples, v.ext, lane == 0);
+        apply_cmds<SET == 0 || SET == 3, SET == 2 || SET == 3>(s, nd.state, cmd_block, v.cmds, v.n_cmds, v.samples, v.ext, lane == 0, nd.kind == K_SAMPLER);
         if (nd.kind == K_BIQUAD && v.n_cmds) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // lane 0's coefficient stores
     }
 
@@ -393,8 +393,12 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
                 break;
             }
             GainRun run = smoother_begin(s.s0, s.p0, frames);        // :432-433
-            if (!smoother_is_smoothing(s.s0) && run.c < 0.00001f) {  // :437-443
+            // SPEC gain envelope: it moves with the smoother — in every block that gets here, whatever happens below.
+            // `env`: the envelope as this block's frames read it; the state moves on behind the block (smp_env_behind_block), on every exit
+            const SmpEnv env = smp_env_of(s);
+            if (!smoother_is_smoothing(s.s0) && run.c < 0.00001f) {  // :437-443 (a test on the smoother alone)
                 out_mask = clear_all_outputs(io, 0, nd.n_out);
+                smp_env_behind_block(s, (uint32_t)frames);
                 break;
             }
             // the batch-start playhead comes from k_frozen_scan's snapshot: the wave of the batch's last block stores the
@@ -420,6 +424,7 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
                     s.s0.last = run.prev;
                 }
                 out_mask = clear_all_outputs(io, 0, nd.n_out);
+                smp_env_behind_block(s, (uint32_t)frames);
                 break;
             }
             const int sch = sd.channels;
@@ -433,6 +438,8 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
                 v4f g = gain_chunk(run, n, lane);
                 int f0 = base + lane * 4;
                 if (f0 >= frames) continue;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) g[j] = g[j] * smp_env_value(env, (uint32_t)(f0 + j));  // g[i] = s[i] * env(i), one product
                 v4f first = splat(0.f);
                 for (int c = 0; c < nfill; ++c) {
                     v4f x = (vec_src && f0 + 4 <= frames ? (v4f)(*(const v4f_u*)(vsrc + (size_t)c * sd.frames + f0))
@@ -451,6 +458,7 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
             if (nd.n_out > sch && !(nd.n_out == 2 && sch == 1))
                 for (int c = sch; c < nd.n_out; ++c) out_mask |= (1ull << c);  // :556
             if (run.ramp) s.s0.last = run.prev;
+            smp_env_behind_block(s, (uint32_t)frames);
             break;
         }
 
@@ -856,7 +864,7 @@ __global__ void k_frozen_scan(DevView v, int n_nodes, uint32_t cmd_block0, uint3
                 case K_SAMPLER:  // steady playback: the playhead of block b has a closed form (see node_process_wave)
                     if (s.sample < 0 || !s.playing || v.samples[s.sample].data == nullptr) {
                         fz = true;  // outputs cleared, nothing moves (sampler.rs:416-430)
-                    } else if (smoother_at_rest(s.s0, s.p0)) {
+                    } else if (smoother_at_rest(s.s0, s.p0) && smp_env_at_rest(s)) {  // (a fade in flight moves every block: the serial path)
                         if (s.s0.status == SM_INACTIVE && s.s0.input < 0.00001f) {
                             fz = true;  // muted: cleared, the playhead does not move (:437-443)
                         } else if (s.has_loop) {
@@ -1272,7 +1280,7 @@ __device__ __forceinline__ uint32_t frozen_fast(const DevView& v, const int node
         const int has_loop = s0.has_loop;
         uint32_t todo = 0u;
         if (sd.format != FMT_P_F32 || sd.channels != 2) return ~0u;
-        const float g = s0.s0.input;  // (k_frozen_scan: the gain rests and is no mute)
+        const float g = smp_rest_gain(s0, s0.s0.input);  // (k_frozen_scan: the gain rests and is no mute, the envelope rests at E1)
         const uint64_t ph0 = v.frozen_playhead[node];
         FzLinks L;  // (a playing sampler's block is never flagged silent: every block of the fast path goes on through the links)
         fz_links(v, nd.aux0, L);

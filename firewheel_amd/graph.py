@@ -148,6 +148,37 @@ class SamplerNode(_Node):  # nodes/sampler.rs:46-182
         lr = loop_range or LoopRange(LoopRange.NONE)
         self.cx._check(self.cx.L.fwgpu_sampler_set_loop_range(self.cx.c, self.id, lr.mode, lr.start, lr.end, at_block))
 
+    # ---- SPEC gain envelope: declicked pause, stop and start in one message each
+    FADE_FRAMES_MAX = 1 << 24
+    FADE_THEN = {None: 0, "none": 0, "pause": 1, "stop": 2}
+
+    def fade_to(self, gain, frames, then=None, at_block=0):
+        """from block `at_block` of the next process call on, move the voice's gain envelope to `gain` (0..1) over `frames` frames,
+        linearly (0: a step); `then` = None, "pause" or "stop": what the sampler does at the fade's end (fwgpu_sampler_fade).  The
+        envelope is a transient — every pause and stop puts it back to 1.0 — so a level that should last belongs in percent_volume.
+        With a `then`, is_playing() is False from this call on, as after pause() / stop(): the voice is on its way out."""
+        if then not in self.FADE_THEN:
+            raise ValueError("fade_to: then must be None, 'pause' or 'stop'")
+        self.cx._check(self.cx.L.fwgpu_sampler_fade(self.cx.c, self.id, gain, frames, self.FADE_THEN[then], at_block))
+        if self.FADE_THEN[then]:
+            self.playing = False
+
+    def fade_to_secs(self, gain, secs, then=None, at_block=0):
+        """... over `secs` seconds, rounded to whole frames of the context's sample rate"""
+        self.fade_to(gain, max(0, int(round(secs * self.cx.sample_rate))), then, at_block)
+
+    def fade_out(self, frames, then="stop", at_block=0):
+        """a declicked stop (or pause): down to 0 over `frames` frames, then `then`"""
+        self.fade_to(0.0, frames, then, at_block)
+
+    def fade_in(self, frames, at_block=0):
+        """a declicked start of a voice that is not playing — three messages for one block: the envelope steps to 0, the voice
+        plays, the envelope rises to 1 over `frames` frames"""
+        self.fade_to(0.0, 0, None, at_block)
+        self.cx._check(self.cx.L.fwgpu_sampler_play(self.cx.c, self.id, at_block))
+        self.playing = True
+        self.fade_to(1.0, frames, None, at_block)
+
 
 class HardClipNode(_Node):  # nodes/hard_clip.rs:7-13
     KIND = 5

@@ -278,6 +278,37 @@ int fwgpu_sampler_set_playhead_secs(fwgpu_ctx* ctx, int64_t node, double playhea
 int fwgpu_sampler_set_loop_range(fwgpu_ctx* ctx, int64_t node, int mode, double start_secs,
                                  double end_secs, uint32_t at_block);
 
+/* ---- sampler: a gain envelope per voice — declicked pause, stop and start in one message (SPEC).
+ * fwgpu_sampler_fade: from the first frame of block `at_block` of the next process call, move the sampler's envelope to `target`
+ * (0..1) over `frames` frames, linearly, and at the fade's end do `then`.  One CMD_SMP_FADE (16), ordered like every sampler message.
+ * A sampler has an envelope E0, E1 (f32 in 0..1), N, k (integers, k < N <= 2^24) and `then`; it is at rest when N == 0, its value at
+ * rest is E1, and a new sampler rests at 1.0f.  The value of the frame j frames ahead of the current position:
+ *   env(j) = N == 0 || k + j >= N ? E1
+ *          : clamp(E0 + (d * ((float)(k + j) / (float)N)), min(E0, E1), max(E0, E1))        d = E1 - E0, computed once
+ * every operation a separately rounded f32 operation, the division IEEE, no FMA; (float)(k + j) and (float)N are exact.  env(0) of a
+ * fresh fade is E0 bit for bit; the value is monotone in j and never leaves [min, max] (E0 + d can round one ulp past E1: the clamp).
+ * The message, at a block's first frame: frames == 0: E1 = target, at rest, then = NONE.  Else E0 = env(0) under the old state (a
+ * retarget in mid-fade continues from where the fade stands), E1 = target, N = frames, k = 0, `then` as given.
+ * Rendering: the envelope moves with the gain smoother — in exactly the blocks in which the reference reaches
+ * gain_smoother.set_and_process (sampler.rs:432: a sample is set and alive, the sampler is playing), whatever happens afterwards.  The
+ * block's gains are g[i] = s[i] * env(i), one f32 product (s[i]: what the smoother gives, a constant or its ramp), the output x * g[i].
+ * The mute test (sampler.rs:437) stays a test on the smoother alone; there is no new silence rule: a voice resting at 0 renders zeros.
+ * Behind the block: k += frames; a fade in flight with k >= N is over (N = k = 0) and, for `then` PAUSE / STOP, the sampler does exactly
+ * what fwgpu_sampler_pause / _stop at the next block's first frame would do — the block the fade ended in was rendered whole, its frames
+ * behind the end at E1 — after which the envelope rests at 1.0f; with then == NONE it rests at E1.
+ * The envelope is a transient: whenever `playing` goes false for any other reason — pause, stop, set_sample with stop_playback, a
+ * one-shot that ends (behind that block's gains) — it goes to rest at 1.0f with then = NONE.  No other message touches it (play,
+ * set_playhead, set_loop_range, set_percent_volume, set_sample without stop): a level that should last belongs in percent_volume.
+ * Without a fade message nothing changes by a bit (s * 1.0f == s).  A fade-in of a stopped voice is three messages for one block:
+ * fade(0, 0), play, fade(1, N).  A voice inside a fade is not steady: its calls run the control kernel, and lazy calls resume behind
+ * the fade.  Resampling sources (FWGPU_RESAMPLER) have no envelope.
+ * FWGPU_ERR_INVALID: `node` is no FWGPU_SAMPLER; `target` is NaN, infinite or outside 0..1 (-0.0 counts as +0.0); frames >
+ * FWGPU_SAMPLER_FADE_FRAMES_MAX; `then` outside 0..2; frames == 0 with then != FWGPU_FADE_NONE (a step has no end to wait for: use
+ * fwgpu_sampler_stop).  FWGPU_ERR_QUEUE_FULL as the other sampler messages.  A fade for a node no plan holds yet waits for the update. */
+enum fwgpu_fade_then { FWGPU_FADE_NONE = 0, FWGPU_FADE_PAUSE = 1, FWGPU_FADE_STOP = 2 };
+#define FWGPU_SAMPLER_FADE_FRAMES_MAX 16777216
+int fwgpu_sampler_fade(fwgpu_ctx* ctx, int64_t node, float target, uint32_t frames, int then, uint32_t at_block);
+
 /* ---- processing */
 /* FirewheelProcessor::process_interleaved (graph/processor.rs:61-165): host buffers, splits `frames`
  * into max_block_frames blocks, returns after the output has landed in `output`. */

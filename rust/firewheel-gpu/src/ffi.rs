@@ -30,6 +30,8 @@ pub const FWGPU_CROSSFADE_FRAMES_MAX: u32 = 16777216;
 pub const FWGPU_CROSSFADE_CH_MAX: u32 = 8;
 /// the longest glide of fwgpu_resampler_glide, in frames
 pub const FWGPU_RESAMPLER_GLIDE_FRAMES_MAX: u32 = 16777216;
+/// the longest fade of fwgpu_sampler_fade, in frames
+pub const FWGPU_SAMPLER_FADE_FRAMES_MAX: u32 = 16777216;
 /// AudioNodeProcessor::process + ProcInfo (core/node.rs:37-53,94-118) as the C callback of a FWGPU_HOST_NODE
 pub type fwgpu_host_process_fn = Option<
     unsafe extern "C" fn(
@@ -120,6 +122,11 @@ pub const FWGPU_ERR_INVALID: c_int = -20;
 pub const FWGPU_ERR_QUEUE_FULL: c_int = -21;
 pub const FWGPU_ERR_DEVICE: c_int = -30;
 
+// enum fwgpu_fade_then
+pub const FWGPU_FADE_NONE: c_int = 0;
+pub const FWGPU_FADE_PAUSE: c_int = 1;
+pub const FWGPU_FADE_STOP: c_int = 2;
+
 #[link(name = "fwgpu")]
 extern "C" {
     pub fn fwgpu_ctx_create(device: c_int, sample_rate: u32, max_block_frames: u32, num_graph_inputs: u32, num_graph_outputs: u32, hip_stream: *mut c_void) -> *mut fwgpu_ctx;
@@ -167,6 +174,7 @@ extern "C" {
     pub fn fwgpu_sampler_stop(ctx: *mut fwgpu_ctx, node: i64, at_block: u32) -> c_int;
     pub fn fwgpu_sampler_set_playhead_secs(ctx: *mut fwgpu_ctx, node: i64, playhead_secs: f64, at_block: u32) -> c_int;
     pub fn fwgpu_sampler_set_loop_range(ctx: *mut fwgpu_ctx, node: i64, mode: c_int, start_secs: f64, end_secs: f64, at_block: u32) -> c_int;
+    pub fn fwgpu_sampler_fade(ctx: *mut fwgpu_ctx, node: i64, target: f32, frames: u32, then: c_int, at_block: u32) -> c_int;
     pub fn fwgpu_process_interleaved(ctx: *mut fwgpu_ctx, input: *const f32, output: *mut f32, num_in_channels: u32, num_out_channels: u32, frames: u64, stream_time_secs: f64, stream_status: u32) -> c_int;
     pub fn fwgpu_process_interleaved_begin(ctx: *mut fwgpu_ctx, input: *const f32, num_in_channels: u32, num_out_channels: u32, frames: u64, stream_time_secs: f64, stream_status: u32) -> i64;
     pub fn fwgpu_process_interleaved_end(ctx: *mut fwgpu_ctx, ticket: i64, output: *mut f32) -> c_int;

@@ -221,6 +221,25 @@ impl GpuSamplerNode {
         self.playing = false;
         Ok(())
     }
+    /// the longest fade one message takes, in frames
+    pub const FADE_FRAMES_MAX: u32 = ffi::FWGPU_SAMPLER_FADE_FRAMES_MAX;
+    /// SPEC gain envelope: from the next block on, move the voice's envelope to `gain` (0..1) over `frames`
+    /// frames, linearly (0: a step), and at the fade's end do `then` (`ffi::FWGPU_FADE_NONE`, `_PAUSE` or `_STOP`) — a declicked
+    /// pause or stop in one message.  The envelope is a transient: every pause and stop puts it back to 1.0, so a level that should
+    /// last belongs in `percent_volume`.  With a `then`, `playing` is false from this call on, as after `pause` / `stop`.
+    pub fn fade_to(&mut self, gain: f32, frames: u32, then: i32) -> Result<(), ()> {
+        self.msg(|c, n| unsafe { ffi::fwgpu_sampler_fade(c, n, gain, frames, then, 0) })?;
+        if then != ffi::FWGPU_FADE_NONE {
+            self.playing = false;
+        }
+        Ok(())
+    }
+    /// a declicked start of a voice that is not playing: the envelope steps to 0, the voice plays, the envelope rises to 1 over `frames`
+    pub fn fade_in(&mut self, frames: u32) -> Result<(), ()> {
+        self.fade_to(0.0, 0, ffi::FWGPU_FADE_NONE)?;
+        self.play()?;
+        self.fade_to(1.0, frames, ffi::FWGPU_FADE_NONE)
+    }
     /// sampler.rs:136-147
     pub fn set_playhead(&mut self, playhead_secs: f64) -> Result<(), ()> {
         self.msg(|c, n| unsafe { ffi::fwgpu_sampler_set_playhead_secs(c, n, playhead_secs, 0) })
