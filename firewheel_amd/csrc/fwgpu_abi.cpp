@@ -972,6 +972,35 @@ int fwgpu_node_set_param(fwgpu_ctx* c, int64_t node, int param, float value, uin
             return fail(c, FWGPU_ERR_INVALID, "node kind has no runtime params");
     }
 }
+// SPEC biquad coefficient sweep: one CMD_BQ_SWEEP — the target's five coefficients packed as param 1 / 2 pack them
+// into a CMD_SET_COEFS, the frames to reach them over in the low bits of d1.  frames == 0 is that message, a step.
+int fwgpu_biquad_sweep(fwgpu_ctx* c, int64_t node, float cutoff_hz, float q, uint32_t frames, uint32_t at_block) {
+    static_assert(FWGPU_BIQUAD_SWEEP_FRAMES_MAX == BQ_SWEEP_FRAMES_MAX, "the header's sweep cap");
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    HostNode* n = c->graph.get(node);
+    if (!n) return fail(c, FWGPU_ERR_INVALID, "unknown node id");
+    if (n->kind != K_BIQUAD) return fail(c, FWGPU_ERR_INVALID, "fwgpu_biquad_sweep: the node is not a BiquadNode");
+    if (cutoff_hz != cutoff_hz || q != q) return fail(c, FWGPU_ERR_INVALID, "fwgpu_biquad_sweep: cutoff_hz or q is NaN");
+    if (frames > FWGPU_BIQUAD_SWEEP_FRAMES_MAX) return fail(c, FWGPU_ERR_INVALID, "fwgpu_biquad_sweep: at most 2^24 frames");
+    n->init.p0 = cutoff_hz;  // (a later set_param of Q alone starts from these)
+    n->init.p1 = q;
+    float co[5];
+    biquad_coefs(n->init.enabled, cutoff_hz, q, c->sample_rate, co);
+    Cmd m;
+    memset(&m, 0, sizeof(m));
+    m.block = at_block;
+    m.type = frames ? CMD_BQ_SWEEP : CMD_SET_COEFS;
+    m.f0 = co[0];
+    memcpy(&m.i0, &co[1], 4);
+    memcpy(&m.i1, &co[2], 4);
+    uint32_t lo, hi;
+    memcpy(&lo, &co[3], 4);
+    memcpy(&hi, &co[4], 4);
+    const uint64_t u = ((uint64_t)hi << 32) | lo, f = (uint64_t)frames;
+    memcpy(&m.d0, &u, 8);
+    memcpy(&m.d1, &f, 8);
+    return push_cmd(c, node, -1, m, false);
+}
 int fwgpu_node_set_params(fwgpu_ctx* c, uint32_t n, const int64_t* nodes, const int* params, const float* values, const uint32_t* at_blocks) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
     if (n && (!nodes || !params || !values || !at_blocks)) return fail(c, FWGPU_ERR_INVALID, "null message list");

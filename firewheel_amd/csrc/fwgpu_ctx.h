@@ -399,6 +399,12 @@ struct fwgpu_ctx : fwgpu::PlanImage {
     uint32_t lazy_epoch = 0;                     // epoch the LazyRecs were made under
     bool lazy_valid = false;                     // nothing but lazy calls has moved the voices since they were made
     bool lazy_this_call = false;
+    // biquad coefficient sweeps (CMD_BQ_SWEEP): the host knows every sweep's length and counts the frames it renders —
+    // frames_done: frames rendered by process calls so far; bq_sweep_until: the frame count behind which no sweep sent so far is in
+    // flight (an upper bound: a message for block b starts no later than b whole blocks into its call); bq_sweep_live: the call being
+    // rendered may meet a sweep — no lazy call, no batch walkers (k_level<1> renders the sweep's blocks), k_chain's sweep instantiation
+    uint64_t frames_done = 0, bq_sweep_until = 0;
+    bool bq_sweep_live = false;
     StatCounter lazy_calls, ctl_calls;           // fused batches rendered without / with a control kernel (fwgpu_lazy_stats)
     int ctl_ahead_mode = 2;          // 1 = every qualifying call (round 3), 2 = only calls with messages / continuing glides (round 4)
     hipStream_t ctl_stream = nullptr;

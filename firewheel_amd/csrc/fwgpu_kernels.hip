@@ -68,7 +68,7 @@ int launch_level(hipStream_t s, const DevView& v, const int* d_level_nodes, int 
     if (pairs >= 262144 && (bpw_wide == 8u || bpw_wide == 16u || bpw_wide == 32u)) bpw = bpw_wide;
     dim3 grid((n_nodes + WPB - 1) / WPB, (K + bpw - 1) / bpw);
     // the level holds a biquad / delay node — in a batch, the ones that are bus effects go to the walkers' kernel
-    const uint32_t walkers = (kinds & LB_WALKERS) && K > 1 ? 1u : 0u;
+    const uint32_t walkers = (kinds & LB_WALKERS) && K > 1 && !v.no_walkers ? 1u : 0u;
     if (kinds & LB_SET0) hipLaunchKernelGGL(k_level<0>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, 0u);
     if (kinds & LB_SET1) hipLaunchKernelGGL(k_level<1>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, walkers);
     if (kinds & LB_SET2) hipLaunchKernelGGL(k_level<2>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, 0u);
@@ -186,10 +186,19 @@ int launch_chain(hipStream_t s, const FusedView& fv, int K, uint32_t cmd_block0,
     if (fv.n_groups <= 0 || K <= 0) return 0;
     // nq: bits 0..1 = tile size / 64 frames, bit 2 = the plan holds a voice with two biquads, bit 3 = ... with a gain stage between two
     // filters or a hard clip (fwgpu_ctx.h chain_nq)
-    const bool bq2 = (nq & 4) != 0, sites = (nq & 8) != 0;
+    // bit 4 = the call may meet a biquad coefficient sweep: the sweep instantiation (64-frame tiles whatever bits 0..1 say, the general
+    // loop only), launched for such calls alone — the steady instantiations are the kernels they were
+    const bool bq2 = (nq & 4) != 0, sites = (nq & 8) != 0, sweep = (nq & 16) != 0;
     nq &= 3;
     const dim3 grid(fv.n_groups, 2), block(CH_THREADS);
 #define FW_CHAIN_LAUNCH(N, B, S) hipLaunchKernelGGL((k_chain<N, B, S>), grid, block, 0, s, fv, K, cmd_block0)
+    if (sweep) {
+#define FW_CHAIN_LAUNCH_SW(B, S) hipLaunchKernelGGL((k_chain<1, B, S, true>), grid, block, 0, s, fv, K, cmd_block0)
+        if (bq2) { if (sites) FW_CHAIN_LAUNCH_SW(true, true); else FW_CHAIN_LAUNCH_SW(true, false); }
+        else { if (sites) FW_CHAIN_LAUNCH_SW(false, true); else FW_CHAIN_LAUNCH_SW(false, false); }
+#undef FW_CHAIN_LAUNCH_SW
+        return (int)hipGetLastError();
+    }
     if (nq == 2) {
         if (bq2) { if (sites) FW_CHAIN_LAUNCH(2, true, true); else FW_CHAIN_LAUNCH(2, true, false); }
         else { if (sites) FW_CHAIN_LAUNCH(2, false, true); else FW_CHAIN_LAUNCH(2, false, false); }

@@ -40,6 +40,9 @@ struct DevView {
     // blocks: two waves never meet in a slot).  meter_K = 0: nothing is recorded (fwgpu_node_process).
     uint64_t meter_blk0 = 0;
     uint32_t meter_K = 0;
+    // 1: this call may meet a biquad coefficient sweep (fwgpu_run.cpp note_bq_sweeps) — launch_level starts no batch walkers: k_level<1>
+    // and k_bus_iir each decide on the device who renders a bus filter, the first moves the sweep's state, and they must decide alike
+    int no_walkers = 0;
 };
 
 // The compact records are tiled: 32 voices x 8 blocks per 4 KiB tile, [voice % 32][block % 8].  A voice's 8 consecutive blocks

@@ -593,7 +593,7 @@ static int activate_nodes(ImageBuild& b) {
         size_t len = 0;
         std::vector<float> head;
         if (n.kind == K_BIQUAD) {
-            len = 5 + 4 * (size_t)nch;
+            len = 5 + 4 * (size_t)nch + BQ_SNAP_LEN;  // (behind the channels' state: a sweep as the chain plan's call found it)
             head.resize(5);
             biquad_coefs(n.init.enabled, n.init.p0, n.init.p1, c->sample_rate, head.data());
         } else if (n.kind == K_DELAY) {

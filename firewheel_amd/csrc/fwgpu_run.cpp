@@ -208,6 +208,9 @@ void retire_cmds_node(fwgpu_ctx* c, int slot) {
         if (m.state == slot) {
             if (m.block == 0) {  // applied by this call
                 note_set_sample(c, m);
+                // (a sweep started by ONE node's process call moves only with that node's calls: the frame count of the process calls
+                //  says nothing about it, so from here on every process call of this ctx counts as one that may meet a sweep)
+                if (m.type == CMD_BQ_SWEEP) c->bq_sweep_until = ~0ull;
                 continue;
             }
             Cmd k = m;
@@ -384,6 +387,16 @@ static int run_host_level(fwgpu_ctx* c, const DevView& v, const std::vector<fwgp
     return 0;
 }
 
+// biquad sweeps: raise bq_sweep_until over the sweep messages on the list (kept ones included: their block counts from this call's
+// first frame now) and say whether this call may meet a sweep
+static void note_bq_sweeps(fwgpu_ctx* c) {
+    for (const Cmd& m : c->cmds)
+        if (m.type == CMD_BQ_SWEEP) {
+            const uint64_t end = c->frames_done + (uint64_t)m.block * c->mbf + (uint64_t)bq_cmd_frames(m.d1);
+            if (end > c->bq_sweep_until) c->bq_sweep_until = end;
+        }
+    c->bq_sweep_live = c->frames_done < c->bq_sweep_until;
+}
 // K blocks of `frames` frames through the level-batched executor (schedule.rs:289-344 as one launch per level for
 // all K blocks: each block has its own pool slice, a stateful node walks its K blocks in order inside one wave)
 int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const float* d_in, int n_in_ch, float* d_out,
@@ -393,6 +406,7 @@ int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const
     DevView v = generic_view(c, frames);
     v.meter_blk0 = c->blocks_done;  // level meters record this batch's blocks
     v.meter_K = (uint32_t)K;
+    v.no_walkers = c->bq_sweep_live ? 1 : 0;
     // which gain-like stateful nodes cannot change during this batch (their blocks then run in parallel): decided once,
     // before the first level
     if (K > 1 && c->d_frozen.ensure_n("d_frozen", (size_t)c->plan.nodes.size()) == hipSuccess &&
@@ -427,7 +441,7 @@ int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const
         LCHK(c, launch_voice_control(c->stream, fv, K, cmd_block));
         timer_end(c, e1);
         timer_begin(c, 0, &e0, &e1);
-        if (c->hybrid_fx) LCHK(c, launch_chain(c->stream, fv, K, cmd_block, c->chain_nq));
+        if (c->hybrid_fx) LCHK(c, launch_chain(c->stream, fv, K, cmd_block, c->chain_nq | (c->bq_sweep_live ? 16 : 0)));
         else LCHK(c, launch_leaf_sum(c->stream, fv, K));
         timer_end(c, e1);
     } else {
@@ -667,7 +681,7 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
     c->abs_blk += (uint64_t)K;
     timer_begin(c, 0, &e0, &e1);
     if (fv.sp_hist_in_render) LCHK(c, launch_sp_hist_copy(c->stream, fv));
-    if (c->fused_fx) LCHK(c, launch_chain(c->stream, fv, K, cmd_block0, c->chain_nq));
+    if (c->fused_fx) LCHK(c, launch_chain(c->stream, fv, K, cmd_block0, c->chain_nq | (c->bq_sweep_live ? 16 : 0)));
     else if (lazy && !c->fused_rs) LCHK(c, launch_leaf_sum_lazy(c->stream, fv, K));
     else LCHK(c, launch_leaf_sum(c->stream, fv, K));
     timer_end(c, e1);
@@ -730,6 +744,7 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
         v.frozen_playhead = nullptr;  // (no sampler can sit in a master chain)
         v.meter_blk0 = c->blocks_done;  // a master meter: one more launch_level below, its K blocks in parallel
         v.meter_K = (uint32_t)K;
+        v.no_walkers = c->bq_sweep_live ? 1 : 0;
         if (K > 1) {
             LCHK(c, launch_frozen_scan(c->stream, v, c->n_tail, cmd_block0, K, c->d_tail_frozen.as<uint8_t>(),
                                        c->d_tail_frozen.as<unsigned long long>()));
@@ -784,6 +799,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     // sent messages to (their glides continue).  A message-free call's control kernel is ~8 us of steady tails; beside the render
     // kernel of the call before it cost that kernel 7-15 us of co-residency and the step a ~10 us cross-stream event.
     drain_ring(c);
+    note_bq_sweeps(c);
     const bool hot = c->ctl_ahead_mode == 1 || !c->cmds.empty() || !c->hot_prev.empty();
     const bool ahead = c->ctl_ahead_on && hot && can_fuse && !c->timing && !stable_out && frames % mbf == 0 && frames / mbf > 1;
     if (!ahead && c->streams_split) {
@@ -796,7 +812,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     c->lazy_this_call = false;
     // (one-block callbacks belong to the realtime kernels, which run their own control)
     if (c->lazy_on && can_fuse && c->lazy_capable && !ahead && !(stable_out && frames == mbf) && !c->rt_use_graph && frames % mbf == 0 && c->cmds.empty() &&
-        c->hot_prev.empty() &&
+        c->hot_prev.empty() && !c->bq_sweep_live &&  // (a plan with a sweep in flight runs its control kernel)
         c->lazy_valid && c->lazy_epoch == c->epoch && c->h_lazy_pub) {
         const unsigned long long seq = __atomic_load_n(&c->h_lazy_pub[1], __ATOMIC_ACQUIRE);
         const unsigned long long horizon = __atomic_load_n(&c->h_lazy_pub[0], __ATOMIC_RELAXED);
@@ -823,7 +839,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     // steady realtime call: no message on the device, one fused batch, the same output block as last time — every
     // kernel argument repeats (block counters and playheads live in device state), so the launch sequence is replayed
     // from a hipGraph instead of being re-issued kernel by kernel
-    if (stable_out && c->rt_use_graph && c->meters.empty() && can_fuse && !c->timing && c->n_cmds_dev == 0 && frames % mbf == 0 &&
+    if (stable_out && c->rt_use_graph && c->meters.empty() && can_fuse && !c->timing && c->n_cmds_dev == 0 && !c->bq_sweep_live && frames % mbf == 0 &&
         frames / mbf <= (c->fused_fx ? std::min<uint32_t>(c->kmax, CH_FAST_KMAX) : c->kmax)) {
         const uint32_t K = (uint32_t)(frames / mbf);
         fwgpu_ctx::RtGraph& g = c->rt_graph;
@@ -851,6 +867,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
         }
         HIPC(c, hipGraphLaunch(g.exec, c->stream));
         c->blocks_done += nblocks;
+        c->frames_done += frames;
         retire_cmds(c, nblocks);
         return 0;
     }
@@ -882,6 +899,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
         c->rt_signalled = true;
     }
     c->ahead_this_call = false;
+    c->frames_done += frames;
     retire_cmds(c, nblocks);
     return 0;
 }

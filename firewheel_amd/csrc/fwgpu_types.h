@@ -127,6 +127,10 @@ struct NodeState {
     uint32_t sample_rate;
     // SPEC nodes with per-channel state: offset/length (floats) of this node's slice of the ext pool
     //   BIQUAD: ext = [b0 b1 b2 a1 a2][x1 x2 y1 y2] x channels      DELAY: ext = ring[channels][D]
+    //   BIQUAD also keeps its coefficient sweep (CMD_BQ_SWEEP) in the two smoothers, which it has no other use for:
+    //        s0.status = N (0: at rest, the coefficients are the ext head's), s1.status = k, s0 / s1 .input .last .a .b .eps = A / T
+    //        (bq_sweep_* below the struct); behind the channels' state the ext slice holds BQ_SNAP_LEN more floats, the sweep as
+    //        it stood at the START of the chain plan's current call (k_voice_control writes it, k_chain's sweep instantiation reads it)
     //   DELAY also uses p0 = feedback, p1 = mix, gain = dry (1-mix), playhead = ring position, loop_end = D
     //   FIR: ext = mirrored history ring[channels][2R]; playhead = ring position, loop_end = R, loop_start = T,
     //        sample = impulse-response sample id
@@ -323,6 +327,91 @@ FW_TYPES_HD inline void smp_env_behind_block(NodeState& s, uint32_t frames) {
 // the sampler's constant gain while its smoother (value c) and its envelope rest: what every frozen / steady / lazy path multiplies by
 FW_TYPES_HD inline float smp_rest_gain(const NodeState& s, float c) { return c * s.gain; }
 
+// K_BIQUAD coefficient sweep (SPEC): ONE statement for the message, the node kernels, the control kernel and k_chain's
+// sweep instantiation.  The five coefficients (b0 b1 b2 a1 a2) move from A to T over N frames, k of them rendered; at rest (N == 0)
+// they are the five at the head of the node's ext slice.  Every operation below is a separately rounded f32 operation
+// (-ffp-contract=off), the division is IEEE, and (float)(k + j), (float)N are exact (both <= 2^24).  In the NodeState: s0.status = N,
+// s1.status = k, A = s0.{input, last, a, b, eps}, T = s1.{input, last, a, b, eps}
+#define BQ_SWEEP_FRAMES_MAX 16777216u
+#define BQ_SNAP_LEN 12  // A[5], T[5], N, k as 32-bit words in the float slots
+struct BqSweep {
+    float A[5], T[5];
+    uint32_t N, k;
+};
+FW_TYPES_HD inline bool bq_sweep_at_rest(const NodeState& s) { return s.s0.status == 0; }
+FW_TYPES_HD inline BqSweep bq_sweep_of(const NodeState& s) {
+    BqSweep w;
+    w.A[0] = s.s0.input, w.A[1] = s.s0.last, w.A[2] = s.s0.a, w.A[3] = s.s0.b, w.A[4] = s.s0.eps;
+    w.T[0] = s.s1.input, w.T[1] = s.s1.last, w.T[2] = s.s1.a, w.T[3] = s.s1.b, w.T[4] = s.s1.eps;
+    w.N = (uint32_t)s.s0.status;
+    w.k = (uint32_t)s.s1.status;
+    return w;
+}
+FW_TYPES_HD inline void bq_sweep_put(NodeState& s, const BqSweep& w) {
+    s.s0.input = w.A[0], s.s0.last = w.A[1], s.s0.a = w.A[2], s.s0.b = w.A[3], s.s0.eps = w.A[4];
+    s.s1.input = w.T[0], s.s1.last = w.T[1], s.s1.a = w.T[2], s.s1.b = w.T[3], s.s1.eps = w.T[4];
+    s.s0.status = (int)w.N;
+    s.s1.status = (int)w.k;
+}
+// the sweep's position j frames ahead, (float)(k + j) / (float)N — one division serves a frame's five coefficients; only for k + j < N
+FW_TYPES_HD inline float bq_sweep_pos(const BqSweep& w, uint32_t j) { return (float)(w.k + j) / (float)w.N; }
+// c_i(j): coefficient i (a compile-time index wherever a kernel calls this) of the frame j frames ahead; `rest` = the ext head's value
+// (the clamp: A + d can round one ulp past T)
+FW_TYPES_HD inline float bq_sweep_coef(const BqSweep& w, int i, uint32_t j, float rest) {
+    if (w.N == 0u) return rest;
+    if (w.k + j >= w.N) return w.T[i];
+    const float a = w.A[i], t = w.T[i];
+    const float d = t - a;
+    const float v = a + (d * bq_sweep_pos(w, j));
+    const float lo = a < t ? a : t, hi = a < t ? t : a;
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+// the message, applied at a block's first frame: N frames from where the coefficients stand (head: the ext slice's five) to T.
+// frames == 0 is a step: the caller writes T to the ext head (CMD_SET_COEFS does the same); so is frames > BQ_SWEEP_FRAMES_MAX, which
+// is NOT SPEC behaviour (fwgpu_biquad_sweep refuses such a call: only a corrupted message gets here).  true: the head must be set to T
+FW_TYPES_HD inline bool bq_sweep_start(BqSweep& w, const float head[5], const float T[5], uint32_t frames) {
+    float from[5];
+    for (int i = 0; i < 5; ++i) from[i] = bq_sweep_coef(w, i, 0u, head[i]);  // a retarget in mid-sweep continues from where the sweep stands
+    for (int i = 0; i < 5; ++i) w.T[i] = T[i];
+    w.k = 0u;
+    if (frames == 0u || frames > BQ_SWEEP_FRAMES_MAX) {
+        w.N = 0u;
+        return true;
+    }
+    for (int i = 0; i < 5; ++i) w.A[i] = from[i];
+    w.N = frames;
+    return false;
+}
+FW_TYPES_HD inline void bq_sweep_stop(BqSweep& w) { w.N = w.k = 0u; }  // CMD_SET_COEFS: the sweep ends, the message's five are the head
+// behind a rendered block of `frames` frames (the values are bq_sweep_coef of the state BEFORE this).  true: the sweep is over — the
+// node is at rest again and the caller writes T to the ext head
+FW_TYPES_HD inline bool bq_sweep_advance(BqSweep& w, uint32_t frames) {
+    if (w.N == 0u) return false;
+    const uint32_t k = w.k + frames;  // (k < N <= 2^24 and a block has fewer than 2^31 frames)
+    if (k < w.N) {
+        w.k = k;
+        return false;
+    }
+    w.N = w.k = 0u;
+    return true;
+}
+// the five coefficients of a CMD_SET_COEFS / CMD_BQ_SWEEP message (f0, i0, i1 = b0, b1, b2; d0 bits = a1 | a2 << 32)
+FW_TYPES_HD inline void bq_cmd_coefs(float f0, int i0, int i1, double d0, float co[5]) {
+    union { double d; uint64_t u; } p;
+    union { uint32_t u; float f; } q;
+    p.d = d0;
+    co[0] = f0;
+    q.u = (uint32_t)i0, co[1] = q.f;
+    q.u = (uint32_t)i1, co[2] = q.f;
+    q.u = (uint32_t)(p.u & 0xffffffffull), co[3] = q.f;
+    q.u = (uint32_t)(p.u >> 32), co[4] = q.f;
+}
+FW_TYPES_HD inline uint32_t bq_cmd_frames(double d1) {  // CMD_BQ_SWEEP: frames in the low bits of d1
+    union { double d; uint64_t u; } p;
+    p.d = d1;
+    return (uint32_t)(p.u & 0xffffffffull);
+}
+
 // K_CROSSFADE (rendered by k_level<0>, no ext slice): the states its case renders.  T never runs behind t0: a message sets t0 = T
 FW_TYPES_HD inline bool xf_state_ok(const NodeState& s, int n_in, int n_out) {
     const auto unit = [](float x) { return x >= 0.0f && x <= 1.0f; };  // (false for a NaN)
@@ -364,6 +453,7 @@ enum : int {
     CMD_SP_ITD = 22,   // spatialiser: i0 / i1 = left / right ear delay in frames
     CMD_XF_TO = 23,    // crossfader: f0 = target position, i0 = frames, i1 = shape; d0 bits = (x1, y1), d1 bits = (x2, y2) as float bits
     CMD_RS_GLIDE = 24,  // resampler: d0 bits = u64 32.32 step to reach, i0 = frames to reach it over (rs_glide_start)
+    CMD_BQ_SWEEP = 25,  // biquad: the target coefficients packed as CMD_SET_COEFS packs them, d1 bits = frames to reach them over (bq_sweep_start)
 };
 struct Cmd {
     int state;
@@ -587,7 +677,7 @@ struct ChainStart {
     float fb, mix, dry; // delay feedback / wet / dry
     float co[5];        // biquad b0 b1 b2 a1 a2
     float co2[5];       // the second biquad's (VoiceDesc::bq2_state)
-    uint32_t pad[2];
+    uint32_t pad[2];    // per biquad: 1 = a sweep was in flight at the call's start — its state is the snapshot behind the node's ext slice
 };
 static_assert(sizeof(ChainStart) == 64, "ChainStart layout");
 

@@ -119,10 +119,97 @@ __device__ __forceinline__ void chain_mix_uniform(const v4f (&x)[32], uint32_t s
     }
 }
 
+// SWEEP instantiation: a biquad of a voice as one role of the workgroup follows it — the coefficient sweep (fwgpu_types.h bq_sweep_*; SPEC,
+// DESIGN.md §6) and, for the frames at rest, the five at the head of the ext slice.  Every role that needs a filter's values keeps a
+// copy and moves it the same way: the state at the call's start (ChainStart::co / co2; a sweep in flight: the snapshot k_voice_control
+// left behind the node's ext slice), the block's messages at its first tile, TT frames on behind every tile.  The control kernel moves
+// the sweep block by block and k_chain tile by tile: c(j) depends on k + j alone, so the values are the same.
+struct ChSweep {
+    BqSweep w;
+    float hd[5];
+};
+__device__ __forceinline__ void chain_sweep_load(ChSweep& z, const FusedView& fv, int bqs, const float (&co)[5], uint32_t live) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) z.hd[j] = co[j], z.w.A[j] = z.w.T[j] = 0.f;
+    z.w.N = z.w.k = 0u;
+    if (bqs >= 0 && live) {
+        const NodeState* bs = &fv.states[bqs];
+        const float* snap = fv.ext + bs->ext_off + bs->ext_len - BQ_SNAP_LEN;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) z.w.A[j] = snap[j], z.w.T[j] = snap[5 + j];
+        z.w.N = __float_as_uint(snap[10]);
+        z.w.k = __float_as_uint(snap[11]);
+    }
+}
+// the messages of (bqs, block), in send order (apply_cmds_from's CMD_SET_COEFS / CMD_BQ_SWEEP, on this copy)
+__device__ __forceinline__ void chain_sweep_block(ChSweep& z, const Cmd* cmds, int n_cmds, int bqs, uint32_t block) {
+    for (int i = chain_cmd_lower_bound(cmds, n_cmds, bqs, block); i < n_cmds; ++i) {
+        const Cmd c = cmds[i];
+        if (c.state != bqs || c.block != block) break;
+        if (c.type == CMD_SET_COEFS) {
+            bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, z.hd);
+            bq_sweep_stop(z.w);
+        } else if (c.type == CMD_BQ_SWEEP) {
+            float T[5];
+            bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, T);
+            if (bq_sweep_start(z.w, z.hd, T, bq_cmd_frames(c.d1))) {
+#pragma unroll
+                for (int j = 0; j < 5; ++j) z.hd[j] = T[j];
+            }
+        }
+    }
+}
+__device__ __forceinline__ void chain_sweep_tile(ChSweep& z, uint32_t tt) {
+    if (bq_sweep_advance(z.w, tt)) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) z.hd[j] = z.w.T[j];
+    }
+}
+// coefficient I of the four frames f0 .. f0 + 3 of the tile under way
+template <int I>
+__device__ __forceinline__ v4f chain_sweep_quad(const ChSweep& z, uint32_t f0) {
+    if (z.w.N == 0u) return splat(z.hd[I]);
+    v4f o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = bq_sweep_coef(z.w, I, f0 + (uint32_t)e, z.hd[I]);
+    return o;
+}
+
+// S2 / S2b of the SWEEP instantiation on one tile row, lane = voice: y[n] = fma(-a1(n), y[n-1], fma(-a2(n), y[n-2], ff[n])), in place.
+// Sixteen frames at a time: their a1 / a2 first — independent of the outputs, so off the recurrence's critical path — then the chain
+template <int TT_>
+__device__ __forceinline__ void chain_sweep_recur(float* row, const ChSweep& z, float& y1, float& y2) {
+#pragma unroll 1
+    for (int c = 0; c < TT_ / 16; ++c) {
+        v4f cur[4], a1q[4], a2q[4], o[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            cur[u] = *(const v4f*)(row + 16 * c + 4 * u);
+            a1q[u] = chain_sweep_quad<3>(z, (uint32_t)(16 * c + 4 * u));
+            a2q[u] = chain_sweep_quad<4>(z, (uint32_t)(16 * c + 4 * u));
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float t = __builtin_fmaf(-a2q[u][e], y2, cur[u][e]);
+                const float y = __builtin_fmaf(-a1q[u][e], y1, t);
+                y2 = y1;
+                y1 = y;
+                o[u][e] = y;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) *(v4f*)(row + 16 * c + 4 * u) = o[u];
+    }
+}
+
 // SITES: some voice of the plan has a gain stage BETWEEN two filters or a hard clip (the instantiation with the five-site stage logic; the
 // other one knows "in front of the first filter" and "behind the last", multiplications only, and keeps its registers: the site tables cost
 // the one-biquad kernel 28 bytes of scratch per lane when they were unconditional)
-template <int NQ, bool BQ2, bool SITES>
+// SWEEP: the instantiation for a call that may meet a biquad coefficient sweep (the host knows: fwgpu_run.cpp note_bq_sweeps) — per-frame
+// coefficients in S1 / S1b (frame-parallel) and in S2 / S2b, the general loop only; the steady instantiations have none of it
+template <int NQ, bool BQ2, bool SITES, bool SWEEP = false>
 __global__ __launch_bounds__(CH_THREADS) void k_chain(FusedView fv, int K, uint32_t cmd_block0) {
     constexpr int TT = 64 * NQ;        // frames per tile
     constexpr int PITCH = TT + 4;      // floats per voice row: + 4 -> the 32 S2 lanes' b128 reads are conflict-free
@@ -237,6 +324,11 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain(FusedView fv, int K, uint3
     float c0 = cs.co2[0], c1 = cs.co2[1], c2 = cs.co2[2], d1 = cs.co2[3], d2 = cs.co2[4];
     float* bq2_st = nullptr;
     float z1 = 0.f, z2 = 0.f;  // its y[n-1], y[n-2]
+    ChSweep sw1, sw2;  // SWEEP: this role's copy of the two filters' coefficients (unused, and gone, in the steady instantiations)
+    if constexpr (SWEEP) {
+        chain_sweep_load(sw1, fv, has_bq ? vd.bq_state : -1, cs.co, cs.pad[0]);
+        chain_sweep_load(sw2, fv, (BQ2 && active && vd.bq2_state >= 0) ? vd.bq2_state : -1, cs.co2, cs.pad[1]);
+    }
     // its x[n-1], x[n-2] at the start of the next tile, per voice row: read by the row's first worker lane (S1b), written by its last
     __shared__ float bq2_u[BQ2 ? 32 : 1][2];
     if (has_bq2 && is_serial2) {
@@ -309,7 +401,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain(FusedView fv, int K, uint3
     __shared__ uint32_t vcls[32];  // per voice: bit c set = some block of the call fetches source class c (SF_*): exactly one for a steady voice
     if (threadIdx.x < 32) vcls[threadIdx.x] = 0u;
     __syncthreads();
-    bool fast_ok = K <= CH_FAST_KMAX && !(fv.dbg & 32);  // FWGPU_CHAIN_SKIP=32: A/B against the general loop
+    bool fast_ok = !SWEEP && K <= CH_FAST_KMAX && !(fv.dbg & 32);  // FWGPU_CHAIN_SKIP=32: A/B against the general loop
     if (fv.n_cmds && active) {
         // messages for THIS leaf's biquads / delays in this call (coefficients, feedback, mix) are replayed block by
         // block by the general loop; messages for other leaves, for master nodes or for later calls do not concern this
@@ -429,7 +521,13 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain(FusedView fv, int K, uint3
             v4f x = *(const v4f*)(r2 + 4 * j);
             pre(x, j);
             const v4f x1v = (v4f){h1, x[0], x[1], x[2]}, x2v = (v4f){h2, h1, x[0], x[1]};
-            const v4f ff = ((x * c0) + (x1v * c1)) + (x2v * c2);
+            v4f ff;
+            if constexpr (SWEEP) {
+                const uint32_t f0 = (uint32_t)(LF * q + 4 * j);
+                ff = ((x * chain_sweep_quad<0>(sw2, f0)) + (x1v * chain_sweep_quad<1>(sw2, f0))) + (x2v * chain_sweep_quad<2>(sw2, f0));
+            } else {
+                ff = ((x * c0) + (x1v * c1)) + (x2v * c2);
+            }
             h1 = x[3];
             h2 = x[2];
             if (on) *(v4f*)(r2 + 4 * j) = ff;
@@ -846,7 +944,9 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain(FusedView fv, int K, uint3
 #pragma unroll
                     for (int j = 0; j < FW_CHAIN_STAGES - 1; ++j) inf0.g[j] = d->g[j + 1][ch];
                 }
-                if (has_bq && fv.n_cmds) {
+                if constexpr (SWEEP) {
+                    if (has_bq && fv.n_cmds) chain_sweep_block(sw1, fv.cmds, fv.n_cmds, vd.bq_state, cmd_block0 + (uint32_t)k1);
+                } else if (has_bq && fv.n_cmds) {
                     const ChainCoefs co = chain_find_coefs(fv.cmds, fv.n_cmds, vd.bq_state, cmd_block0 + (uint32_t)k1);
                     if (co.found) {
                         b0 = co.b0;
@@ -948,11 +1048,18 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain(FusedView fv, int K, uint3
                     for (int j = 0; j < NQ; ++j) {
                         const v4f xc = x[j];
                         const v4f x1v = (v4f){p1, xc[0], xc[1], xc[2]}, x2v = (v4f){p2, p1, xc[0], xc[1]};
-                        const v4f a = ((xc * b0) + (x1v * b1)) + (x2v * b2);  // ((b0*x) + (b1*x1)) + (b2*x2)
+                        v4f a;
+                        if constexpr (SWEEP) {  // (each frame its own b0 b1 b2: the lane's frames are LF * q + 4 * j + e of the tile)
+                            const uint32_t f0 = (uint32_t)(LF * q + 4 * j);
+                            a = ((xc * chain_sweep_quad<0>(sw1, f0)) + (x1v * chain_sweep_quad<1>(sw1, f0))) + (x2v * chain_sweep_quad<2>(sw1, f0));
+                        } else {
+                            a = ((xc * b0) + (x1v * b1)) + (x2v * b2);  // ((b0*x) + (b1*x1)) + (b2*x2)
+                        }
                         p1 = xc[3];
                         p2 = xc[2];
                         *(v4f*)(row + 4 * j) = a;
                     }
+                    if constexpr (SWEEP) chain_sweep_tile(sw1, (uint32_t)TT);
                 } else {
 #pragma unroll
                     for (int j = 0; j < NQ; ++j) *(v4f*)(row + 4 * j) = x[j];
@@ -965,7 +1072,9 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain(FusedView fv, int K, uint3
             }
             if constexpr (BQ2) {  // ================= S1b on tile s-2 (its coefficient messages at block starts, like S1's)
                 const bool real = s >= 2 && s - 2 < n_tiles;
-                if (real && has_bq2 && tf == 0 && fv.n_cmds) {
+                if constexpr (SWEEP) {
+                    if (real && has_bq2 && tf == 0 && fv.n_cmds) chain_sweep_block(sw2, fv.cmds, fv.n_cmds, vd.bq2_state, cmd_block0 + (uint32_t)kf);
+                } else if (real && has_bq2 && tf == 0 && fv.n_cmds) {
                     const ChainCoefs co = chain_find_coefs(fv.cmds, fv.n_cmds, vd.bq2_state, cmd_block0 + (uint32_t)kf);
                     if (co.found) {
                         c0 = co.b0;
@@ -978,6 +1087,9 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain(FusedView fv, int K, uint3
                     //  stale ramp bit would fetch a ramp row behind the table — a memory fault at one block per call, found by the fuzz)
                     if (any_C && real && active) xq = gsite1(SITE_C, xq, inf2, kf, tf, jq);
                 });
+                if constexpr (SWEEP) {
+                    if (real && has_bq2) chain_sweep_tile(sw2, (uint32_t)TT);
+                }
                 if (real && ++tf == tpb) {
                     tf = 0;
                     ++kf;
@@ -1071,14 +1183,21 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain(FusedView fv, int K, uint3
             // ================= S2 on tile s-1: the recursive half of the biquad, lane = voice
             CH_PROF_BEGIN();
             if (any_bq && s >= 1 && s - 1 < n_tiles && !CH_SKIP(1) && !(fv.dbg & 256)) {  // (FWGPU_CHAIN_SKIP=256: timing experiments)
-                if (has_bq && t2 == 0 && fv.n_cmds) {
+                if constexpr (SWEEP) {
+                    if (has_bq && t2 == 0 && fv.n_cmds) chain_sweep_block(sw1, fv.cmds, fv.n_cmds, vd.bq_state, cmd_block0 + (uint32_t)k2);
+                } else if (has_bq && t2 == 0 && fv.n_cmds) {
                     const ChainCoefs co = chain_find_coefs(fv.cmds, fv.n_cmds, vd.bq_state, cmd_block0 + (uint32_t)k2);
                     if (co.found) {
                         a1 = co.a1;
                         a2 = co.a2;
                     }
                 }
-                if (has_bq) {
+                if constexpr (SWEEP) {
+                    if (has_bq) {
+                        chain_sweep_recur<TT>(&tile[CH_BUF(s - 1)][v][0], sw1, y1, y2);
+                        chain_sweep_tile(sw1, (uint32_t)TT);
+                    }
+                } else if (has_bq) {
                     float* row = &tile[CH_BUF(s - 1)][v][0];
                     v4f cur[4], nxt[4];
 #pragma unroll
@@ -1132,14 +1251,21 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain(FusedView fv, int K, uint3
         for (int s = 0; s < n_steps; ++s) {
             CH_PROF_BEGIN();
             if (any_bq2 && s >= 3 && s - 3 < n_tiles && !(fv.dbg & 128)) {  // (FWGPU_CHAIN_SKIP=128: timing experiments, wrong audio)
-                if (has_bq2 && tb == 0 && fv.n_cmds) {
+                if constexpr (SWEEP) {
+                    if (has_bq2 && tb == 0 && fv.n_cmds) chain_sweep_block(sw2, fv.cmds, fv.n_cmds, vd.bq2_state, cmd_block0 + (uint32_t)kb);
+                } else if (has_bq2 && tb == 0 && fv.n_cmds) {
                     const ChainCoefs co = chain_find_coefs(fv.cmds, fv.n_cmds, vd.bq2_state, cmd_block0 + (uint32_t)kb);
                     if (co.found) {
                         d1 = co.a1;
                         d2 = co.a2;
                     }
                 }
-                if (has_bq2) {
+                if constexpr (SWEEP) {
+                    if (has_bq2) {
+                        chain_sweep_recur<TT>(&tile[CH_BUF(s - 3)][v][0], sw2, z1, z2);
+                        chain_sweep_tile(sw2, (uint32_t)TT);
+                    }
+                } else if (has_bq2) {
                     float* row = &tile[CH_BUF(s - 3)][v][0];
                     v4f cur[4], nxt[4];
 #pragma unroll

@@ -182,10 +182,16 @@ __device__ inline int chain_cmd_lower_bound(const Cmd* cmds, int n_cmds, int sta
 // SMP: the sampler's gain envelope (fwgpu_types.h smp_env_*) is compiled in (k_level<2>, k_single_node and the control wave: every
 // other kernel keeps the code it had); smp_env: the node IS a SamplerNode — its envelope takes CMD_SMP_FADE and goes to rest with
 // every pause and stop.  (A resampling source takes pause messages too and keeps a ratio glide in the same fields: never set for one.)
-template <bool XF = false, bool SMP = false>
+// BQ: the biquad's coefficient sweep (fwgpu_types.h bq_sweep_*) is compiled in (k_level<1> and k_single_node: the kernels that render a
+// biquad node; the chain plan's control kernel and k_chain replay a biquad's messages themselves)
+template <bool XF = false, bool SMP = false, bool BQ = false>
 __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t block, const Cmd* cmds, int n_cmds, const SampleDesc* samples,
                                       int lo, float* ext = nullptr, bool ext_write = false, bool smp_env = false) {
     int i = lo;
+    // BQ: the head of the ext slice as the messages of this block have left it so far — every lane follows it in registers (lane 0
+    // alone stores it, and a later message of the same block must not read the slice back)
+    float bq_head[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    bool bq_head_known = false;
     for (; i < n_cmds; ++i) {
         Cmd c = cmds[i];
         if (c.state != state_idx || c.block != block) break;
@@ -203,6 +209,36 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                     unsigned long long u = (unsigned long long)__double_as_longlong(c.d0);
                     co[3] = __int_as_float((int)(u & 0xffffffffull));
                     co[4] = __int_as_float((int)(u >> 32));
+                }
+                if constexpr (BQ) {  // (a sweep in flight ends here: the node is at rest at the message's five)
+                    bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, bq_head);
+                    bq_head_known = true;
+                    s.s0.status = 0;
+                    s.s1.status = 0;
+                }
+                break;
+            case CMD_BQ_SWEEP:  // SPEC coefficient sweep
+                if constexpr (BQ) {
+                    if (ext) {
+                        float* co = ext + s.ext_off;
+                        if (!bq_head_known) {
+#pragma unroll
+                            for (int j = 0; j < 5; ++j) bq_head[j] = co[j];
+                            bq_head_known = true;
+                        }
+                        float T[5];
+                        bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, T);
+                        BqSweep w = bq_sweep_of(s);
+                        if (bq_sweep_start(w, bq_head, T, bq_cmd_frames(c.d1))) {  // (a step: the target is the head)
+#pragma unroll
+                            for (int j = 0; j < 5; ++j) bq_head[j] = T[j];
+                            if (ext_write) {
+#pragma unroll
+                                for (int j = 0; j < 5; ++j) co[j] = T[j];
+                            }
+                        }
+                        bq_sweep_put(s, w);
+                    }
                 }
                 break;
             case CMD_SMP_SET_SAMPLE:  // sampler.rs:333-364
@@ -282,11 +318,11 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
     }
     return i;
 }
-template <bool XF = false, bool SMP = false>
+template <bool XF = false, bool SMP = false, bool BQ = false>
 __device__ inline void apply_cmds(NodeState& s, int state_idx, uint32_t block, const Cmd* cmds, int n_cmds,
                                   const SampleDesc* samples, float* ext = nullptr, bool ext_write = false, bool smp_env = false) {
     if (n_cmds == 0) return;
-    apply_cmds_from<XF, SMP>(s, state_idx, block, cmds, n_cmds, samples, chain_cmd_lower_bound(cmds, n_cmds, state_idx, block), ext, ext_write, smp_env);
+    apply_cmds_from<XF, SMP, BQ>(s, state_idx, block, cmds, n_cmds, samples, chain_cmd_lower_bound(cmds, n_cmds, state_idx, block), ext, ext_write, smp_env);
 }
 
 // The same lower bound by a whole wave (all 64 lanes active, arguments wave-uniform): 64 pivots per round instead of one —

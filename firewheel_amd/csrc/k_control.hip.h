@@ -870,28 +870,68 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
         for (int which = 0; which < 2; ++which) {  // the chain's biquad(s): the record holds the coefficients at the call's start, the ext
             const int bqs = which ? vd.bq2_state : vd.bq_state;  // pool the ones at its end (k_chain replays the messages in between)
             if (bqs < 0) continue;
-            float* co = fv.ext + fv.states[bqs].ext_off;
+            NodeState* bs = &fv.states[bqs];
+            float* co = fv.ext + bs->ext_off;
 #pragma unroll
             for (int j = 0; j < 5; ++j) (which ? cs.co2 : cs.co)[j] = co[j];
-            if (fv.n_cmds) {
-                bool found = false;
-                float nc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-                for (int i = chain_cmd_lower_bound(fv.cmds, fv.n_cmds, bqs, cmd_block0); i < fv.n_cmds; ++i) {
-                    const Cmd c = fv.cmds[i];
-                    if (c.state != bqs || c.block >= cmd_block0 + (uint32_t)K) break;
-                    if (c.type != CMD_SET_COEFS) continue;
-                    nc[0] = c.f0;
-                    nc[1] = __int_as_float(c.i0);
-                    nc[2] = __int_as_float(c.i1);
-                    unsigned long long u = (unsigned long long)__double_as_longlong(c.d0);
-                    nc[3] = __int_as_float((int)(u & 0xffffffffull));
-                    nc[4] = __int_as_float((int)(u >> 32));
-                    found = true;
-                }
-                if (found && w0) {
+            // a coefficient sweep (SPEC): as it stands at the call's start it goes behind the node's ext slice for
+            // k_chain's sweep instantiation (the record's pad word says that it is there), the node state to where the call leaves it
+            const bool live0 = bs->s0.status != 0;
+            cs.pad[which] = live0 ? 1u : 0u;
+            if (!live0 && !fv.n_cmds) continue;
+            BqSweep sw = bq_sweep_of(*bs);
+            if (live0 && w0) {
+                float* snap = co + bs->ext_len - BQ_SNAP_LEN;
 #pragma unroll
-                    for (int j = 0; j < 5; ++j) co[j] = nc[j];
+                for (int j = 0; j < 5; ++j) snap[j] = sw.A[j], snap[5 + j] = sw.T[j];
+                snap[10] = __uint_as_float(sw.N);
+                snap[11] = __uint_as_float(sw.k);
+            }
+            float head[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) head[j] = co[j];
+            bool head_new = false, moved = false;
+            int ci = fv.n_cmds ? chain_cmd_lower_bound(fv.cmds, fv.n_cmds, bqs, cmd_block0) : 0;
+            for (int b = 0; b < K; ++b) {
+                bool more = false;  // a message of this node still to come in this call
+                for (; ci < fv.n_cmds; ++ci) {
+                    const Cmd c = fv.cmds[ci];
+                    if (c.state != bqs || c.block >= cmd_block0 + (uint32_t)K) break;
+                    if (c.block != cmd_block0 + (uint32_t)b) {
+                        more = true;
+                        break;
+                    }
+                    if (c.type == CMD_SET_COEFS) {
+                        bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, head);
+                        bq_sweep_stop(sw);
+                        head_new = moved = true;
+                    } else if (c.type == CMD_BQ_SWEEP) {
+                        float T[5];
+                        bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, T);
+                        if (bq_sweep_start(sw, head, T, bq_cmd_frames(c.d1))) {
+#pragma unroll
+                            for (int j = 0; j < 5; ++j) head[j] = T[j];
+                            head_new = true;
+                        }
+                        moved = true;
+                    }
                 }
+                if (sw.N == 0u && !more) break;
+                if (sw.N != 0u) {
+                    moved = true;
+                    if (bq_sweep_advance(sw, (uint32_t)frames)) {  // over: at rest at its target
+#pragma unroll
+                        for (int j = 0; j < 5; ++j) head[j] = sw.T[j];
+                        head_new = true;
+                    }
+                }
+            }
+            if (w0) {
+                if (head_new) {
+#pragma unroll
+                    for (int j = 0; j < 5; ++j) co[j] = head[j];
+                }
+                if (moved) bq_sweep_put(*bs, sw);
             }
         }
         if (w0) fv.chain_start[vi] = cs;

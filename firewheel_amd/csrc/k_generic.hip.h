@@ -110,6 +110,62 @@ __device__ __forceinline__ void bq_filter_chunk(const BqRows& r, int nch, int la
     bq_wave_sync();
 }
 
+// The same chunk inside a coefficient sweep (SPEC; fwgpu_types.h bq_sweep_*): frame i of the chunk is frame j0 + i of the
+// block and takes the five values c(j0 + i).  Phase A, a frame per lane and step: the frame's position in the sweep (ONE division), its
+// b0 b1 b2 into the feed-forward sum, its a1 a2 kept; once every lane has read the X rows (and lane c has taken channel c's x1, x2 from
+// them) the a1 / a2 of the chunk's frames go to the X rows of channels 0 and 1 — the rows exist whatever nch is — so that the serial
+// phase B reads operands instead of dividing on its critical path.  Same operations per frame, same order as bq_filter_chunk.
+__device__ __forceinline__ void bq_filter_chunk_sweep(const BqRows& r, int nch, int lane, int n, const BqSweep& sw, uint32_t j0, float& x1,
+                                                      float& x2, float& y1, float& y2) {
+    if (lane < nch) {
+        BQ_X(r, lane)[0] = x2;
+        BQ_X(r, lane)[1] = x1;
+    }
+    bq_wave_sync();
+    float a1v[4], a2v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = lane + 64 * q;
+        const uint32_t j = j0 + (uint32_t)i;
+        const float b0 = bq_sweep_coef(sw, 0, j, 0.f), b1 = bq_sweep_coef(sw, 1, j, 0.f), b2 = bq_sweep_coef(sw, 2, j, 0.f);
+        a1v[q] = bq_sweep_coef(sw, 3, j, 0.f);
+        a2v[q] = bq_sweep_coef(sw, 4, j, 0.f);
+        if (i < n)
+            for (int c = 0; c < nch; ++c) {
+                float acc = b0 * BQ_X(r, c)[2 + i];
+                acc = acc + (b1 * BQ_X(r, c)[1 + i]);
+                acc = acc + (b2 * BQ_X(r, c)[i]);
+                BQ_FF(r, c)[i] = acc;
+            }
+    }
+    if (lane < nch) {
+        x1 = BQ_X(r, lane)[1 + n];  // x[n-1]
+        x2 = BQ_X(r, lane)[n];      // x[n-2]
+    }
+    bq_wave_sync();  // every read of the X rows is done
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = lane + 64 * q;
+        if (i < n) {
+            BQ_X(r, 0)[i] = a1v[q];
+            BQ_X(r, 1)[i] = a2v[q];
+        }
+    }
+    bq_wave_sync();
+    if (lane < nch) {
+        const float* f = BQ_FF(r, lane);
+        float* yo = BQ_Y(r, lane);
+        for (int i = 0; i < n; ++i) {
+            float acc = __builtin_fmaf(-BQ_X(r, 1)[i], y2, f[i]);
+            acc = __builtin_fmaf(-BQ_X(r, 0)[i], y1, acc);
+            y2 = y1;
+            y1 = acc;
+            yo[i] = acc;
+        }
+    }
+    bq_wave_sync();
+}
+
 
 // core/util.rs:165-175
 __device__ __forceinline__ uint64_t clear_all_outputs(const WaveIO& io, int first, int n_out) {
@@ -269,7 +325,7 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
     const bool stateful = kind_is_stateful(nd.kind);
     if (stateful) {
         s = v.states[nd.state];
-        apply_cmds<SET == 0 || SET == 3, SET == 2 || SET == 3>(s, nd.state, cmd_block, v.cmds, v.n_cmds, v.samples, v.ext, lane == 0, nd.kind == K_SAMPLER);
+        apply_cmds<SET == 0 || SET == 3, SET == 2 || SET == 3, SET == 1 || SET == 3>(s, nd.state, cmd_block, v.cmds, v.n_cmds, v.samples, v.ext, lane == 0, nd.kind == K_SAMPLER);
         if (nd.kind == K_BIQUAD && v.n_cmds) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // lane 0's coefficient stores
     }
 
@@ -580,7 +636,68 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
             // Serial in time: lane c runs channel c (the generic executor's coverage path).
             float* ext = v.ext + s.ext_off;
             const int nch = nd.n_in < nd.n_out ? nd.n_in : nd.n_out;
-            if (nch <= BQ_LDS_CH) {
+            if (!bq_sweep_at_rest(s)) {
+                // A coefficient sweep in flight (SPEC): every frame has its own five values, c(j) of the sweep as the block
+                // finds it.  Up to 4 channels through the LDS rows as below, more than that a lane per channel with the values worked
+                // out in its loop; behind the block the sweep moves on, and one that is over leaves its target at the head of the slice.
+                BqSweep sw = bq_sweep_of(s);
+                if (nch <= BQ_LDS_CH) {
+                    const BqRows rows = bq_rows();
+                    float x1 = 0.f, x2 = 0.f, y1 = 0.f, y2 = 0.f;
+                    float* st = ext + 5 + 4 * (lane < nch ? lane : 0);
+                    if (lane < nch) x1 = st[0], x2 = st[1], y1 = st[2], y2 = st[3];
+                    for (int base = 0; base < frames; base += 256) {
+                        const int n = frames - base < 256 ? frames - base : 256;
+                        for (int c = 0; c < nch; ++c) {
+                            const float* in = io.in(c) + base;
+                            for (int f = lane; f < n; f += WAVE) BQ_X(rows, c)[2 + f] = in[f];
+                        }
+                        bq_filter_chunk_sweep(rows, nch, lane, n, sw, (uint32_t)base, x1, x2, y1, y2);
+                        for (int c = 0; c < nch; ++c) {
+                            float* out = io.out(c) + base;
+                            for (int f = lane; f < n; f += WAVE) out[f] = BQ_Y(rows, c)[f];
+                        }
+                        bq_wave_sync();  // (the next 256 frames overwrite the rows)
+                    }
+                    if (lane < nch) {
+                        st[0] = x1;
+                        st[1] = x2;
+                        st[2] = y1;
+                        st[3] = y2;
+                    }
+                } else if (lane < nch) {
+                    float* st = ext + 5 + 4 * lane;
+                    float x1 = st[0], x2 = st[1], y1 = st[2], y2 = st[3];
+                    const float* in = io.in(lane);
+                    float* out = io.out(lane);
+                    for (int i = 0; i < frames; ++i) {
+                        const uint32_t j = (uint32_t)i;
+                        float x = in[i];
+                        float acc = bq_sweep_coef(sw, 0, j, 0.f) * x;
+                        acc = acc + (bq_sweep_coef(sw, 1, j, 0.f) * x1);
+                        acc = acc + (bq_sweep_coef(sw, 2, j, 0.f) * x2);
+                        acc = __builtin_fmaf(-bq_sweep_coef(sw, 4, j, 0.f), y2, acc);
+                        acc = __builtin_fmaf(-bq_sweep_coef(sw, 3, j, 0.f), y1, acc);
+                        x2 = x1;
+                        x1 = x;
+                        y2 = y1;
+                        y1 = acc;
+                        out[i] = acc;
+                    }
+                    st[0] = x1;
+                    st[1] = x2;
+                    st[2] = y1;
+                    st[3] = y2;
+                }
+                if (bq_sweep_advance(sw, (uint32_t)frames)) {
+                    if (lane == 0) {
+#pragma unroll
+                        for (int j = 0; j < 5; ++j) ext[j] = sw.T[j];
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // lane 0's coefficient stores: the next block's lanes read them
+                }
+                bq_sweep_put(s, sw);
+            } else if (nch <= BQ_LDS_CH) {
                 // Up to 4 channels (a bus effect, a master filter): the block goes through LDS 256 frames at a time — the wave
                 // loads it coalesced, lane c runs channel c's recurrence on LDS operands, the wave stores the result.  With
                 // the samples read from global memory inside the loop every frame paid a memory round trip behind the
@@ -939,6 +1056,10 @@ __device__ __forceinline__ void frozen_finish(const DevView& v, int node_idx, ui
 __device__ __forceinline__ bool biquad_walk_ok(const DevView& v, const NodeDesc& nd, uint32_t cmd_block0, uint32_t K) {
     const int nch = nd.n_in < nd.n_out ? nd.n_in : nd.n_out;
     if (nd.kind != K_BIQUAD || nch < 1 || nch > 2 || K < 2 || (v.frames & 255)) return false;  // mono / stereo, whole 256-frame chunks
+    // a coefficient sweep in flight goes block by block through node_process_wave (a sweep MESSAGE in the batch is a message: below).
+    // (k_level<1> and k_bus_iir must decide alike, and the first changes this state: the host launches no walkers while a sweep may be
+    //  in flight — fwgpu_run.cpp bq_sweep_live — so this line guards, it does not dispatch)
+    if (!bq_sweep_at_rest(v.states[nd.state])) return false;
     if (v.n_cmds) {
         const int c = chain_cmd_lower_bound(v.cmds, v.n_cmds, nd.state, cmd_block0);
         if (c < v.n_cmds && v.cmds[c].state == nd.state && v.cmds[c].block < cmd_block0 + K) return false;

@@ -244,6 +244,21 @@ class BiquadNode(_Node):  # SPEC node: RBJ biquad, Direct Form I in f32; coeffic
         self.q = q
         self._set(2, q, at_block)
 
+    SWEEP_FRAMES_MAX = 1 << 24
+
+    def sweep_to(self, cutoff_hz, frames, q=None, at_block=0):
+        """from block `at_block` of the next process call on, move the filter to (`cutoff_hz`, `q`; q None: the Q it has) over
+        `frames` frames — the five coefficients travel linearly and per frame (0: a step, as set_cutoff_hz) — ONE message for an
+        occlusion or under-water muffle instead of a set_cutoff_hz per block (fwgpu_biquad_sweep).  A second sweep starts from where
+        the first stands.  `self.cutoff_hz` and `self.q` hold the TARGET from this call on."""
+        q = self.q if q is None else q
+        self.cx._check(self.cx.L.fwgpu_biquad_sweep(self.cx.c, self.id, cutoff_hz, q, frames, at_block))
+        self.cutoff_hz, self.q = cutoff_hz, q
+
+    def sweep_to_secs(self, cutoff_hz, secs, q=None, at_block=0):
+        """sweep_to with the length in seconds of the context's sample rate"""
+        self.sweep_to(cutoff_hz, max(0, int(round(secs * self.cx.sample_rate))), q, at_block)
+
 
 class DelayNode(_Node):  # SPEC node: integer-sample delay line (fixed length) with feedback and dry/wet mix
     KIND = 11

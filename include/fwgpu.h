@@ -614,6 +614,24 @@ int fwgpu_crossfade_to(fwgpu_ctx* ctx, int64_t node, float position, uint32_t fr
 #define FWGPU_RESAMPLER_GLIDE_FRAMES_MAX 16777216
 int fwgpu_resampler_glide(fwgpu_ctx* ctx, int64_t node, float ratio, uint32_t frames, uint32_t at_block);
 
+/* ---- biquad: a coefficient sweep (a moving cutoff) in one message (SPEC).
+ * fwgpu_biquad_sweep: from the first frame of block `at_block` of the next process call, move the node's five coefficients
+ * (b0, b1, b2, a1, a2) to the ones params 1 and 2 would set for `cutoff_hz` and `q` — T, computed in f64 with the same clamps and
+ * rounded to f32 — over `frames` frames, linearly and per frame.  With A the five values the filter has reached at that block's first
+ * frame, d_i = T_i - A_i (one f32 subtraction), N = frames and k the frames of the sweep rendered so far, the frame j frames ahead uses
+ *   c_i(j) = k + j >= N ? T_i : clamp(A_i + (d_i * ((float)(k + j) / (float)N)), min(A_i, T_i), max(A_i, T_i))
+ * every operation a separately rounded f32 operation, the division IEEE, no FMA; the filter itself is what it is at rest, frame by
+ * frame with that frame's values: ff = ((b0*x) + (b1*x1)) + (b2*x2); y = fma(-a1, y1, fma(-a2, y2, ff)).  Behind a rendered block
+ * k += the block's frames; once k >= N the node is at rest at T.  The stable (a1, a2) form a convex set, so every frame of a sweep
+ * between two stable filters is a stable filter; a long sweep that must follow log-frequency is several segments.
+ * frames == 0 is exactly params 1 + 2 (a step).  A second sweep starts from where the first stands; params 1 / 2 during a sweep end it
+ * and set the coefficients; several messages for one block apply in send order.  A filter inside a sweep is not steady: its calls run
+ * the control kernel, and lazy calls resume with the first call behind the sweep.  The node's cutoff and Q as params 1 / 2 see them are
+ * the sweep's targets from this call on.  FWGPU_ERR_INVALID for a node of another kind, a NaN cutoff_hz or q, or frames >
+ * FWGPU_BIQUAD_SWEEP_FRAMES_MAX. */
+#define FWGPU_BIQUAD_SWEEP_FRAMES_MAX 16777216
+int fwgpu_biquad_sweep(fwgpu_ctx* ctx, int64_t node, float cutoff_hz, float q, uint32_t frames, uint32_t at_block);
+
 /* ProcInfo::stream_time_secs / stream_status (core/node.rs:111-132) of the most recent fwgpu_process_interleaved call —
  * what a custom node run through fwgpu_node_process inside that call would be handed — and how often the backend has
  * reported StreamStatus::OUTPUT_UNDERFLOW (bit 1) / INPUT_OVERFLOW (bit 0) so far.  Any pointer may be NULL. */

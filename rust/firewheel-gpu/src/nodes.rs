@@ -408,6 +408,24 @@ param_node!(GpuStereoWidthNode, "stereo_width", ffi::FWGPU_STEREO_WIDTH, io(2, 2
 param_node!(GpuBiquadNode, "biquad", ffi::FWGPU_BIQUAD, io(1, 64, 1, 64, false),
             "RBJ biquad (filter_type 0 = low-pass, 1 = high-pass, 2 = band-pass), Direct Form I in f32",
             [filter_type, cutoff_hz, q], {set_cutoff_hz => (1, cutoff_hz), set_q => (2, q)});
+impl GpuBiquadNode {
+    /// the longest sweep one message takes, in frames
+    pub const SWEEP_FRAMES_MAX: u32 = ffi::FWGPU_BIQUAD_SWEEP_FRAMES_MAX;
+    /// From the next block on, move the filter to (`cutoff_hz`, `q`) over `frames` frames: the five coefficients travel linearly and
+    /// per frame (0: a step, as `set_cutoff_hz`) — one message for an occlusion or under-water muffle.  A second sweep starts from
+    /// where the first stands.  Before activation only the target is kept: the node then starts there.  The node's recorded cutoff
+    /// and Q are the TARGET from this call on, also while the sweep is still in flight.
+    pub fn sweep_to(&mut self, cutoff_hz: f32, q: f32, frames: u32) -> Result<(), GpuError> {
+        if let Some(node) = self.b.node {
+            let _g = self.b.cx.control();
+            let rc = unsafe { ffi::fwgpu_biquad_sweep(self.b.cx.as_ptr(), node, cutoff_hz, q, frames, 0) };
+            self.b.cx.check(rc as i64)?;
+        }
+        self.cutoff_hz = cutoff_hz;
+        self.q = q;
+        Ok(())
+    }
+}
 param_node!(GpuDelayNode, "delay", ffi::FWGPU_DELAY, io(1, 64, 1, 64, false),
             "integer-sample delay line with feedback and dry/wet mix; the delay time is fixed at construction",
             [delay_secs, feedback, mix], {set_feedback => (1, feedback), set_mix => (2, mix)});
