@@ -95,6 +95,11 @@ SIGNATURES = {
     "fwgpu_set_force_generic": (ci, [vp, ci]),
     "fwgpu_sample_create": (ci, [vp, ci, u32, u64, vp]),
     "fwgpu_sample_create_device": (ci, [vp, ci, u32, u64, vp]),
+    "fwgpu_sample_create_stream": (ci, [vp, ci, u32, u64]),
+    "fwgpu_sample_stream_write": (ci, [vp, ci, vp, u64]),
+    "fwgpu_sample_stream_write_device": (ci, [vp, ci, vp, u64]),
+    "fwgpu_sample_stream_end": (ci, [vp, ci]),
+    "fwgpu_sample_stream_status": (ci, [vp, ci, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(ci)]),
     "fwgpu_sample_destroy": (ci, [vp, ci]),
     "fwgpu_poll_returned_samples": (ci, [vp, C.POINTER(i64), C.POINTER(ci), ci]),
     "fwgpu_sample_retired": (ci, [vp, ci]),

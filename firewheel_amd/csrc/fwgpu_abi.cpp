@@ -74,6 +74,112 @@ void collect_returns(fwgpu_ctx* c) {
     }
 }
 
+// ---- SPEC streaming sources, control side
+size_t stream_elem_size(int fmt) { return (fmt == FMT_I_F32 || fmt == FMT_P_F32) ? 4 : 2; }
+StreamRec* stream_of(fwgpu_ctx* c, int sample) {
+    if (sample < 0 || sample >= (int)c->samples.size() || !c->samples[sample].alive) return nullptr;
+    const int si = c->samples[sample].stream;
+    return si >= 0 && si < (int)c->streams.size() ? &c->streams[si] : nullptr;
+}
+// the audio side stops publishing the stream's sampler (under the gate: the audio side reads the table inside its calls)
+void stream_pub_drop(fwgpu_ctx* c, StreamRec& r) {
+    if (r.pub < 0) return;
+    ControlGate gate(c);
+    c->stream_pub_slot[r.pub] = -1;
+    c->stream_pub_n--;
+    r.pub = -1;
+}
+// the sampler let go of the stream (another sample, the node removed, the stream destroyed): finished for good
+void stream_detach(fwgpu_ctx* c, StreamRec& r) {
+    stream_pub_drop(c, r);
+    r.detached = true;
+    r.finished = true;
+}
+// C, U and `finished` of every bound stream as of the last process call KNOWN to be complete: the newest bank whose event has
+// completed and whose ticket did not move while it was read.  Never blocks.
+void stream_refresh(fwgpu_ctx* c) {
+    if (!c->h_stream_pub || c->stream_pub_n == 0) return;
+    const uint64_t t0 = c->stream_pub_ticket[0].load(std::memory_order_acquire), t1 = c->stream_pub_ticket[1].load(std::memory_order_acquire);
+    const int order[2] = {t0 >= t1 ? 0 : 1, t0 >= t1 ? 1 : 0};
+    for (int k = 0; k < 2; ++k) {
+        const int bank = order[k];
+        const uint64_t t = c->stream_pub_ticket[bank].load(std::memory_order_acquire);
+        if (!t) continue;
+        if (hipEventQuery(c->ev_stream_pub[bank]) != hipSuccess) {
+            (void)hipGetLastError();
+            continue;
+        }
+        bool torn = false;
+        for (StreamRec& r : c->streams) {
+            if (r.pub < 0) continue;
+            NodeState st;
+            memcpy(&st, c->h_stream_pub + (size_t)bank * fwgpu_ctx::STREAM_PUB_MAX + r.pub, sizeof(st));
+            if (c->stream_pub_ticket[bank].load(std::memory_order_acquire) != t) {
+                torn = true;
+                break;
+            }
+            if (st.sample != r.sample || !smp_stream_on(st)) continue;  // (the bind message has not been applied yet)
+            const SmpStream ss = smp_stream_of(st);
+            if (ss.C >= r.consumed) {  // (counts only move forward: an older bank never overrides a newer one)
+                r.consumed = ss.C;
+                r.starved = ss.U;
+                if (ss.flags & SMP_STREAM_FINISHED) r.finished = true;
+            }
+        }
+        if (!torn) break;
+    }
+    // a finished stream has nothing left to publish: the resident realtime kernel may come back
+    for (StreamRec& r : c->streams)
+        if (r.pub >= 0 && r.finished) stream_pub_drop(c, r);
+}
+uint64_t stream_free(const StreamRec& r) { return r.ring - (r.written - r.consumed); }
+// `frames` frames at ring position written % R, split at the ring's end and, planar, per channel: src laid out as a sample of
+// `src_frames` frames (null: zero padding — bytes of 0, or 0x8000 elements for the unsigned formats).  Plain copies on the control side's stream,
+// waited for on that stream alone
+int stream_put(fwgpu_ctx* c, const StreamRec& r, const void* src, uint64_t frames, uint64_t src_frames, bool on_device) {
+    const SampleDesc& d = c->samples[r.sample].desc;
+    const size_t es = stream_elem_size(d.format), ch = (size_t)d.channels;
+    const bool planar = d.format >= FMT_P_I16;
+    const uint64_t pos = r.written % r.ring;
+    const uint64_t n0 = std::min<uint64_t>(frames, r.ring - pos), n1 = frames - n0;
+    std::vector<uint16_t> pad;
+    if (!src && (d.format == FMT_I_U16 || d.format == FMT_P_U16)) {
+        pad.assign((size_t)frames * ch, (uint16_t)0x8000);
+        src = pad.data();
+        on_device = false;
+    }
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    auto piece = [&](uint64_t dst_elem, uint64_t src_elem, uint64_t elems) -> hipError_t {
+        if (!elems) return hipSuccess;
+        char* dst = (char*)d.data + dst_elem * es;
+        if (!src) return hipMemsetAsync(dst, 0, elems * es, c->stream_wr);
+        return hipMemcpyAsync(dst, (const char*)src + src_elem * es, elems * es, kind, c->stream_wr);
+    };
+    hipError_t e = hipSuccess;
+    if (planar) {
+        for (size_t k = 0; k < ch && e == hipSuccess; ++k) {
+            e = piece(k * r.ring + pos, k * src_frames, n0);
+            if (e == hipSuccess) e = piece(k * r.ring, k * src_frames + n0, n1);
+        }
+    } else {
+        e = piece(pos * ch, 0, n0 * ch);
+        if (e == hipSuccess) e = piece(0, n0 * ch, n1 * ch);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream_wr);  // the data has landed before the sampler is told of it
+    return e == hipSuccess ? 0 : hipfail(c, e, "stream write");
+}
+// one CMD_SMP_STREAM to the bound sampler, at_block 0: the new W and, with has_end, E
+int stream_tell(fwgpu_ctx* c, StreamRec& r, uint64_t W, bool has_end, uint64_t E) {
+    if (r.node < 0 || r.detached) return 0;
+    Cmd m;
+    memset(&m, 0, sizeof(m));
+    m.type = CMD_SMP_STREAM;
+    m.i0 = has_end ? 1 : 0;
+    m.d0 = fw_double_of(W);
+    m.d1 = fw_double_of(E);
+    return push_cmd(c, r.node, K_SAMPLER, m, true);
+}
+
 }  // namespace
 
 // ================================================================= C ABI
@@ -340,6 +446,11 @@ void fwgpu_ctx_destroy(fwgpu_ctx* c) {
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_jobs) (void)hipHostFree(c->h_jobs);
     if (c->ev_build) (void)hipEventDestroy(c->ev_build);
+    if (c->stream_wr) (void)hipStreamDestroy(c->stream_wr);
+    if (c->h_stream_pub) (void)hipHostFree(c->h_stream_pub);
+    if (c->h_stream_jobs) (void)hipHostFree(c->h_stream_jobs);
+    for (hipEvent_t e : c->ev_stream_pub)
+        if (e) (void)hipEventDestroy(e);
     DevBuf* bufs[] = {&c->d_states, &c->d_ext, &c->d_samples, &c->d_rt_sync, &c->d_lazy_horizon, &c->d_cmds, &c->d_in_stage, &c->d_out_stage, &c->d_scratch_pool,
                       &c->d_scratch_flags, &c->d_scratch_tab, &c->d_mask, &c->d_trace, &c->d_rs_table};
     for (DevBuf* b : bufs) b->release();
@@ -376,6 +487,8 @@ int64_t fwgpu_add_node(fwgpu_ctx* c, int kind, uint32_t n_in, uint32_t n_out, co
         if (ir < 0 || ir >= (int)c->samples.size() || !c->samples[ir].alive || c->samples[ir].desc.frames == 0)
             return fail(c, FWGPU_ERR_INVALID, kind == K_FIR ? "FIR node: params[0] must be the id of a non-empty impulse-response sample"
                                                             : "Resampler node: params[0] must be the id of a non-empty source sample");
+        if (c->samples[ir].stream >= 0)
+            return fail(c, FWGPU_ERR_INVALID, "a stream cannot be an impulse response or a resampler's source");
         if (kind == K_FIR && c->samples[ir].desc.frames > (1u << 24))
             return fail(c, FWGPU_ERR_INVALID, "FIR node: at most 2^24 taps");
         if (kind == K_RESAMPLER && c->samples[ir].desc.frames >= (1ull << 31))
@@ -408,7 +521,10 @@ int fwgpu_remove_node(fwgpu_ctx* c, int64_t node) {
             fr.ir = hn->kind == K_FIR ? hn->init.sample : -1;
         }
     if (HostNode* hn = c->graph.get(node)) fr.kind = hn->kind;
+    int held_stream = -1;  // (SPEC streaming source: removing the sampler leaves its stream finished)
+    if (HostNode* hn = c->graph.get(node)) held_stream = hn->stream;
     int rc = c->graph.remove_node(node);
+    if (rc == 0 && held_stream >= 0 && held_stream < (int)c->streams.size()) stream_detach(c, c->streams[held_stream]);
     if (rc) return fail(c, rc, "remove_node: unknown node or graph in/out node");
     if (fr.any) c->limbo.push_back({c->build_gen + 1, 1, fr.off, (uint32_t)(((size_t)fr.len + 63) / 64 * 64)});
     if (fr.ir >= 0) {  // the f32 copy of an impulse response goes with its last FIR user
@@ -745,6 +861,110 @@ int fwgpu_sample_create_device(fwgpu_ctx* c, int format, uint32_t channels, uint
     NEED_CTX(c, FWGPU_ERR_INVALID);
     return sample_add(c, format, channels, frames, device_data, true);
 }
+// ---- SPEC streaming sources
+int fwgpu_sample_create_stream(fwgpu_ctx* c, int format, uint32_t channels, uint64_t ring_frames) {
+    static_assert(FWGPU_STREAM_RING_FRAMES_MAX == SMP_STREAM_RING_MAX && FWGPU_STREAM_RING_MIN_BLOCKS == SMP_STREAM_RING_MIN_BLOCKS, "the header's ring bounds");
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    if (format < 0 || format > FMT_P_F32 || channels == 0 || channels > 64) return fail(c, FWGPU_ERR_INVALID, "bad sample format/channels");
+    if (ring_frames < (uint64_t)SMP_STREAM_RING_MIN_BLOCKS * c->mbf || ring_frames > SMP_STREAM_RING_MAX)
+        return fail(c, FWGPU_ERR_INVALID, "fwgpu_sample_create_stream: ring_frames must lie in [4 * max_block_frames, 2^30]");
+    use_device(c);
+    if (!c->h_stream_pub) {  // the first stream of the ctx: the copy stream, the pinned banks and their events
+        RtHold hold(c);  // (pinned allocations wait for the device)
+        for (int& sl : c->stream_pub_slot) sl = -1;
+        const size_t n = 2 * (size_t)fwgpu_ctx::STREAM_PUB_MAX;
+        HIPC(c, hipStreamCreateWithFlags(&c->stream_wr, hipStreamNonBlocking));
+        HIPC(c, hipHostMalloc((void**)&c->h_stream_jobs, n * sizeof(BuildJob), hipHostMallocDefault));
+        HIPC(c, hipEventCreateWithFlags(&c->ev_stream_pub[0], hipEventDisableTiming));
+        HIPC(c, hipEventCreateWithFlags(&c->ev_stream_pub[1], hipEventDisableTiming));
+        NodeState* pub = nullptr;
+        HIPC(c, hipHostMalloc((void**)&pub, n * sizeof(NodeState), hipHostMallocDefault));
+        memset(pub, 0, n * sizeof(NodeState));
+        ControlGate gate(c);
+        c->h_stream_pub = pub;
+    }
+    const size_t bytes = (size_t)ring_frames * channels * stream_elem_size(format);
+    void* d = nullptr;
+    {
+        RtHold hold(c);
+        HIPC(c, hipMalloc(&d, bytes + 256));  // slack: a wave's last dwordx4 may overhang the data
+        const hipError_t e = hipMemset(d, 0, bytes + 256);  // the ring starts zeroed
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return hipfail(c, e, "stream ring");
+        }
+    }
+    const int id = sample_add(c, format, channels, ring_frames, d, true);
+    if (id < 0) {
+        (void)hipFree(d);
+        return id;
+    }
+    c->samples[id].owned = true;  // (the ring is the library's: fwgpu_sample_destroy frees it)
+    StreamRec r;
+    r.sample = id;
+    r.ring = ring_frames;
+    c->streams.push_back(r);
+    c->samples[id].stream = (int)c->streams.size() - 1;
+    return id;
+}
+static int stream_write_impl(fwgpu_ctx* c, int sample, const void* data, uint64_t frames, bool on_device) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    StreamRec* r = stream_of(c, sample);
+    if (!r) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sample_stream_write: not a stream");
+    if (r->ended || r->detached) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sample_stream_write: the stream has ended");
+    if (frames && !data) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sample_stream_write: data is null");
+    use_device(c);
+    stream_refresh(c);
+    const uint64_t n = std::min<uint64_t>(frames, stream_free(*r));
+    if (n == 0) return 0;
+    // (the source is laid out as a sample of `frames` frames: a planar channel starts c * frames elements in, whatever is accepted)
+    int rc = stream_put(c, *r, data, n, frames, on_device);
+    if (rc) return rc;
+    rc = stream_tell(c, *r, r->written + n, false, 0);  // a full message ring: `written` does not move, the same call can be repeated
+    if (rc) return rc;
+    r->written += n;
+    return (int)n;
+}
+int fwgpu_sample_stream_write(fwgpu_ctx* c, int sample, const void* data, uint64_t frames) { return stream_write_impl(c, sample, data, frames, false); }
+int fwgpu_sample_stream_write_device(fwgpu_ctx* c, int sample, const void* device_data, uint64_t frames) {
+    return stream_write_impl(c, sample, device_data, frames, true);
+}
+int fwgpu_sample_stream_end(fwgpu_ctx* c, int sample) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    StreamRec* r = stream_of(c, sample);
+    if (!r) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sample_stream_end: not a stream");
+    if (r->ended && !r->detached && r->node >= 0 && !r->end_told) {
+        // ended before it was bound, and the binding found no room for the message that carries E: the same call delivers it
+        const int rc = stream_tell(c, *r, r->written, true, r->end_at);
+        if (rc == 0) r->end_told = true;
+        return rc;
+    }
+    if (r->ended || r->detached) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sample_stream_end: the stream has ended");
+    use_device(c);
+    stream_refresh(c);
+    if (stream_free(*r) < c->mbf) return fail(c, FWGPU_ERR_QUEUE_FULL, "fwgpu_sample_stream_end: no room yet for the padding behind the data");
+    int rc = stream_put(c, *r, nullptr, c->mbf, c->mbf, false);
+    if (rc) return rc;
+    rc = stream_tell(c, *r, r->written + c->mbf, true, r->written);
+    if (rc) return rc;
+    r->end_at = r->written;
+    r->written += c->mbf;
+    r->ended = true;
+    r->end_told = r->node >= 0 && !r->detached;  // (not bound yet: the end travels behind the binding)
+    return 0;
+}
+int fwgpu_sample_stream_status(fwgpu_ctx* c, int sample, uint64_t* written, uint64_t* consumed, uint64_t* starved_blocks, int* finished) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    StreamRec* r = stream_of(c, sample);
+    if (!r) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sample_stream_status: not a stream");
+    use_device(c);
+    stream_refresh(c);
+    if (written) *written = r->ended ? r->end_at : r->written;
+    if (consumed) *consumed = r->consumed;
+    if (starved_blocks) *starved_blocks = r->starved;
+    if (finished) *finished = r->finished ? 1 : 0;
+    return 0;
+}
 int fwgpu_sample_destroy(fwgpu_ctx* c, int sample) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
     if (sample < 0 || sample >= (int)c->samples.size() || !c->samples[sample].alive)
@@ -761,6 +981,19 @@ int fwgpu_sample_destroy(fwgpu_ctx* c, int sample) {
     (void)hipStreamSynchronize(c->stream);
     if (c->ctl_stream) (void)hipStreamSynchronize(c->ctl_stream);
     SampleRec& r = c->samples[sample];
+    if (r.stream >= 0) {  // (the gate is held: the table entry is cleared by hand, stream_pub_drop would take it again)
+        StreamRec& sr = c->streams[r.stream];
+        if (sr.pub >= 0) {
+            c->stream_pub_slot[sr.pub] = -1;
+            c->stream_pub_n--;
+            sr.pub = -1;
+        }
+        sr.detached = sr.finished = true;
+        // (the sampler that held it holds a stream no longer: seek and loop messages are accepted on it again)
+        if (HostNode* hn = sr.node >= 0 ? c->graph.get(sr.node) : nullptr)
+            if (hn->stream == r.stream) hn->stream = -1;
+        if (c->stream_wr) (void)hipStreamSynchronize(c->stream_wr);
+    }
     if (r.owned && r.d_data) (void)hipFree(r.d_data);
     r.alive = false;
     r.d_data = nullptr;
@@ -1020,9 +1253,40 @@ int fwgpu_sampler_set_sample(fwgpu_ctx* c, int64_t node, int sample, int stop_pl
     m.type = CMD_SMP_SET_SAMPLE;
     m.i0 = sample;
     m.i1 = stop_playback != 0;
+    // SPEC streaming source: a stream is bound once, to one sampler; the message carries R and the current W
+    StreamRec* sr = stream_of(c, sample);
+    HostNode* hn = c->graph.get(node);
+    int pub = -1;
+    if (sr) {
+        if (!hn || hn->kind != K_SAMPLER) return fail(c, FWGPU_ERR_INVALID, "node kind does not accept this message");
+        if (sr->node >= 0 || sr->detached) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_set_sample: a stream is bound once, to one sampler");
+        for (int i = 0; i < fwgpu_ctx::STREAM_PUB_MAX && pub < 0; ++i)
+            if (c->stream_pub_slot[i] < 0) pub = i;
+        if (pub < 0) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_set_sample: too many samplers hold a stream (64)");
+        m.d0 = fw_double_of(sr->ring);
+        m.d1 = fw_double_of(sr->written);
+    }
     int rc = push_cmd(c, node, K_SAMPLER, m, true);
-    if (rc == 0) c->sample_refs[sample]++;  // the message carries the reference (an Arc clone in the reference: sampler.rs:67-79)
-    return rc;
+    if (rc) return rc;
+    c->sample_refs[sample]++;  // the message carries the reference (an Arc clone in the reference: sampler.rs:67-79)
+    if (hn && hn->stream >= 0 && hn->stream < (int)c->streams.size()) stream_detach(c, c->streams[hn->stream]);  // the stream it held is finished
+    if (hn) hn->stream = sr ? (int)(sr - c->streams.data()) : -1;
+    if (sr) {
+        sr->node = node;
+        {
+            ControlGate gate(c);
+            c->stream_pub_slot[pub] = (int)(node & 0xffffffff);
+            c->stream_pub_n++;
+        }
+        sr->pub = pub;
+        if (sr->ended) {  // (ended before it was bound: the end travels behind the binding)
+            rc = stream_tell(c, *sr, sr->written, true, sr->end_at);
+            // no room for it (FWGPU_ERR_QUEUE_FULL): the binding stands, and fwgpu_sample_stream_end, called again, delivers the end
+            if (rc) return rc;
+            sr->end_told = true;
+        }
+    }
+    return 0;
 }
 static int simple_msg(fwgpu_ctx* c, int64_t node, int type, uint32_t at_block) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
@@ -1063,6 +1327,8 @@ int fwgpu_sampler_set_playhead_secs(fwgpu_ctx* c, int64_t node, double secs, uin
     Cmd m;
     memset(&m, 0, sizeof(m));
     m.block = at_block;
+    if (HostNode* hn = c->graph.get(node))
+        if (hn->stream >= 0) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_set_playhead_secs: the sampler holds a stream: there is no position to seek to");
     m.type = CMD_SMP_SET_PLAYHEAD;
     m.d0 = secs;
     return push_cmd(c, node, K_SAMPLER, m, true);
@@ -1073,6 +1339,8 @@ int fwgpu_sampler_set_loop_range(fwgpu_ctx* c, int64_t node, int mode, double st
     Cmd m;
     memset(&m, 0, sizeof(m));
     m.block = at_block;
+    if (HostNode* hn = c->graph.get(node))
+        if (hn->stream >= 0) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_set_loop_range: the sampler holds a stream: there is no range to loop");
     m.type = CMD_SMP_SET_LOOP;
     m.i0 = mode;
     m.d0 = start;

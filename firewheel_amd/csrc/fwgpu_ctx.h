@@ -121,6 +121,22 @@ struct SampleRec {
     bool owned = true;
     void* d_data = nullptr;
     SampleDesc desc{};
+    int stream = -1;  // index into fwgpu_ctx::streams when the storage is a ring (fwgpu_sample_create_stream), else -1
+};
+
+// SPEC streaming source, control side: a sample whose storage is a ring of `ring` frames the control side appends to
+struct StreamRec {
+    int sample = -1;
+    uint64_t ring = 0;
+    uint64_t written = 0;     // frames appended so far (the end's padding included): W as the control side knows it
+    uint64_t end_at = 0;      // E, valid once `ended`
+    bool ended = false;
+    bool end_told = false;    // the message that carries E has been queued to the bound sampler (fwgpu_sample_stream_end repeats it until then)
+    int64_t node = -1;        // the sampler it was bound to — once — or -1
+    int pub = -1;             // its entry of fwgpu_ctx::stream_pub_slot while the audio side publishes its counts, else -1
+    bool detached = false;    // the sampler took another sample, or was removed, or the stream was destroyed: finished for good
+    uint64_t consumed = 0, starved = 0;  // C and U as of the last completed process call that published them
+    bool finished = false;
 };
 
 constexpr size_t RT_IO_BYTES = 256 * 1024;  // realtime path: calls whose interleaved in/out blocks fit (e.g. 16 x 1024 stereo)
@@ -450,6 +466,20 @@ struct fwgpu_ctx : fwgpu::PlanImage {
     bool ret_this_call = false;
     // control side of the same: reference counts per sample id = SetSample messages sent - samples handed back
     std::vector<int64_t> sample_refs;
+    // SPEC streaming sources.  Control side: the streams, and the copy stream their writes run on (never the audio
+    // stream).  Audio side, changed only under ControlGate: the state slots of the samplers that hold a stream — once per process call
+    // ONE launch_build_apply copies their NodeStates to pinned memory (two banks, by call parity; an event and a ticket per bank say
+    // which call a bank holds and whether it has completed).  While stream_pub_n > 0 the resident realtime kernel is not launched.
+    static constexpr int STREAM_PUB_MAX = 64;  // samplers on a stream at one time
+    std::vector<StreamRec> streams;
+    hipStream_t stream_wr = nullptr;
+    int stream_pub_slot[STREAM_PUB_MAX];  // state slot, or -1: entry free
+    int stream_pub_n = 0;
+    NodeState* h_stream_pub = nullptr;    // pinned [2][STREAM_PUB_MAX]
+    BuildJob* h_stream_jobs = nullptr;    // pinned [2][STREAM_PUB_MAX]
+    hipEvent_t ev_stream_pub[2] = {nullptr, nullptr};
+    std::atomic<uint64_t> stream_pub_ticket[2] = {};  // 1 + the number of the process call whose publication the bank holds; 0: none, or being written
+    uint64_t stream_pub_calls = 0;        // audio side: process calls that published so far
     std::vector<RetItem> ret_ready;  // completed returns not yet handed to fwgpu_poll_returned_samples
     std::vector<uint32_t> dropped_samplers_ctl;  // control side: removed sampler nodes since the last build
 
@@ -743,6 +773,7 @@ int upload_cmds(fwgpu_ctx* c, bool drained = false);  // drained: the caller has
 int rt_persist_stop(fwgpu_ctx* c);
 int lazy_flush(fwgpu_ctx* c);  // audio side (or whoever holds the gate): node state brought up to date after lazily rendered blocks; the LazyRecs end here
 int rt_block_relaunch(fwgpu_ctx* c, float* d_out, unsigned long long seq);  // after the watchdog race: the same block through k_rt_block  // ends the resident realtime kernel, if one is running, and waits for it
+int publish_streams(fwgpu_ctx* c);  // end of a process call: the counts of the samplers that hold a stream -> pinned memory, one launch
 void finish_returns(fwgpu_ctx* c);  // end of a process call: completion event for the samples it handed back
 void retire_cmds(fwgpu_ctx* c, uint32_t nblocks);
 void retire_cmds_node(fwgpu_ctx* c, int slot);

@@ -37,6 +37,7 @@ struct HostNode {
     // thread publishes a drain epoch, the count restarts when the producer sees a new one.
     int pending_msgs = 0;
     uint64_t pending_epoch = 0;
+    int stream = -1;  // a sampler whose sample, as last sent, is a stream (SPEC streaming source): its index in fwgpu_ctx::streams
 };
 
 inline int64_t make_id(uint32_t slot, uint32_t gen) { return (int64_t(gen) << 32) | int64_t(slot); }

@@ -187,6 +187,36 @@ void finish_returns(fwgpu_ctx* c) {
     c->returns.publish();
     c->ret_ticket++;
 }
+// SPEC streaming sources: C, U and `finished` of every sampler that holds a stream, as this call leaves them, go to
+// pinned memory — the whole 128-byte NodeState of each, as one-row copy jobs of ONE launch_build_apply behind the call's kernels.  The
+// control side reads a bank once its event has completed (fwgpu_abi.cpp stream_refresh).  A fixed number of calls per process call.
+int publish_streams(fwgpu_ctx* c) {
+    if (c->stream_pub_n == 0 || !c->h_stream_pub) return 0;
+    const int bank = (int)(c->stream_pub_calls & 1);
+    // (the bank's last publication — two calls ago — has been read by its kernel: the job list may be rewritten)
+    if (c->stream_pub_calls >= 2) HIPC(c, hipEventSynchronize(c->ev_stream_pub[bank]));
+    c->stream_pub_ticket[bank].store(0, std::memory_order_release);
+    BuildJob* jobs = c->h_stream_jobs + (size_t)bank * fwgpu_ctx::STREAM_PUB_MAX;
+    const size_t n_states = c->d_states.cap / sizeof(NodeState);
+    int n = 0;
+    for (int i = 0; i < fwgpu_ctx::STREAM_PUB_MAX; ++i) {
+        const int slot = c->stream_pub_slot[i];
+        if (slot < 0 || (size_t)slot >= n_states) continue;  // (a sampler no built plan holds yet has no state to copy)
+        BuildJob j;
+        memset(&j, 0, sizeof(j));
+        j.dst = c->h_stream_pub + (size_t)bank * fwgpu_ctx::STREAM_PUB_MAX + i;
+        j.src = c->d_states.as<NodeState>() + slot;
+        j.row_bytes = j.pitch = sizeof(NodeState);
+        j.rows = 1;
+        j.head = -1;
+        jobs[n++] = j;
+    }
+    if (n) LCHK(c, launch_build_apply(c->stream, jobs, n));
+    HIPC(c, hipEventRecord(c->ev_stream_pub[bank], c->stream));
+    c->stream_pub_ticket[bank].store(c->stream_pub_calls + 1, std::memory_order_release);
+    c->stream_pub_calls++;
+    return 0;
+}
 void retire_cmds(fwgpu_ctx* c, uint32_t nblocks) {
     size_t w = 0;  // in place: nothing is allocated on the process path
     for (const Cmd& m : c->cmds)
@@ -600,7 +630,9 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
         // (on a big tree the resident kernel LOSES to a launch per callback — config 5's 256 leaf workgroups: 94-113 us resident, 51-53
         //  launched, round 5: hundreds of idle workgroups polling beside the few that carry the block up the tree — so it is the small
         //  trees' edge: rt_persist_max_leaves, FWGPU_RT_PERSIST_MAX_LEAVES)
-        if (c->rt_persist && c->n_leaves <= c->rt_persist_max_leaves && c->rt_stream && flag && c->n_cmds_dev == 0 && !c->host_prof && cmd_block0 == 0) {
+        // (SPEC streaming sources: while a sampler holds a stream every callback is its own launch — the resident kernel fetches the next
+        //  block's sources ahead of its doorbell, and must not do that from a ring that is being written)
+        if (c->rt_persist && c->stream_pub_n == 0 && c->n_leaves <= c->rt_persist_max_leaves && c->rt_stream && flag && c->n_cmds_dev == 0 && !c->host_prof && cmd_block0 == 0) {
             fwgpu_ctx::RtResident& r = c->rtp;
             const unsigned long long seq = c->rt_signal_seq;
             if (r.launched && c->h_rt_mb->alive && r.epoch == c->epoch && r.d_out == d_out && r.blks == fv.blks && r.next_seq == seq &&
@@ -801,7 +833,10 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     drain_ring(c);
     note_bq_sweeps(c);
     const bool hot = c->ctl_ahead_mode == 1 || !c->cmds.empty() || !c->hot_prev.empty();
-    const bool ahead = c->ctl_ahead_on && hot && can_fuse && !c->timing && !stable_out && frames % mbf == 0 && frames / mbf > 1;
+    // (SPEC streaming sources: no ahead mode while a sampler holds a stream.  The control kernel of call N + 1 would move C beside or
+    //  before the render of call N, whose publication — a copy of the live NodeStates behind that render — could then hand the writer a
+    //  C the leaf kernel has not read up to yet: an overestimate of the free space.  Every write makes the next call hot, so it matters)
+    const bool ahead = c->ctl_ahead_on && hot && can_fuse && !c->timing && !stable_out && frames % mbf == 0 && frames / mbf > 1 && c->stream_pub_n == 0;
     if (!ahead && c->streams_split) {
         rc = join_streams(c);
         if (rc) return rc;
@@ -868,6 +903,8 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
         HIPC(c, hipGraphLaunch(g.exec, c->stream));
         c->blocks_done += nblocks;
         c->frames_done += frames;
+        rc = publish_streams(c);
+        if (rc) return rc;
         retire_cmds(c, nblocks);
         return 0;
     }
@@ -893,6 +930,11 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
         c->blocks_done += (uint64_t)K;
         done += (uint64_t)K * bf;
         blk += K;
+    }
+    rc = publish_streams(c);
+    if (rc) {
+        c->ahead_this_call = false;
+        return rc;
     }
     if (c->rt_signal_seq && !c->rt_signalled) {
         LCHK(c, launch_signal_done(c->stream, c->d_rt_flag, c->rt_signal_seq));

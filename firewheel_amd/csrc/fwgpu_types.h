@@ -140,6 +140,9 @@ struct NodeState {
     //        message but CMD_SMP_FADE reaches these fields (a sampler's only parameter is p0); a node's state keeps its slot over
     //        a plan install (only the steady cache is carried, and a voice in a fade has none), and k_lazy_flush moves the playhead alone — a voice in a fade leaves no lazy record.  The arithmetic is
     //        smp_env_* below the struct
+    //   SAMPLER on a stream (CMD_SMP_STREAM) also keeps W, C, E, U and its flags as raw bits in ext_off / ext_len, s1.input /
+    //        s1.last, s1.a / s1.b, aux and phasor_inc (a sampler has no ext slice and no second smoother), with has_loop = 1 and
+    //        loop = [0, R): smp_stream_* below the struct.  A sampler that holds no stream has phasor_inc == 0 (make_state)
     //   RESAMPLER: sample = source, playhead = 32.32 source position, loop_start = 32.32 step, has_loop, playing; a ratio glide
     //        (CMD_RS_GLIDE): full_range = left (frames of the glide still to render, 0: none), loop_end = target (the
     //        step behind the glide), enabled / ext_off = the low / high 32 bits of inc, the signed step change per frame (a
@@ -295,15 +298,151 @@ FW_TYPES_HD inline void smp_env_start(NodeState& s, float target, uint32_t frame
     s.enabled = (int)(frames | ((uint32_t)then << 28));
     s.s1.status = 0;
 }
+// K_SAMPLER on a stream (SPEC streaming source): ONE statement for the messages (apply_cmds_from), the node kernels and
+// the control kernel.  The sample is a ring of R frames the control side appends to; the sampler is a looping sampler over the whole
+// ring (has_loop = 1, loop = [0, R): smp_stream_bind sets the fields, no loop or seek message moves them while the stream is on) and
+// keeps four integers in fields a sampler has no other use for, as raw bits: W (frames written that it has been told of) in
+// ext_off | ext_len << 32, C (frames consumed) in s1.input | s1.last << 32, E (the end; valid with SMP_STREAM_HAS_END) in
+// s1.a | s1.b << 32, U (starved blocks) in aux, the flags in phasor_inc.  A sampler that holds no stream has flags == 0.
+#define SMP_STREAM_ON 1u
+#define SMP_STREAM_HAS_END 2u
+#define SMP_STREAM_FINISHED 4u
+#define SMP_STREAM_RING_MAX (1ull << 30)
+#define SMP_STREAM_RING_MIN_BLOCKS 4u
+FW_TYPES_HD inline uint32_t fw_bits_of(float f) {
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    return u;
+}
+FW_TYPES_HD inline float fw_float_of(uint32_t u) {
+    float f;
+    __builtin_memcpy(&f, &u, 4);
+    return f;
+}
+FW_TYPES_HD inline uint64_t fw_bits_of64(double d) {
+    uint64_t u;
+    __builtin_memcpy(&u, &d, 8);
+    return u;
+}
+FW_TYPES_HD inline double fw_double_of(uint64_t u) {
+    double d;
+    __builtin_memcpy(&d, &u, 8);
+    return d;
+}
+struct SmpStream {
+    uint64_t W, C, E;
+    uint32_t U, flags;
+};
+FW_TYPES_HD inline uint32_t smp_stream_flags(const NodeState& s) { return fw_bits_of(s.phasor_inc); }
+FW_TYPES_HD inline bool smp_stream_on(const NodeState& s) { return (smp_stream_flags(s) & SMP_STREAM_ON) != 0u; }
+FW_TYPES_HD inline bool smp_stream_finished(const NodeState& s) { return (smp_stream_flags(s) & SMP_STREAM_FINISHED) != 0u; }
+// the voice reads a ring that may be written under it: never steady, never frozen, no lazy record — until the stream is finished
+FW_TYPES_HD inline bool smp_stream_live(const NodeState& s) { return (smp_stream_flags(s) & (SMP_STREAM_ON | SMP_STREAM_FINISHED)) == SMP_STREAM_ON; }
+FW_TYPES_HD inline SmpStream smp_stream_of(const NodeState& s) {
+    SmpStream t;
+    t.W = (uint64_t)s.ext_off | ((uint64_t)s.ext_len << 32);
+    t.C = (uint64_t)fw_bits_of(s.s1.input) | ((uint64_t)fw_bits_of(s.s1.last) << 32);
+    t.E = (uint64_t)fw_bits_of(s.s1.a) | ((uint64_t)fw_bits_of(s.s1.b) << 32);
+    t.U = fw_bits_of(s.aux);
+    t.flags = smp_stream_flags(s);
+    return t;
+}
+FW_TYPES_HD inline void smp_stream_put(NodeState& s, const SmpStream& t) {
+    s.ext_off = (uint32_t)t.W;
+    s.ext_len = (uint32_t)(t.W >> 32);
+    s.s1.input = fw_float_of((uint32_t)t.C);
+    s.s1.last = fw_float_of((uint32_t)(t.C >> 32));
+    s.s1.a = fw_float_of((uint32_t)t.E);
+    s.s1.b = fw_float_of((uint32_t)(t.E >> 32));
+    s.aux = fw_float_of(t.U);
+    s.phasor_inc = fw_float_of(t.flags);
+}
+// CMD_SMP_SET_SAMPLE with a stream (R = the ring's frames, W = the frames written so far): the sampler starts at the ring's frame 0
+FW_TYPES_HD inline void smp_stream_bind(NodeState& s, uint64_t R, uint64_t W) {
+    SmpStream t;
+    t.W = W;
+    t.C = t.E = 0;
+    t.U = 0;
+    t.flags = SMP_STREAM_ON;
+    smp_stream_put(s, t);
+    s.has_loop = 1;
+    s.full_range = 0;
+    s.loop_start = 0;
+    s.loop_end = R;
+    s.playhead = 0;
+}
+// CMD_SMP_SET_SAMPLE with anything else on a sampler that holds a stream: a one-shot at frame 0 again
+FW_TYPES_HD inline void smp_stream_unbind(NodeState& s) {
+    SmpStream t;
+    t.W = t.C = t.E = 0;
+    t.U = 0;
+    t.flags = 0;
+    smp_stream_put(s, t);
+    s.has_loop = 0;
+    s.full_range = 0;
+    s.loop_start = s.loop_end = 0;
+    s.playhead = 0;
+}
+// CMD_SMP_STREAM: W (never backwards), and with `has_end` the end E; ignored by a sampler that holds no stream.  An end that arrives
+// when every frame has been played already (E <= C: the writer called `end` late) finishes the sampler here, as the block that reached E
+// would have (smp_pause): no block of padding is played behind it
+FW_TYPES_HD inline void smp_stream_msg(NodeState& s, uint64_t W, int has_end, uint64_t E) {
+    if (!smp_stream_on(s)) return;
+    SmpStream t = smp_stream_of(s);
+    if (W > t.W) t.W = W;
+    bool late = false;
+    if (has_end && !(t.flags & SMP_STREAM_HAS_END)) {
+        t.E = E;
+        t.flags |= SMP_STREAM_HAS_END;
+        late = t.E <= t.C;
+        if (late) t.flags |= SMP_STREAM_FINISHED;
+    }
+    smp_stream_put(s, t);
+    if (late) {
+        s.playing = 0;
+        smp_env_reset(s);
+    }
+}
+// In front of a block of n frames of a PLAYING sampler, behind the block's messages.  true: the frames are not there (W - C < n) —
+// U += 1 and the block is rendered exactly as a block of a sampler that does not play; `playing` itself stays 1
+FW_TYPES_HD inline bool smp_stream_starved(NodeState& s, uint32_t n) {
+    if (!smp_stream_on(s)) return false;
+    SmpStream t = smp_stream_of(s);
+    if (t.W - t.C >= (uint64_t)n) return false;
+    t.U += 1u;
+    smp_stream_put(s, t);
+    return true;
+}
+// How many of a block's n frames lie in front of the end (n: all of them; call it in front of the block's advance).  A block the end
+// falls into is rendered as a one-shot's last block — frames from there on are 0.0 (the Fetch's tail_zero) — unless the ring's wrap
+// falls in front of the end inside the same block: a record holds one break, so that block reads the padding behind the end from the
+// ring (zero bytes; the unsigned 16-bit formats have no element that decodes to 0.0, their padding is 0x8000: 1.5e-5)
+FW_TYPES_HD inline uint32_t smp_stream_block_data(const NodeState& s, uint32_t n) {
+    if ((smp_stream_flags(s) & (SMP_STREAM_ON | SMP_STREAM_HAS_END)) != (SMP_STREAM_ON | SMP_STREAM_HAS_END)) return n;
+    const SmpStream t = smp_stream_of(s);
+    if (t.E <= t.C) return 0u;
+    return t.E - t.C < (uint64_t)n ? (uint32_t)(t.E - t.C) : n;
+}
 // CMD_SMP_PAUSE / CMD_SMP_STOP (sampler.rs:372-391), as messages and as what a fade's `then` asks for
 FW_TYPES_HD inline void smp_pause(NodeState& s) {
     s.playing = 0;
     smp_env_reset(s);
 }
 FW_TYPES_HD inline void smp_stop(NodeState& s) {
-    s.playhead = s.has_loop ? s.loop_start : 0;
+    if (!smp_stream_on(s)) s.playhead = s.has_loop ? s.loop_start : 0;  // (a stream does not rewind: stop acts as pause)
     s.playing = 0;
     smp_env_reset(s);
+}
+// Behind a rendered block of n frames (behind smp_env_behind_block); ph0 = the playhead in front of the block.  C moves in exactly
+// the blocks in which the playhead moved (a muted voice holds both); at the end the sampler stops where it stands and is finished
+FW_TYPES_HD inline void smp_stream_behind_block(NodeState& s, uint64_t ph0, uint32_t n) {
+    if (!smp_stream_on(s) || s.playhead == ph0) return;
+    SmpStream t = smp_stream_of(s);
+    t.C += (uint64_t)n;
+    const bool end = (t.flags & SMP_STREAM_HAS_END) && t.C >= t.E;
+    if (end) t.flags |= SMP_STREAM_FINISHED;
+    smp_stream_put(s, t);
+    if (end) smp_pause(s);
 }
 // behind a rendered block of `frames` frames in which the gain smoother ran (the values are smp_env_value of a snapshot taken BEFORE
 // this): k += frames; a fade that is over comes to rest and its `then` takes effect; a sampler that no longer plays — paused or
@@ -448,6 +587,8 @@ enum : int {
     CMD_SMP_SET_SAMPLE = 10, CMD_SMP_PLAY = 11, CMD_SMP_PAUSE = 12, CMD_SMP_STOP = 13,
     CMD_SMP_SET_PLAYHEAD = 14, CMD_SMP_SET_LOOP = 15,
     CMD_SMP_FADE = 16,  // sampler: f0 = target gain (0..1), i0 = frames to reach it over, i1 = then (SMP_FADE_*) (smp_env_start)
+    CMD_SMP_STREAM = 17,  // sampler on a stream: d0 bits = W, the frames written so far; i0 != 0: the stream has ended, d1 bits = E (smp_stream_msg);
+                          // CMD_SMP_SET_SAMPLE of a stream carries d0 bits = R, the ring's frames, and d1 bits = W (smp_stream_bind)
     CMD_RS_STEP = 20,  // resampler: d0 bits = u64 32.32 step
     CMD_RS_SEEK = 21,  // resampler: d0 bits = u64 source frame
     CMD_SP_ITD = 22,   // spatialiser: i0 / i1 = left / right ear delay in frames

@@ -243,6 +243,13 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                 break;
             case CMD_SMP_SET_SAMPLE:  // sampler.rs:333-364
                 s.sample = c.i0;
+                if constexpr (SMP) {  // SPEC streaming source: d0 bits = the ring's frames R (0: no stream), d1 bits = W
+                    if (smp_env) {
+                        const uint64_t R = (uint64_t)__double_as_longlong(c.d0);
+                        if (R) smp_stream_bind(s, R, (uint64_t)__double_as_longlong(c.d1));
+                        else if (smp_stream_on(s)) smp_stream_unbind(s);
+                    }
+                }
                 if (s.has_loop && s.sample >= 0 && s.full_range) {  // update_sample :265-277
                     s.loop_start = 0;
                     s.loop_end = samples[s.sample].frames;
@@ -253,13 +260,15 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                     if (SMP && smp_env) smp_env_reset(s);
                 }
                 break;
-            case CMD_SMP_PLAY: s.playing = 1; break;  // :365-371
+            case CMD_SMP_PLAY:  // :365-371 (a finished stream stays finished)
+                if (!(SMP && smp_env && smp_stream_finished(s))) s.playing = 1;
+                break;
             case CMD_SMP_PAUSE:                       // :372-378
                 s.playing = 0;
                 if (SMP && smp_env) smp_env_reset(s);
                 break;
-            case CMD_SMP_STOP:  // :379-391
-                s.playhead = s.has_loop ? s.loop_start : 0;
+            case CMD_SMP_STOP:  // :379-391 (a stream does not rewind: stop acts as pause)
+                if (!(SMP && smp_env && smp_stream_on(s))) s.playhead = s.has_loop ? s.loop_start : 0;
                 s.playing = 0;
                 if (SMP && smp_env) smp_env_reset(s);
                 break;
@@ -268,7 +277,13 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                     if (smp_env) smp_env_start(s, c.f0, (uint32_t)c.i0, c.i1);
                 }
                 break;
-            case CMD_SMP_SET_PLAYHEAD:  // :392-399
+            case CMD_SMP_STREAM:  // SPEC streaming source: d0 bits = W, i0 = an end follows, d1 bits = E (smp_stream_msg)
+                if constexpr (SMP) {
+                    if (smp_env) smp_stream_msg(s, (uint64_t)__double_as_longlong(c.d0), c.i0, (uint64_t)__double_as_longlong(c.d1));
+                }
+                break;
+            case CMD_SMP_SET_PLAYHEAD:  // :392-399 (ignored on a stream, like CMD_SMP_SET_LOOP: nothing to seek to, no range to loop)
+                if (SMP && smp_env && smp_stream_on(s)) break;
                 s.playhead = sat_round_u64(c.d0 * (double)s.sample_rate);
                 break;
             case CMD_RS_STEP:  // (a step ends a glide in flight)
@@ -297,6 +312,7 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
             }
                 break;  // (compiled out: the message is ignored, it does not fall through)
             case CMD_SMP_SET_LOOP:  // :400-412 + ProcLoopRange::new :241-263
+                if (SMP && smp_env && smp_stream_on(s)) break;
                 if (c.i0 == 0) {
                     s.has_loop = 0;
                 } else {
@@ -408,6 +424,15 @@ __device__ __forceinline__ bool sampler_advance(NodeState& s, uint64_t len, uint
         s.playhead += (uint64_t)frames;
     }
     return true;
+}
+
+// SPEC streaming source: the block the stream's end falls into, `data` = smp_stream_block_data taken in front of the
+// advance.  It becomes a one-shot's last block unless the ring's wrap comes first (a Fetch holds one break)
+__device__ __forceinline__ void stream_tail(Fetch& f, uint32_t data, uint32_t frames) {
+    if (data >= frames || (f.wrap && f.n1 < data)) return;
+    f.n1 = data;
+    f.wrap = 0;
+    f.tail_zero = 1;
 }
 
 // core/sample_resource.rs:338-345 + fill_buffers_* :348-456 — one source element, converted.

@@ -1160,7 +1160,11 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
                 else if ((np >> 32) >= sd.frames + RS_TAPS / 2) ss.playing = 0;
                 ss.playhead = np;
             }
-        } else if (ss.sample >= 0 && ss.playing && sd.data != nullptr) {
+        } else if (ss.sample >= 0 && ss.playing && sd.data != nullptr && !smp_stream_starved(ss, (uint32_t)frames)) {
+            // (SPEC streaming source, DESIGN.md §6: a starved block is the record of a voice that does not play; a played one is a looping
+            //  voice's record, and C moves in the blocks in which the playhead does)
+            const uint64_t stream_ph0 = ss.playhead;
+            const uint32_t stream_data = smp_stream_block_data(ss, (uint32_t)frames);
             GainRun run = smoother_begin(ss.s0, ss.p0, frames);
             // SPEC gain envelope: it moves with the smoother, in every block that gets here.  The values of THIS block
             // come from the state as it stands here; the state moves on behind the block (smp_env_behind_block)
@@ -1169,6 +1173,7 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
             if (!(!smoother_is_smoothing(ss.s0) && run.c < 0.00001f)) {
                 Fetch ft;
                 bool ok = sampler_advance(ss, sd.frames, (uint32_t)frames, ft);
+                if (ok) stream_tail(ft, stream_data, (uint32_t)frames);
                 bool had_ramp = false;
                 if (run.ramp) {
                     if (ramp_emit(run, frames, ramp_base, ramp_base + fv.stride, lane)) {
@@ -1196,6 +1201,7 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
                 }
             }
             smp_env_behind_block(ss, (uint32_t)frames);
+            smp_stream_behind_block(ss, stream_ph0, (uint32_t)frames);
         }
         CTL_T(10);
         // a biquad / delay between the sampler and the gain stages never reports silence (SPEC nodes: out mask 0)
@@ -1309,7 +1315,9 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
         bool upstream_silent = false;
         bool ramping = false;  // some smoother is still moving: the rest of the call is a RAMP CONTINUATION, then steady
         int mode = 0;
-        if (ss.sample < 0 || !ss.playing || sd.data == nullptr || (vd.src_kind == 1 && sd.frames == 0)) {
+        if (vd.src_kind != 1 && smp_stream_live(ss)) {
+            steady = false;  // a voice on a stream is never steady: no carried cache, no lazy record — W, C and U move block by block
+        } else if (ss.sample < 0 || !ss.playing || sd.data == nullptr || (vd.src_kind == 1 && sd.frames == 0)) {
             upstream_silent = true;  // frozen sampler: nothing moves
         } else if (vd.src_kind == 1) {  // resampling source: the position has a closed form while it keeps playing
             if (cached_sample != ss.sample || ss.full_range != 0) steady = false;  // (a glide in flight: block by block, no lazy record)

@@ -448,6 +448,13 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
                 out_mask = clear_all_outputs(io, 0, nd.n_out);
                 break;
             }
+            // SPEC streaming source: a block whose frames are not in the ring yet is a block of a sampler that does not play
+            if (smp_stream_starved(s, (uint32_t)frames)) {
+                out_mask = clear_all_outputs(io, 0, nd.n_out);
+                break;
+            }
+            const uint64_t stream_ph0 = s.playhead;  // (C moves in the blocks in which the playhead does: smp_stream_behind_block)
+            const uint32_t stream_data = smp_stream_block_data(s, (uint32_t)frames);
             GainRun run = smoother_begin(s.s0, s.p0, frames);        // :432-433
             // SPEC gain envelope: it moves with the smoother — in every block that gets here, whatever happens below.
             // `env`: the envelope as this block's frames read it; the state moves on behind the block (smp_env_behind_block), on every exit
@@ -481,8 +488,10 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
                 }
                 out_mask = clear_all_outputs(io, 0, nd.n_out);
                 smp_env_behind_block(s, (uint32_t)frames);
+                smp_stream_behind_block(s, stream_ph0, (uint32_t)frames);
                 break;
             }
+            stream_tail(ft, stream_data, (uint32_t)frames);
             const int sch = sd.channels;
             const int nfill = nd.n_out < sch ? nd.n_out : sch;  // fill_buffers zip + gain zip (:535)
             // planar f32, the whole block contiguous in the sample: one 16-byte load per lane and channel instead of
@@ -515,6 +524,7 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
                 for (int c = sch; c < nd.n_out; ++c) out_mask |= (1ull << c);  // :556
             if (run.ramp) s.s0.last = run.prev;
             smp_env_behind_block(s, (uint32_t)frames);
+            smp_stream_behind_block(s, stream_ph0, (uint32_t)frames);
             break;
         }
 
@@ -981,6 +991,8 @@ __global__ void k_frozen_scan(DevView v, int n_nodes, uint32_t cmd_block0, uint3
                 case K_SAMPLER:  // steady playback: the playhead of block b has a closed form (see node_process_wave)
                     if (s.sample < 0 || !s.playing || v.samples[s.sample].data == nullptr) {
                         fz = true;  // outputs cleared, nothing moves (sampler.rs:416-430)
+                    } else if (smp_stream_live(s)) {
+                        // SPEC streaming source: never frozen — W, C and the starved count move block by block (the serial path)
                     } else if (smoother_at_rest(s.s0, s.p0) && smp_env_at_rest(s)) {  // (a fade in flight moves every block: the serial path)
                         if (s.s0.status == SM_INACTIVE && s.s0.input < 0.00001f) {
                             fz = true;  // muted: cleared, the playhead does not move (:437-443)

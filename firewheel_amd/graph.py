@@ -121,7 +121,9 @@ class SamplerNode(_Node):  # nodes/sampler.rs:46-182
         self._set(0, percent_volume, at_block)
 
     def set_sample(self, sample, stop_playback, at_block=0):
-        self.cx._check(self.cx.L.fwgpu_sampler_set_sample(self.cx.c, self.id, sample, int(stop_playback), at_block))
+        """`sample`: a sample id, or a StreamSource (FirewheelGpuCtx.new_stream) — that binds the stream to this sampler, once"""
+        sid = sample.id if isinstance(sample, StreamSource) else sample
+        self.cx._check(self.cx.L.fwgpu_sampler_set_sample(self.cx.c, self.id, sid, int(stop_playback), at_block))
 
     def play(self, at_block=0):  # sampler.rs:82-97: only sends when not already playing
         if not self.playing:
@@ -178,6 +180,50 @@ class SamplerNode(_Node):  # nodes/sampler.rs:46-182
         self.cx._check(self.cx.L.fwgpu_sampler_play(self.cx.c, self.id, at_block))
         self.playing = True
         self.fade_to(1.0, frames, None, at_block)
+
+
+class StreamSource(object):
+    """A sample whose storage is a ring fed while one sampler plays it (SPEC streaming source; include/fwgpu.h
+    fwgpu_sample_create_stream).  `id` is its sample id: destroy_sample / sample_retired take it like any other."""
+
+    def __init__(self, cx, fmt, channels, ring_frames):
+        self.cx, self.fmt, self.channels, self.ring_frames = cx, fmt, channels, int(ring_frames)
+        self.id = cx._check(cx.L.fwgpu_sample_create_stream(cx.c, fmt, channels, self.ring_frames))
+        self.ended = False
+
+    def write(self, data):
+        """append frames: a numpy array (or anything numpy converts) laid out as new_sample's data, or a torch tensor on this device
+        (no copy through the host).  Returns the frames accepted, 0..frames: the ring's free space as of the last process call known to
+        be complete.  A full message ring raises FwgpuError(FWGPU_ERR_QUEUE_FULL); the same call can then be repeated."""
+        if hasattr(data, "data_ptr") and getattr(data, "is_cuda", False):
+            t = data.contiguous()
+            if t.element_size() != np.dtype(SampleFormat.DTYPE[self.fmt]).itemsize:
+                raise ValueError("StreamSource.write: the tensor's element size does not fit the stream's format")
+            frames = t.numel() // self.channels
+            import torch
+
+            torch.cuda.current_stream(t.device).synchronize()  # (the copy runs on the library's own stream)
+            return self.cx._check(self.cx.L.fwgpu_sample_stream_write_device(self.cx.c, self.id, C.c_void_p(t.data_ptr()), frames))
+        a = np.ascontiguousarray(np.asarray(data, dtype=SampleFormat.DTYPE[self.fmt]))
+        frames = a.size // self.channels
+        return self.cx._check(self.cx.L.fwgpu_sample_stream_write(self.cx.c, self.id, a.ctypes.data_as(C.c_void_p), frames))
+
+    def end(self):
+        """no more data: the sampler stops behind the last frame written.  FwgpuError(FWGPU_ERR_QUEUE_FULL) while the ring has no room
+        for the max_block_frames of padding yet"""
+        self.cx._check(self.cx.L.fwgpu_sample_stream_end(self.cx.c, self.id))
+        self.ended = True
+
+    def status(self):
+        """(written, consumed, starved_blocks, finished) as of the last completed process call; never blocks"""
+        w, c, u, f = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        self.cx._check(self.cx.L.fwgpu_sample_stream_status(self.cx.c, self.id, C.byref(w), C.byref(c), C.byref(u), C.byref(f)))
+        return w.value, c.value, u.value, bool(f.value)
+
+    def free_frames(self):
+        """how many frames write() would accept now (an underestimate, never an overestimate; 0 behind end())"""
+        w, c, _, fin = self.status()
+        return 0 if fin or self.ended else self.ring_frames - (w - c)
 
 
 class HardClipNode(_Node):  # nodes/hard_clip.rs:7-13
@@ -818,6 +864,10 @@ class FirewheelGpuCtx(object):
 
     def new_sample_device(self, fmt, channels, frames, device_ptr):
         return self._check(self.L.fwgpu_sample_create_device(self.c, fmt, channels, frames, C.c_void_p(device_ptr)))
+
+    def new_stream(self, fmt, channels, ring_frames):
+        """a StreamSource: a ring of `ring_frames` frames (4 * max_block_frames .. 2^30) that SamplerNode.set_sample accepts"""
+        return StreamSource(self, fmt, channels, ring_frames)
 
     def destroy_sample(self, sample):
         """Release a sample's HBM (the last Arc<dyn SampleResource> dropped).  Refused while a FIR / resampler node

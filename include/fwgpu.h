@@ -309,6 +309,68 @@ enum fwgpu_fade_then { FWGPU_FADE_NONE = 0, FWGPU_FADE_PAUSE = 1, FWGPU_FADE_STO
 #define FWGPU_SAMPLER_FADE_FRAMES_MAX 16777216
 int fwgpu_sampler_fade(fwgpu_ctx* ctx, int64_t node, float target, uint32_t frames, int then, uint32_t at_block);
 
+/* ---- streaming sample sources: a sampler that plays a ring fed while it plays (SPEC; the "disk and network streaming"
+ * of the reference's DESIGN_DOC.md:11-28).  A stream is a sample whose storage is a ring of R = ring_frames frames, zeroed at creation.
+ * The control side appends frames to it, ONE sampler plays them in order; a block for which the frames are not there yet is silent, and
+ * the voice carries on in the block in which they are.  The id lives in the sample table like any other: fwgpu_sample_destroy and
+ * fwgpu_sample_retired work on it unchanged.  All six formats; R in [4 * max_block_frames, 2^30], anything else is FWGPU_ERR_INVALID.
+ * A stream that is never starved needs a ring that holds a whole process call: R >= (blocks per call + 1) * max_block_frames.
+ *   write         accepts min(frames, R - (written - consumed_seen)) frames and returns that number.  consumed_seen is the consumed count
+ *                 of the last process call KNOWN to be complete: it lags the device, so the free space is an underestimate, never an
+ *                 overestimate.  `data` is laid out as fwgpu_sample_create lays out a sample of `frames` frames (planar: channel c starts
+ *                 c * frames elements in).  The frames go straight into the free part of the ring (split at its end, and per channel for
+ *                 the planar formats) by plain copies on a stream of the control side's own — never the audio stream, never waiting for
+ *                 a process call — and once they have landed ONE message (CMD_SMP_STREAM = 17, at_block 0) tells the bound sampler the
+ *                 new `written`: the frames can be played from the first block of the next process call, and no frame is read before it
+ *                 is there.  A full message ring: `written` does not move, FWGPU_ERR_QUEUE_FULL, and the same call can be repeated.
+ *                 Writes before a sampler holds the stream only fill the ring.
+ *   write_device  the same from memory already on this device (a decoder on the GPU, a torch tensor).
+ *   end           appends max_block_frames frames of padding behind the data (zero bytes; 0x8000 for the unsigned 16-bit formats, which
+ *                 have no element that decodes to 0.0) and tells the sampler E = the frames written before the padding.
+ *                 FWGPU_ERR_QUEUE_FULL while that much space is not free yet.  After `end`, write and end are refused — with one
+ *                 exception: a stream ended BEFORE it was bound sends its end behind the binding, and if fwgpu_sampler_set_sample
+ *                 returns FWGPU_ERR_QUEUE_FULL for such a stream the binding stands and only the end was not sent: call end again
+ *                 (after a process call) and it is delivered.  An end that reaches the sampler when every frame has been played
+ *                 already finishes it there: the blocks in between were starved, and no block of padding is rendered.
+ *   status        the counts as of the last completed process call that published them; never blocks.  *written: frames of data
+ *                 accepted so far (the padding not counted), *consumed = C, *starved_blocks = U, *finished: the sampler has played past
+ *                 the end, or has let go of the stream (another sample set on it, the node removed, the stream destroyed).
+ * Binding: fwgpu_sampler_set_sample with a stream id binds it — once, to one sampler (a second binding is FWGPU_ERR_INVALID; bind with
+ * at_block 0: the sampler hears of writes only once it holds the stream).  A FIR or resampler node built on a stream id is refused.
+ * Setting another sample on the sampler, or removing the node, leaves the stream finished.  fwgpu_sampler_set_playhead_secs and
+ * fwgpu_sampler_set_loop_range are refused on a sampler whose sample, as last sent, is a stream: there is no position to seek to and no
+ * range to loop.  At most 64 samplers hold a stream at one time.
+ * The sampler, at a block of n frames behind the block's messages, with W (frames written that it has been told of), C (consumed), E
+ * (the end, or none) and U (starved blocks), all integers:
+ *   1. it is a looping sampler over the whole ring, whatever its loop fields said: loop = [0, R), playhead = C mod R.
+ *   2. starved: if it is playing and W - C < n then U += 1 and the block is rendered exactly as a block of the same sampler with
+ *      playing == 0 — output, silence flags, a smoother and an envelope that do not move; `playing` itself stays 1, nothing else changes.
+ *   3. otherwise the block is the looping sampler's block, and C moves by n in exactly the blocks in which that sampler's playhead moves
+ *      (a muted voice holds C as it holds its playhead).
+ *   4. the end: behind a block that moved C, if E is set and C >= E the sampler does what fwgpu_sampler_pause at the next block's first
+ *      frame would do (playing = 0, the envelope to rest) and is finished; fwgpu_sampler_play on a finished stream is ignored.  The block
+ *      the end falls into is rendered as a one-shot's last block (frames behind the end are 0.0), so for the blocks that hold data the
+ *      output equals that of a one-shot holding the same data, bit for bit — except where the ring's wrap falls in front of the end
+ *      inside that same block: those frames are read from the padding (0.0 for the signed and float formats, 1.5e-5 for the unsigned).
+ *   5. transport: play and pause are what they are; stop (and a fade's FWGPU_FADE_STOP) acts as pause — a stream does not rewind;
+ *      set-playhead and set-loop messages that reach the device anyway are ignored.
+ * A voice that holds a stream is never steady: its calls run the control kernel, it leaves no lazy record, the level executor never
+ * freezes it, and while any sampler holds a stream one-block callbacks take the per-callback launch instead of the resident realtime
+ * kernel.  All of that comes back once the stream is finished (fwgpu_lazy_stats, fwgpu_rt_resident_stats; the resident kernel after
+ * the control side has seen `finished`: any write / end / status call looks).  Once per process call the NodeStates of the samplers that
+ * hold a stream are copied to pinned memory by one launch, however many there are.  Before it reuses one of its two banks a process
+ * call waits for that bank's copy of two calls back: with synchronous calls or paced callbacks that has long completed, but it is a
+ * driver call on the audio path that can block, and while a stream is bound it lets fwgpu_process_blocks_device and its kin run at
+ * most two calls ahead of the device.  While a stream is bound no call takes the control-ahead mode either: the counts a call publishes
+ * are those of frames its kernels have read. */
+#define FWGPU_STREAM_RING_FRAMES_MAX 1073741824ull
+#define FWGPU_STREAM_RING_MIN_BLOCKS 4
+int fwgpu_sample_create_stream(fwgpu_ctx* ctx, int format, uint32_t channels, uint64_t ring_frames); /* -> sample id */
+int fwgpu_sample_stream_write(fwgpu_ctx* ctx, int sample, const void* data, uint64_t frames);        /* -> frames accepted, 0..frames */
+int fwgpu_sample_stream_write_device(fwgpu_ctx* ctx, int sample, const void* device_data, uint64_t frames);
+int fwgpu_sample_stream_end(fwgpu_ctx* ctx, int sample);
+int fwgpu_sample_stream_status(fwgpu_ctx* ctx, int sample, uint64_t* written, uint64_t* consumed, uint64_t* starved_blocks, int* finished);
+
 /* ---- processing */
 /* FirewheelProcessor::process_interleaved (graph/processor.rs:61-165): host buffers, splits `frames`
  * into max_block_frames blocks, returns after the output has landed in `output`. */

@@ -177,6 +177,11 @@ extern "C" {
     pub fn fwgpu_sampler_set_playhead_secs(ctx: *mut fwgpu_ctx, node: i64, playhead_secs: f64, at_block: u32) -> c_int;
     pub fn fwgpu_sampler_set_loop_range(ctx: *mut fwgpu_ctx, node: i64, mode: c_int, start_secs: f64, end_secs: f64, at_block: u32) -> c_int;
     pub fn fwgpu_sampler_fade(ctx: *mut fwgpu_ctx, node: i64, target: f32, frames: u32, then: c_int, at_block: u32) -> c_int;
+    pub fn fwgpu_sample_create_stream(ctx: *mut fwgpu_ctx, format: c_int, channels: u32, ring_frames: u64) -> c_int;
+    pub fn fwgpu_sample_stream_write(ctx: *mut fwgpu_ctx, sample: c_int, data: *const c_void, frames: u64) -> c_int;
+    pub fn fwgpu_sample_stream_write_device(ctx: *mut fwgpu_ctx, sample: c_int, device_data: *const c_void, frames: u64) -> c_int;
+    pub fn fwgpu_sample_stream_end(ctx: *mut fwgpu_ctx, sample: c_int) -> c_int;
+    pub fn fwgpu_sample_stream_status(ctx: *mut fwgpu_ctx, sample: c_int, written: *mut u64, consumed: *mut u64, starved_blocks: *mut u64, finished: *mut c_int) -> c_int;
     pub fn fwgpu_process_interleaved(ctx: *mut fwgpu_ctx, input: *const f32, output: *mut f32, num_in_channels: u32, num_out_channels: u32, frames: u64, stream_time_secs: f64, stream_status: u32) -> c_int;
     pub fn fwgpu_process_interleaved_begin(ctx: *mut fwgpu_ctx, input: *const f32, num_in_channels: u32, num_out_channels: u32, frames: u64, stream_time_secs: f64, stream_status: u32) -> i64;
     pub fn fwgpu_process_interleaved_end(ctx: *mut fwgpu_ctx, ticket: i64, output: *mut f32) -> c_int;

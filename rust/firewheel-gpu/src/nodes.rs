@@ -265,6 +265,74 @@ impl GpuSamplerNode {
         let _ = self.b.set_param(0, percent_volume);
     }
 }
+/// What [`GpuStreamSource::status`] reports, as of the last completed process call.
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct StreamStatus {
+    /// frames of data accepted so far (the end's padding not counted)
+    pub written: u64,
+    /// frames the sampler has played
+    pub consumed: u64,
+    /// blocks that were silent because their frames were not in the ring yet
+    pub starved_blocks: u64,
+    /// the sampler has played past the end, or has let go of the stream
+    pub finished: bool,
+}
+
+/// SPEC streaming source (include/fwgpu.h `fwgpu_sample_create_stream`): a sample whose storage is a ring of
+/// `ring_frames` frames (4 x max_block_frames ..= 2^30) that the control side appends to while ONE sampler plays it — a music track
+/// that sounds before it is decoded to its end, a voice chat, a radio.  Hand it to [`GpuSamplerNode::set_stream`] once; `write` what the
+/// decoder produces whenever there is room, `end` behind the last frame.  A block whose frames are not there yet is silent and the
+/// voice carries on in the block in which they are.
+pub struct GpuStreamSource {
+    cx: Arc<GpuContext>,
+    sample: GpuSample,
+    channels: u32,
+    elem_bytes: usize,
+    ended: bool,
+}
+impl GpuStreamSource {
+    pub fn new(cx: &Arc<GpuContext>, graveyard: &Arc<crate::sample::Graveyard>, format: i32, channels: u32, ring_frames: u64) -> Result<Self, GpuError> {
+        let sample = GpuSample::create_stream(cx, graveyard, format, channels, ring_frames)?;
+        let elem_bytes = if format == ffi::FWGPU_INTERLEAVED_F32 || format == ffi::FWGPU_PLANAR_F32 { 4 } else { 2 };
+        Ok(Self { cx: Arc::clone(cx), sample, channels, elem_bytes, ended: false })
+    }
+    pub fn sample(&self) -> &GpuSample {
+        &self.sample
+    }
+    /// Append frames: `data` holds whole frames of the stream's format, laid out as a sample of that many frames (planar: channel c
+    /// starts c x frames elements in).  Returns the frames accepted, 0..=frames — the ring's free space as of the last process call
+    /// known to be complete; `Err` with `FWGPU_ERR_QUEUE_FULL` when the sampler's message ring is full (repeat the call).
+    pub fn write(&mut self, data: &[u8]) -> Result<u64, GpuError> {
+        let frames = (data.len() / (self.elem_bytes * self.channels as usize)) as u64;
+        let _g = self.cx.control();
+        let rc = unsafe { ffi::fwgpu_sample_stream_write(self.cx.as_ptr(), self.sample.id(), data.as_ptr().cast(), frames) };
+        Ok(self.cx.check(rc as i64)? as u64)
+    }
+    /// No more data: the sampler stops behind the last frame written.  `Err` with `FWGPU_ERR_QUEUE_FULL` while the ring has no room
+    /// for the padding yet (repeat the call after the next process call).
+    pub fn end(&mut self) -> Result<(), GpuError> {
+        let _g = self.cx.control();
+        self.cx.check(unsafe { ffi::fwgpu_sample_stream_end(self.cx.as_ptr(), self.sample.id()) } as i64)?;
+        self.ended = true;
+        Ok(())
+    }
+    pub fn has_ended(&self) -> bool {
+        self.ended
+    }
+    /// never blocks
+    pub fn status(&self) -> Result<StreamStatus, GpuError> {
+        let (mut w, mut c, mut u, mut f) = (0u64, 0u64, 0u64, 0i32);
+        let _g = self.cx.control();
+        self.cx.check(unsafe { ffi::fwgpu_sample_stream_status(self.cx.as_ptr(), self.sample.id(), &mut w, &mut c, &mut u, &mut f) } as i64)?;
+        Ok(StreamStatus { written: w, consumed: c, starved_blocks: u, finished: f != 0 })
+    }
+}
+impl GpuSamplerNode {
+    /// bind a stream to this sampler — once per stream; seek and loop messages are refused while the sampler holds it
+    pub fn set_stream(&mut self, stream: &GpuStreamSource, stop_playback: bool) -> Result<(), ()> {
+        self.set_sample(stream.sample().clone(), stop_playback)
+    }
+}
 impl AudioNode for GpuSamplerNode {
     fn debug_name(&self) -> &'static str {
         "sampler"

@@ -66,6 +66,15 @@ impl GpuSample {
         Ok(Self(Arc::new(Inner { cx: Arc::clone(cx), id, graveyard: Arc::clone(graveyard) })))
     }
 
+    /// A stream's ring (SPEC streaming source): `ring_frames` zeroed frames the control side appends to while one
+    /// sampler plays them — see [`crate::nodes::GpuStreamSource`], which owns the handle and the calls that feed it.
+    pub(crate) fn create_stream(cx: &Arc<GpuContext>, graveyard: &Arc<Graveyard>, format: i32, channels: u32, ring_frames: u64) -> Result<Self, GpuError> {
+        let _g = cx.control();
+        let id = cx.check(unsafe { ffi::fwgpu_sample_create_stream(cx.as_ptr(), format, channels, ring_frames) } as i64)? as i32;
+        drop(_g);
+        Ok(Self(Arc::new(Inner { cx: Arc::clone(cx), id, graveyard: Arc::clone(graveyard) })))
+    }
+
     /// `InterleavedResourceI16` (core/sample_resource.rs:28-60)
     pub fn from_interleaved_i16(cx: &Arc<GpuContext>, g: &Arc<Graveyard>, r: &InterleavedResourceI16) -> Result<Self, GpuError> {
         Self::create(cx, g, ffi::FWGPU_INTERLEAVED_I16, r.channels.get() as u32, r.len_frames(), r.data.as_ptr().cast())
