@@ -171,13 +171,7 @@ int stream_put(fwgpu_ctx* c, const StreamRec& r, const void* src, uint64_t frame
 // one CMD_SMP_STREAM to the bound sampler, at_block 0: the new W and, with has_end, E
 int stream_tell(fwgpu_ctx* c, StreamRec& r, uint64_t W, bool has_end, uint64_t E) {
     if (r.node < 0 || r.detached) return 0;
-    Cmd m;
-    memset(&m, 0, sizeof(m));
-    m.type = CMD_SMP_STREAM;
-    m.i0 = has_end ? 1 : 0;
-    m.d0 = fw_double_of(W);
-    m.d1 = fw_double_of(E);
-    return push_cmd(c, r.node, K_SAMPLER, m, true);
+    return push_cmd(c, r.node, K_SAMPLER, make_smp_stream(W, has_end, E), true);
 }
 
 }  // namespace
@@ -554,7 +548,8 @@ int fwgpu_remove_node(fwgpu_ctx* c, int64_t node) {
         size_t w = 0;
         for (const Cmd& m : c->early_msgs) {
             if (m.state == (int)slot) {
-                if (m.type == CMD_SMP_SET_SAMPLE && m.i0 >= 0 && (size_t)m.i0 < c->sample_refs.size() && c->sample_refs[m.i0] > 0) c->sample_refs[m.i0]--;
+                const int smp = m.type == CMD_SMP_SET_SAMPLE ? smp_cmd_sample(m) : -1;
+                if (smp >= 0 && (size_t)smp < c->sample_refs.size() && c->sample_refs[smp] > 0) c->sample_refs[smp]--;
                 continue;
             }
             c->early_msgs[w++] = m;
@@ -1032,8 +1027,7 @@ int fwgpu_ext_pool_floats(fwgpu_ctx* c, uint64_t* in_use, uint64_t* capacity) {
     return 0;
 }
 
-// SPEC crossfader: one CMD_XF_TO — the target in f0, frames and shape in i0 / i1, the control values as float bits in
-// d0 = (x1, y1) and d1 = (x2, y2), packed as CMD_SET_COEFS packs (a1, a2)
+// SPEC crossfader: one CMD_XF_TO; position and x in 0..1, y in -1..2, at most 2^24 frames
 int fwgpu_crossfade_to(fwgpu_ctx* c, int64_t node, float position, uint32_t frames, int shape, float x1, float y1, float x2, float y2,
                        uint32_t at_block) {
     static_assert(FWGPU_CROSSFADE_FRAMES_MAX == XF_FRAMES_MAX && FWGPU_CROSSFADE_CH_MAX == XF_CH_MAX, "the header's crossfader caps");
@@ -1048,26 +1042,10 @@ int fwgpu_crossfade_to(fwgpu_ctx* c, int64_t node, float position, uint32_t fram
         return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: x1 and x2 must be in 0..1");
     if (!(y1 >= -1.0f && y1 <= 2.0f && y2 >= -1.0f && y2 <= 2.0f))
         return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: y1 and y2 must be in -1..2");
-    Cmd m;
-    memset(&m, 0, sizeof(m));
-    m.block = at_block;
-    m.type = CMD_XF_TO;
-    m.f0 = position;
-    m.i0 = (int)frames;
-    m.i1 = shape;
-    const float lo[2] = {x1, x2}, hi[2] = {y1, y2};
-    double* const d[2] = {&m.d0, &m.d1};
-    for (int k = 0; k < 2; ++k) {
-        uint32_t l, h;
-        memcpy(&l, &lo[k], 4);
-        memcpy(&h, &hi[k], 4);
-        const uint64_t u = ((uint64_t)h << 32) | l;
-        memcpy(d[k], &u, 8);
-    }
-    return push_cmd(c, node, K_CROSSFADE, m, false);
+    return push_cmd(c, node, K_CROSSFADE, make_xf_to(at_block, position, frames, shape, x1, y1, x2, y2), false);
 }
-// SPEC resampler ratio glide: one CMD_RS_GLIDE — the step to reach as u64 bits in d0 (param 1's resampler_step), the
-// frames to reach it over in i0.  frames == 0 is param 1's message, a step.
+// SPEC resampler ratio glide: one CMD_RS_GLIDE to param 1's resampler_step of the ratio; frames == 0 is param 1's
+// message, a step.  Any ratio but a NaN, at most 2^24 frames
 int fwgpu_resampler_glide(fwgpu_ctx* c, int64_t node, float ratio, uint32_t frames, uint32_t at_block) {
     static_assert(FWGPU_RESAMPLER_GLIDE_FRAMES_MAX == RS_GLIDE_FRAMES_MAX, "the header's glide cap");
     NEED_CTX(c, FWGPU_ERR_INVALID);
@@ -1076,102 +1054,51 @@ int fwgpu_resampler_glide(fwgpu_ctx* c, int64_t node, float ratio, uint32_t fram
     if (n->kind != K_RESAMPLER) return fail(c, FWGPU_ERR_INVALID, "fwgpu_resampler_glide: the node is not a resampling source");
     if (ratio != ratio) return fail(c, FWGPU_ERR_INVALID, "fwgpu_resampler_glide: ratio is NaN");
     if (frames > FWGPU_RESAMPLER_GLIDE_FRAMES_MAX) return fail(c, FWGPU_ERR_INVALID, "fwgpu_resampler_glide: at most 2^24 frames");
-    Cmd m;
-    memset(&m, 0, sizeof(m));
-    m.block = at_block;
-    m.type = frames ? CMD_RS_GLIDE : CMD_RS_STEP;
-    m.i0 = (int)frames;
-    const uint64_t u = resampler_step(ratio);
-    memcpy(&m.d0, &u, 8);
-    return push_cmd(c, node, -1, m, false);
+    return push_cmd(c, node, -1, make_rs_step(at_block, resampler_step(ratio), frames), false);
 }
 int fwgpu_node_set_param(fwgpu_ctx* c, int64_t node, int param, float value, uint32_t at_block) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
     HostNode* n = c->graph.get(node);
     if (!n) return fail(c, FWGPU_ERR_INVALID, "unknown node id");
-    Cmd m;
-    memset(&m, 0, sizeof(m));
-    m.block = at_block;
+    const auto push = [&](const Cmd& m) { return push_cmd(c, node, -1, m, false); };
     switch (n->kind) {
         case K_VOLUME:
         case K_SAMPLER:  // volume.rs:28-34, sampler.rs:171-177
             if (param != 0) return fail(c, FWGPU_ERR_INVALID, "unknown param");
-            m.type = CMD_SET_P0;
-            m.f0 = percent_volume_to_raw_gain(value);
-            return push_cmd(c, node, -1, m, false);
+            return push(make_set(CMD_SET_P0, at_block, percent_volume_to_raw_gain(value)));
         case K_BEEP:  // beep_test.rs:30-32
             if (param != 0) return fail(c, FWGPU_ERR_INVALID, "unknown param");
-            m.type = CMD_SET_ENABLED;
-            m.i0 = value != 0.0f;
-            return push_cmd(c, node, -1, m, false);
+            return push(make_set_enabled(at_block, value != 0.0f));
         case K_PAN: {
             if (param != 0) return fail(c, FWGPU_ERR_INVALID, "unknown param");
             float gl, gr;
             pan_to_gains(value, &gl, &gr);
-            m.type = CMD_SET_P0;
-            m.f0 = gl;
-            int rc = push_cmd(c, node, -1, m, false);
-            if (rc) return rc;
-            m.type = CMD_SET_P1;
-            m.f0 = gr;
-            return push_cmd(c, node, -1, m, false);
+            const int rc = push(make_set(CMD_SET_P0, at_block, gl));
+            return rc ? rc : push(make_set(CMD_SET_P1, at_block, gr));
         }
         case K_WIDTH:
             if (param != 0) return fail(c, FWGPU_ERR_INVALID, "unknown param");
-            m.type = CMD_SET_P0;
-            m.f0 = fmaxf(value, 0.0f);
-            return push_cmd(c, node, -1, m, false);
+            return push(make_set(CMD_SET_P0, at_block, fmaxf(value, 0.0f)));
         case K_BIQUAD: {  // param 1 = cutoff_hz, 2 = Q: recompute the coefficients on the control side
             if (param != 1 && param != 2) return fail(c, FWGPU_ERR_INVALID, "unknown param");
             if (param == 1) n->init.p0 = value;
             else n->init.p1 = value;
             float co[5];
             biquad_coefs(n->init.enabled, n->init.p0, n->init.p1, c->sample_rate, co);
-            m.type = CMD_SET_COEFS;
-            m.f0 = co[0];
-            memcpy(&m.i0, &co[1], 4);
-            memcpy(&m.i1, &co[2], 4);
-            uint32_t lo, hi;
-            memcpy(&lo, &co[3], 4);
-            memcpy(&hi, &co[4], 4);
-            uint64_t u = ((uint64_t)hi << 32) | lo;
-            memcpy(&m.d0, &u, 8);
-            return push_cmd(c, node, -1, m, false);
+            return push(make_bq_coefs(at_block, co, 0u));
         }
         case K_DELAY: {  // param 1 = feedback, 2 = mix (the delay time is fixed at construction)
-            if (param == 1) {
-                m.type = CMD_SET_P0;
-                m.f0 = fminf(fmaxf(value, 0.0f), 0.999f);
-                return push_cmd(c, node, -1, m, false);
-            }
+            if (param == 1) return push(make_set(CMD_SET_P0, at_block, fminf(fmaxf(value, 0.0f), 0.999f)));
             if (param != 2) return fail(c, FWGPU_ERR_INVALID, "unknown param");
-            float mix = fminf(fmaxf(value, 0.0f), 1.0f);
-            m.type = CMD_SET_P1;
-            m.f0 = mix;
-            int rc = push_cmd(c, node, -1, m, false);
-            if (rc) return rc;
-            m.type = CMD_SET_GAIN;
-            m.f0 = 1.0f - mix;
-            return push_cmd(c, node, -1, m, false);
+            const float mix = fminf(fmaxf(value, 0.0f), 1.0f);
+            const int rc = push(make_set(CMD_SET_P1, at_block, mix));
+            return rc ? rc : push(make_set(CMD_SET_GAIN, at_block, 1.0f - mix));
         }
-        case K_RESAMPLER: {  // 1 = ratio (source frames per output frame), 3 = playing, 4 = seek to a source frame
-            uint64_t u;
-            if (param == 1) {
-                m.type = CMD_RS_STEP;
-                u = resampler_step(value);
-                memcpy(&m.d0, &u, 8);
-                return push_cmd(c, node, -1, m, false);
-            }
-            if (param == 3) {
-                m.type = value != 0.0f ? CMD_SMP_PLAY : CMD_SMP_PAUSE;
-                return push_cmd(c, node, -1, m, false);
-            }
+        case K_RESAMPLER:  // 1 = ratio (source frames per output frame), 3 = playing, 4 = seek to a source frame
+            if (param == 1) return push(make_rs_step(at_block, resampler_step(value), 0u));
+            if (param == 3) return push(make_smp_transport(value != 0.0f ? CMD_SMP_PLAY : CMD_SMP_PAUSE, at_block));
             if (param != 4) return fail(c, FWGPU_ERR_INVALID, "unknown param");
-            m.type = CMD_RS_SEEK;
-            u = (uint64_t)fmaxf(value, 0.0f);
-            memcpy(&m.d0, &u, 8);
-            return push_cmd(c, node, -1, m, false);
-        }
+            return push(make_rs_seek(at_block, (uint64_t)fmaxf(value, 0.0f)));
         case K_SPATIAL: {  // 0 / 1 / 2 = x / y / z of the source relative to the listener
             if (param < 0 || param > 2) return fail(c, FWGPU_ERR_INVALID, "unknown param");
             if (param == 0) n->init.phasor = value;
@@ -1180,17 +1107,10 @@ int fwgpu_node_set_param(fwgpu_ctx* c, int64_t node, int param, float value, uin
             float gl, gr;
             int dl, dr;
             spatial_params(n->init.phasor, n->init.phasor_inc, n->init.gain, c->sample_rate, &gl, &gr, &dl, &dr);
-            m.type = CMD_SET_P0;
-            m.f0 = gl;
-            int rc = push_cmd(c, node, -1, m, false);
+            int rc = push(make_set(CMD_SET_P0, at_block, gl));
             if (rc) return rc;
-            m.type = CMD_SET_P1;
-            m.f0 = gr;
-            if ((rc = push_cmd(c, node, -1, m, false))) return rc;
-            m.type = CMD_SP_ITD;
-            m.i0 = dl;
-            m.i1 = dr;
-            return push_cmd(c, node, -1, m, false);
+            if ((rc = push(make_set(CMD_SET_P1, at_block, gr)))) return rc;
+            return push(make_sp_itd(at_block, gr, dl, dr));
         }
         case K_CROSSFADE:  // param 0 = position: a jump (fwgpu_crossfade_to with frames 0)
             if (param != 0) return fail(c, FWGPU_ERR_INVALID, "unknown param");
@@ -1205,8 +1125,8 @@ int fwgpu_node_set_param(fwgpu_ctx* c, int64_t node, int param, float value, uin
             return fail(c, FWGPU_ERR_INVALID, "node kind has no runtime params");
     }
 }
-// SPEC biquad coefficient sweep: one CMD_BQ_SWEEP — the target's five coefficients packed as param 1 / 2 pack them
-// into a CMD_SET_COEFS, the frames to reach them over in the low bits of d1.  frames == 0 is that message, a step.
+// SPEC biquad coefficient sweep: one CMD_BQ_SWEEP to the coefficients param 1 / 2 would set; frames == 0 is their
+// message, a step.  Any cutoff and Q but a NaN, at most 2^24 frames
 int fwgpu_biquad_sweep(fwgpu_ctx* c, int64_t node, float cutoff_hz, float q, uint32_t frames, uint32_t at_block) {
     static_assert(FWGPU_BIQUAD_SWEEP_FRAMES_MAX == BQ_SWEEP_FRAMES_MAX, "the header's sweep cap");
     NEED_CTX(c, FWGPU_ERR_INVALID);
@@ -1219,20 +1139,7 @@ int fwgpu_biquad_sweep(fwgpu_ctx* c, int64_t node, float cutoff_hz, float q, uin
     n->init.p1 = q;
     float co[5];
     biquad_coefs(n->init.enabled, cutoff_hz, q, c->sample_rate, co);
-    Cmd m;
-    memset(&m, 0, sizeof(m));
-    m.block = at_block;
-    m.type = frames ? CMD_BQ_SWEEP : CMD_SET_COEFS;
-    m.f0 = co[0];
-    memcpy(&m.i0, &co[1], 4);
-    memcpy(&m.i1, &co[2], 4);
-    uint32_t lo, hi;
-    memcpy(&lo, &co[3], 4);
-    memcpy(&hi, &co[4], 4);
-    const uint64_t u = ((uint64_t)hi << 32) | lo, f = (uint64_t)frames;
-    memcpy(&m.d0, &u, 8);
-    memcpy(&m.d1, &f, 8);
-    return push_cmd(c, node, -1, m, false);
+    return push_cmd(c, node, -1, make_bq_coefs(at_block, co, frames), false);
 }
 int fwgpu_node_set_params(fwgpu_ctx* c, uint32_t n, const int64_t* nodes, const int* params, const float* values, const uint32_t* at_blocks) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
@@ -1247,12 +1154,6 @@ int fwgpu_sampler_set_sample(fwgpu_ctx* c, int64_t node, int sample, int stop_pl
     NEED_CTX(c, FWGPU_ERR_INVALID);
     if (sample < 0 || sample >= (int)c->samples.size() || !c->samples[sample].alive)
         return fail(c, FWGPU_ERR_INVALID, "unknown sample id");
-    Cmd m;
-    memset(&m, 0, sizeof(m));
-    m.block = at_block;
-    m.type = CMD_SMP_SET_SAMPLE;
-    m.i0 = sample;
-    m.i1 = stop_playback != 0;
     // SPEC streaming source: a stream is bound once, to one sampler; the message carries R and the current W
     StreamRec* sr = stream_of(c, sample);
     HostNode* hn = c->graph.get(node);
@@ -1263,10 +1164,8 @@ int fwgpu_sampler_set_sample(fwgpu_ctx* c, int64_t node, int sample, int stop_pl
         for (int i = 0; i < fwgpu_ctx::STREAM_PUB_MAX && pub < 0; ++i)
             if (c->stream_pub_slot[i] < 0) pub = i;
         if (pub < 0) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_set_sample: too many samplers hold a stream (64)");
-        m.d0 = fw_double_of(sr->ring);
-        m.d1 = fw_double_of(sr->written);
     }
-    int rc = push_cmd(c, node, K_SAMPLER, m, true);
+    int rc = push_cmd(c, node, K_SAMPLER, make_smp_set_sample(at_block, sample, stop_playback != 0, sr ? sr->ring : 0, sr ? sr->written : 0), true);
     if (rc) return rc;
     c->sample_refs[sample]++;  // the message carries the reference (an Arc clone in the reference: sampler.rs:67-79)
     if (hn && hn->stream >= 0 && hn->stream < (int)c->streams.size()) stream_detach(c, c->streams[hn->stream]);  // the stream it held is finished
@@ -1288,19 +1187,11 @@ int fwgpu_sampler_set_sample(fwgpu_ctx* c, int64_t node, int sample, int stop_pl
     }
     return 0;
 }
-static int simple_msg(fwgpu_ctx* c, int64_t node, int type, uint32_t at_block) {
-    NEED_CTX(c, FWGPU_ERR_INVALID);
-    Cmd m;
-    memset(&m, 0, sizeof(m));
-    m.block = at_block;
-    m.type = type;
-    return push_cmd(c, node, K_SAMPLER, m, true);
-}
-int fwgpu_sampler_play(fwgpu_ctx* c, int64_t node, uint32_t b) { return simple_msg(c, node, CMD_SMP_PLAY, b); }
-int fwgpu_sampler_pause(fwgpu_ctx* c, int64_t node, uint32_t b) { return simple_msg(c, node, CMD_SMP_PAUSE, b); }
-int fwgpu_sampler_stop(fwgpu_ctx* c, int64_t node, uint32_t b) { return simple_msg(c, node, CMD_SMP_STOP, b); }
-// SPEC sampler gain envelope: one CMD_SMP_FADE — the target in f0, the frames to reach it over in i0, what the sampler
-// does at the fade's end in i1
+int fwgpu_sampler_play(fwgpu_ctx* c, int64_t node, uint32_t b) { return c ? push_cmd(c, node, K_SAMPLER, make_smp_transport(CMD_SMP_PLAY, b), true) : FWGPU_ERR_INVALID; }
+int fwgpu_sampler_pause(fwgpu_ctx* c, int64_t node, uint32_t b) { return c ? push_cmd(c, node, K_SAMPLER, make_smp_transport(CMD_SMP_PAUSE, b), true) : FWGPU_ERR_INVALID; }
+int fwgpu_sampler_stop(fwgpu_ctx* c, int64_t node, uint32_t b) { return c ? push_cmd(c, node, K_SAMPLER, make_smp_transport(CMD_SMP_STOP, b), true) : FWGPU_ERR_INVALID; }
+// SPEC sampler gain envelope: one CMD_SMP_FADE; a target in 0..1 (-0.0 counts as +0.0), at most 2^24 frames, a `then`
+// only behind a fade that has frames
 int fwgpu_sampler_fade(fwgpu_ctx* c, int64_t node, float target, uint32_t frames, int then, uint32_t at_block) {
     static_assert(FWGPU_SAMPLER_FADE_FRAMES_MAX == SMP_FADE_FRAMES_MAX, "the header's fade cap");
     static_assert(FWGPU_FADE_NONE == SMP_FADE_NONE && FWGPU_FADE_PAUSE == SMP_FADE_PAUSE && FWGPU_FADE_STOP == SMP_FADE_STOP, "the header's fade ends");
@@ -1313,39 +1204,20 @@ int fwgpu_sampler_fade(fwgpu_ctx* c, int64_t node, float target, uint32_t frames
     if (then < FWGPU_FADE_NONE || then > FWGPU_FADE_STOP) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_fade: then must be 0 (none), 1 (pause) or 2 (stop)");
     if (frames == 0 && then != FWGPU_FADE_NONE)
         return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_fade: a step (frames 0) has no end to pause or stop at: use fwgpu_sampler_pause / _stop");
-    Cmd m;
-    memset(&m, 0, sizeof(m));
-    m.block = at_block;
-    m.type = CMD_SMP_FADE;
-    m.f0 = target == 0.0f ? 0.0f : target;  // (-0.0 counts as +0.0)
-    m.i0 = (int)frames;
-    m.i1 = then;
-    return push_cmd(c, node, K_SAMPLER, m, true);
+    return push_cmd(c, node, K_SAMPLER, make_smp_fade(at_block, target == 0.0f ? 0.0f : target, frames, then), true);  // (-0.0 counts as +0.0)
 }
 int fwgpu_sampler_set_playhead_secs(fwgpu_ctx* c, int64_t node, double secs, uint32_t at_block) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
-    Cmd m;
-    memset(&m, 0, sizeof(m));
-    m.block = at_block;
     if (HostNode* hn = c->graph.get(node))
         if (hn->stream >= 0) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_set_playhead_secs: the sampler holds a stream: there is no position to seek to");
-    m.type = CMD_SMP_SET_PLAYHEAD;
-    m.d0 = secs;
-    return push_cmd(c, node, K_SAMPLER, m, true);
+    return push_cmd(c, node, K_SAMPLER, make_smp_set_playhead(at_block, secs), true);
 }
 int fwgpu_sampler_set_loop_range(fwgpu_ctx* c, int64_t node, int mode, double start, double end, uint32_t at_block) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
     if (mode < 0 || mode > 2) return fail(c, FWGPU_ERR_INVALID, "loop mode must be 0, 1 or 2");
-    Cmd m;
-    memset(&m, 0, sizeof(m));
-    m.block = at_block;
     if (HostNode* hn = c->graph.get(node))
         if (hn->stream >= 0) return fail(c, FWGPU_ERR_INVALID, "fwgpu_sampler_set_loop_range: the sampler holds a stream: there is no range to loop");
-    m.type = CMD_SMP_SET_LOOP;
-    m.i0 = mode;
-    m.d0 = start;
-    m.d1 = end;
-    return push_cmd(c, node, K_SAMPLER, m, true);
+    return push_cmd(c, node, K_SAMPLER, make_smp_set_loop(at_block, mode, start, end), true);
 }
 
 static int process_interleaved_impl(fwgpu_ctx* c, const float* input, float* output, uint32_t n_in_ch, uint32_t n_out_ch,

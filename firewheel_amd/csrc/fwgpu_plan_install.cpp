@@ -1283,7 +1283,7 @@ void adopt_image(fwgpu_ctx* c, PlanImage* n, bool on_audio_thread) {
             bool gone = false;
             for (uint32_t slot : n->removed_slots) gone = gone || m.state == (int)slot;
             if (gone) {
-                if (m.type == CMD_SMP_SET_SAMPLE && m.i0 >= 0) hand_back(m.i0);  // never reached its sampler: handed straight back
+                if (m.type == CMD_SMP_SET_SAMPLE && smp_cmd_sample(m) >= 0) hand_back(smp_cmd_sample(m));  // never reached its sampler: handed straight back
                 continue;
             }
             c->cmds[w++] = m;

@@ -166,7 +166,7 @@ int upload_cmds(fwgpu_ctx* c, bool drained) {
 static void note_set_sample(fwgpu_ctx* c, const Cmd& m) {
     if (m.type != CMD_SMP_SET_SAMPLE || m.state < 0 || (size_t)m.state >= c->cur_sample.size()) return;
     const int old = c->cur_sample[m.state];
-    c->cur_sample[m.state] = m.i0;
+    c->cur_sample[m.state] = smp_cmd_sample(m);
     if (old < 0) return;
     RetItem it;
     it.node = c->slot_ids[m.state];
@@ -422,7 +422,7 @@ static int run_host_level(fwgpu_ctx* c, const DevView& v, const std::vector<fwgp
 static void note_bq_sweeps(fwgpu_ctx* c) {
     for (const Cmd& m : c->cmds)
         if (m.type == CMD_BQ_SWEEP) {
-            const uint64_t end = c->frames_done + (uint64_t)m.block * c->mbf + (uint64_t)bq_cmd_frames(m.d1);
+            const uint64_t end = c->frames_done + (uint64_t)m.block * c->mbf + (uint64_t)bq_cmd_frames(m);
             if (end > c->bq_sweep_until) c->bq_sweep_until = end;
         }
     c->bq_sweep_live = c->frames_done < c->bq_sweep_until;

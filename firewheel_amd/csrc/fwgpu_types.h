@@ -21,6 +21,15 @@ enum : int {
 #else
 #define FW_TYPES_HD  // (the test harnesses compile the host translation units with plain g++)
 #endif
+// Raw bits in a field of another type — how integers travel in NodeState's float slots and in a message's doubles (the Cmd makers
+// and readers below).  A pair of floats in a double: `lo` in bits 0..31, `hi` in bits 32..63.
+FW_TYPES_HD constexpr uint32_t fw_bits_of(float f) { return __builtin_bit_cast(uint32_t, f); }
+FW_TYPES_HD constexpr float fw_float_of(uint32_t u) { return __builtin_bit_cast(float, u); }
+FW_TYPES_HD constexpr uint64_t fw_bits_of64(double d) { return __builtin_bit_cast(uint64_t, d); }
+FW_TYPES_HD constexpr double fw_double_of(uint64_t u) { return __builtin_bit_cast(double, u); }
+FW_TYPES_HD constexpr double fw_double_of2(float lo, float hi) { return fw_double_of((uint64_t)fw_bits_of(lo) | ((uint64_t)fw_bits_of(hi) << 32)); }
+FW_TYPES_HD constexpr float fw_lo_float_of(double d) { return fw_float_of((uint32_t)fw_bits_of64(d)); }
+FW_TYPES_HD constexpr float fw_hi_float_of(double d) { return fw_float_of((uint32_t)(fw_bits_of64(d) >> 32)); }
 // Which kernel runs a kind.  The node kernel k_level exists in three instantiations, by register appetite: one kernel for every kind
 // needed 248 VGPRs (2 waves per SIMD — nothing to hide HBM latency behind, 0.9 TB/s on a level of volume nodes).  Set 0: the streaming
 // kinds (volume, pan, sum, hard clip, mono<->stereo, width: 127 VGPRs), set 1: serial recurrences / filter banks / libm (beep, biquad,
@@ -309,26 +318,6 @@ FW_TYPES_HD inline void smp_env_start(NodeState& s, float target, uint32_t frame
 #define SMP_STREAM_FINISHED 4u
 #define SMP_STREAM_RING_MAX (1ull << 30)
 #define SMP_STREAM_RING_MIN_BLOCKS 4u
-FW_TYPES_HD inline uint32_t fw_bits_of(float f) {
-    uint32_t u;
-    __builtin_memcpy(&u, &f, 4);
-    return u;
-}
-FW_TYPES_HD inline float fw_float_of(uint32_t u) {
-    float f;
-    __builtin_memcpy(&f, &u, 4);
-    return f;
-}
-FW_TYPES_HD inline uint64_t fw_bits_of64(double d) {
-    uint64_t u;
-    __builtin_memcpy(&u, &d, 8);
-    return u;
-}
-FW_TYPES_HD inline double fw_double_of(uint64_t u) {
-    double d;
-    __builtin_memcpy(&d, &u, 8);
-    return d;
-}
 struct SmpStream {
     uint64_t W, C, E;
     uint32_t U, flags;
@@ -534,22 +523,6 @@ FW_TYPES_HD inline bool bq_sweep_advance(BqSweep& w, uint32_t frames) {
     w.N = w.k = 0u;
     return true;
 }
-// the five coefficients of a CMD_SET_COEFS / CMD_BQ_SWEEP message (f0, i0, i1 = b0, b1, b2; d0 bits = a1 | a2 << 32)
-FW_TYPES_HD inline void bq_cmd_coefs(float f0, int i0, int i1, double d0, float co[5]) {
-    union { double d; uint64_t u; } p;
-    union { uint32_t u; float f; } q;
-    p.d = d0;
-    co[0] = f0;
-    q.u = (uint32_t)i0, co[1] = q.f;
-    q.u = (uint32_t)i1, co[2] = q.f;
-    q.u = (uint32_t)(p.u & 0xffffffffull), co[3] = q.f;
-    q.u = (uint32_t)(p.u >> 32), co[4] = q.f;
-}
-FW_TYPES_HD inline uint32_t bq_cmd_frames(double d1) {  // CMD_BQ_SWEEP: frames in the low bits of d1
-    union { double d; uint64_t u; } p;
-    p.d = d1;
-    return (uint32_t)(p.u & 0xffffffffull);
-}
 
 // K_CROSSFADE (rendered by k_level<0>, no ext slice): the states its case renders.  T never runs behind t0: a message sets t0 = T
 FW_TYPES_HD inline bool xf_state_ok(const NodeState& s, int n_in, int n_out) {
@@ -581,20 +554,21 @@ struct NodeDesc {
 };
 
 // control -> audio messages (nodes/sampler.rs:21-28 + the atomics), sorted by (state, block, seq).
+// What a type carries in i0 / f0 / i1 / d0 / d1 is stated ONCE, by its maker below the struct (make_*); nothing else writes those
+// fields, and what is not a single plain field is read through the reader beside the maker.
 enum : int {
     CMD_SET_P0 = 0, CMD_SET_P1 = 1, CMD_SET_ENABLED = 2, CMD_SET_GAIN = 3,
-    CMD_SET_COEFS = 4,  // biquad: f0,i0,i1 (as float bits) = b0,b1,b2; d0 bits = (a1,a2)
+    CMD_SET_COEFS = 4,
     CMD_SMP_SET_SAMPLE = 10, CMD_SMP_PLAY = 11, CMD_SMP_PAUSE = 12, CMD_SMP_STOP = 13,
     CMD_SMP_SET_PLAYHEAD = 14, CMD_SMP_SET_LOOP = 15,
-    CMD_SMP_FADE = 16,  // sampler: f0 = target gain (0..1), i0 = frames to reach it over, i1 = then (SMP_FADE_*) (smp_env_start)
-    CMD_SMP_STREAM = 17,  // sampler on a stream: d0 bits = W, the frames written so far; i0 != 0: the stream has ended, d1 bits = E (smp_stream_msg);
-                          // CMD_SMP_SET_SAMPLE of a stream carries d0 bits = R, the ring's frames, and d1 bits = W (smp_stream_bind)
-    CMD_RS_STEP = 20,  // resampler: d0 bits = u64 32.32 step
-    CMD_RS_SEEK = 21,  // resampler: d0 bits = u64 source frame
-    CMD_SP_ITD = 22,   // spatialiser: i0 / i1 = left / right ear delay in frames
-    CMD_XF_TO = 23,    // crossfader: f0 = target position, i0 = frames, i1 = shape; d0 bits = (x1, y1), d1 bits = (x2, y2) as float bits
-    CMD_RS_GLIDE = 24,  // resampler: d0 bits = u64 32.32 step to reach, i0 = frames to reach it over (rs_glide_start)
-    CMD_BQ_SWEEP = 25,  // biquad: the target coefficients packed as CMD_SET_COEFS packs them, d1 bits = frames to reach them over (bq_sweep_start)
+    CMD_SMP_FADE = 16,
+    CMD_SMP_STREAM = 17,
+    CMD_RS_STEP = 20,
+    CMD_RS_SEEK = 21,
+    CMD_SP_ITD = 22,
+    CMD_XF_TO = 23,
+    CMD_RS_GLIDE = 24,
+    CMD_BQ_SWEEP = 25,
 };
 struct Cmd {
     int state;
@@ -606,6 +580,186 @@ struct Cmd {
     double d0, d1;
 };
 static_assert(sizeof(Cmd) == 40, "Cmd layout");
+// ---- the wire format: one maker per message type, one reader per payload that is not a single plain field.  A maker returns the
+// whole message but `state`, which push_cmd fills in (the struct has no padding: Cmd{} leaves every bit it does not set 0).
+// The readers are macros over a Cmd lvalue `c`, not functions: a kernel's loop holds its message in a local copy, and a copy whose
+// address goes to a function is split into scalars only after inlining — the control kernel then came out with 32 more bytes of
+// scratch per lane and 1.3 % slower under a sweep.  As macros they are the field reads they replace, for the compiler too.
+FW_TYPES_HD constexpr Cmd make_cmd(int type, uint32_t block) {
+    Cmd m{};
+    m.type = type;
+    m.block = block;
+    return m;
+}
+// CMD_SET_P0 / _P1 / _GAIN: f0 = the value
+FW_TYPES_HD constexpr Cmd make_set(int type, uint32_t block, float value) {
+    Cmd m = make_cmd(type, block);
+    m.f0 = value;
+    return m;
+}
+// CMD_SET_ENABLED: i0 = 0 / 1
+FW_TYPES_HD constexpr Cmd make_set_enabled(uint32_t block, bool on) {
+    Cmd m = make_cmd(CMD_SET_ENABLED, block);
+    m.i0 = on ? 1 : 0;
+    return m;
+}
+// CMD_SET_COEFS (frames == 0) / CMD_BQ_SWEEP (bq_sweep_start), biquad: b0 in f0, b1 and b2 as float bits in i0 and i1, (a1, a2) as
+// a pair in d0, d1 bits = the frames to reach them over
+FW_TYPES_HD constexpr Cmd make_bq_coefs(uint32_t block, const float co[5], uint32_t frames) {
+    Cmd m = make_cmd(frames ? CMD_BQ_SWEEP : CMD_SET_COEFS, block);
+    m.f0 = co[0];
+    m.i0 = (int)fw_bits_of(co[1]);
+    m.i1 = (int)fw_bits_of(co[2]);
+    m.d0 = fw_double_of2(co[3], co[4]);
+    m.d1 = fw_double_of((uint64_t)frames);
+    return m;
+}
+FW_TYPES_HD constexpr void bq_coefs_of_fields(float f0, int i0, int i1, double d0, float co[5]) {
+    co[0] = f0;
+    co[1] = fw_float_of((uint32_t)i0);
+    co[2] = fw_float_of((uint32_t)i1);
+    co[3] = fw_lo_float_of(d0);
+    co[4] = fw_hi_float_of(d0);
+}
+#define bq_cmd_coefs(c, co) fwgpu::bq_coefs_of_fields((c).f0, (c).i0, (c).i1, (c).d0, (co))
+#define bq_cmd_frames(c) ((uint32_t)fwgpu::fw_bits_of64((c).d1))
+// CMD_SMP_SET_SAMPLE: i0 = the sample id, i1 = stop_playback; of a stream (smp_stream_bind), d0 bits = R, the ring's frames (0: no
+// stream), d1 bits = W, the frames written so far
+FW_TYPES_HD constexpr Cmd make_smp_set_sample(uint32_t block, int sample, bool stop, uint64_t R, uint64_t W) {
+    Cmd m = make_cmd(CMD_SMP_SET_SAMPLE, block);
+    m.i0 = sample;
+    m.i1 = stop ? 1 : 0;
+    m.d0 = fw_double_of(R);
+    m.d1 = fw_double_of(W);
+    return m;
+}
+#define smp_cmd_sample(c) ((c).i0)
+#define smp_cmd_stop(c) ((c).i1 != 0)
+#define smp_cmd_ring(c) (fwgpu::fw_bits_of64((c).d0))
+#define smp_cmd_written(c) (fwgpu::fw_bits_of64((c).d1))
+// CMD_SMP_PLAY / _PAUSE / _STOP (a resampling source takes play and pause too): no payload
+FW_TYPES_HD constexpr Cmd make_smp_transport(int type, uint32_t block) { return make_cmd(type, block); }
+// CMD_SMP_FADE (smp_env_start): f0 = the target gain (0..1), i0 = the frames to reach it over, i1 = then (SMP_FADE_*)
+FW_TYPES_HD constexpr Cmd make_smp_fade(uint32_t block, float target, uint32_t frames, int then) {
+    Cmd m = make_cmd(CMD_SMP_FADE, block);
+    m.f0 = target;
+    m.i0 = (int)frames;
+    m.i1 = then;
+    return m;
+}
+// CMD_SMP_STREAM (smp_stream_msg), always at block 0: d0 bits = W, the frames written so far; i0 != 0: the stream has ended, d1
+// bits = E, its end
+FW_TYPES_HD constexpr Cmd make_smp_stream(uint64_t W, bool has_end, uint64_t E) {
+    Cmd m = make_cmd(CMD_SMP_STREAM, 0u);
+    m.i0 = has_end ? 1 : 0;
+    m.d0 = fw_double_of(W);
+    m.d1 = fw_double_of(E);
+    return m;
+}
+#define smp_cmd_stream_written(c) (fwgpu::fw_bits_of64((c).d0))
+#define smp_cmd_stream_has_end(c) ((c).i0)
+#define smp_cmd_stream_end(c) (fwgpu::fw_bits_of64((c).d1))
+// CMD_SMP_SET_PLAYHEAD: d0 = seconds
+FW_TYPES_HD constexpr Cmd make_smp_set_playhead(uint32_t block, double secs) {
+    Cmd m = make_cmd(CMD_SMP_SET_PLAYHEAD, block);
+    m.d0 = secs;
+    return m;
+}
+#define smp_cmd_playhead_secs(c) ((c).d0)
+// CMD_SMP_SET_LOOP: i0 = mode (0 off, 1 the whole sample, 2 a range), d0 / d1 = the range's start / end in seconds
+FW_TYPES_HD constexpr Cmd make_smp_set_loop(uint32_t block, int mode, double start, double end) {
+    Cmd m = make_cmd(CMD_SMP_SET_LOOP, block);
+    m.i0 = mode;
+    m.d0 = start;
+    m.d1 = end;
+    return m;
+}
+#define smp_cmd_loop_start_secs(c) ((c).d0)
+#define smp_cmd_loop_end_secs(c) ((c).d1)
+// CMD_RS_STEP (frames == 0) / CMD_RS_GLIDE (rs_glide_start), resampler: d0 bits = the u64 32.32 step, i0 = the frames to reach it over
+FW_TYPES_HD constexpr Cmd make_rs_step(uint32_t block, uint64_t step, uint32_t frames) {
+    Cmd m = make_cmd(frames ? CMD_RS_GLIDE : CMD_RS_STEP, block);
+    m.i0 = (int)frames;
+    m.d0 = fw_double_of(step);
+    return m;
+}
+#define rs_cmd_step(c) (fwgpu::fw_bits_of64((c).d0))
+// CMD_RS_SEEK, resampler: d0 bits = the u64 source frame
+FW_TYPES_HD constexpr Cmd make_rs_seek(uint32_t block, uint64_t frame) {
+    Cmd m = make_cmd(CMD_RS_SEEK, block);
+    m.d0 = fw_double_of(frame);
+    return m;
+}
+#define rs_cmd_frame(c) (fwgpu::fw_bits_of64((c).d0))
+// CMD_SP_ITD, spatialiser: i0 / i1 = the left / right ear's delay in frames.  f0 = the right ear's gain, which the CMD_SET_P1 in front
+// of it delivers: nothing reads it here — the first encoder left it in the record, and the wire pin (tests/test_cmd_wire.py) keeps it
+FW_TYPES_HD constexpr Cmd make_sp_itd(uint32_t block, float gr, int dl, int dr) {
+    Cmd m = make_cmd(CMD_SP_ITD, block);
+    m.f0 = gr;
+    m.i0 = dl;
+    m.i1 = dr;
+    return m;
+}
+// CMD_XF_TO, crossfader: f0 = the target position, i0 = frames, i1 = shape (XF_SHAPE_*), the Bezier's control values as pairs:
+// (x1, y1) in d0, (x2, y2) in d1
+FW_TYPES_HD constexpr Cmd make_xf_to(uint32_t block, float position, uint32_t frames, int shape, float x1, float y1, float x2, float y2) {
+    Cmd m = make_cmd(CMD_XF_TO, block);
+    m.f0 = position;
+    m.i0 = (int)frames;
+    m.i1 = shape;
+    m.d0 = fw_double_of2(x1, y1);
+    m.d1 = fw_double_of2(x2, y2);
+    return m;
+}
+#define xf_cmd_x1(c) (fwgpu::fw_lo_float_of((c).d0))
+#define xf_cmd_y1(c) (fwgpu::fw_hi_float_of((c).d0))
+#define xf_cmd_x2(c) (fwgpu::fw_lo_float_of((c).d1))
+#define xf_cmd_y2(c) (fwgpu::fw_hi_float_of((c).d1))
+// Round trips, maker to reader, in every build: payload bits that read as a NaN or an infinity when viewed as a double or a float
+// (0x7ff0000000000001 is a signalling NaN, 0x7fa00001 too) and -0.0f come back as they went in.
+namespace wire_check {
+constexpr uint64_t SNAN64 = 0x7ff0000000000001ull, INF64 = 0x7ff0000000000000ull, ALL64 = ~0ull;
+constexpr uint32_t SNAN32 = 0x7fa00001u, NEG0 = 0x80000000u;
+constexpr bool bq(uint32_t b0, uint32_t b1, uint32_t b2, uint32_t a1, uint32_t a2, uint32_t frames) {
+    const float co[5] = {fw_float_of(b0), fw_float_of(b1), fw_float_of(b2), fw_float_of(a1), fw_float_of(a2)};
+    const Cmd m = make_bq_coefs(7u, co, frames);
+    float r[5] = {};
+    bq_cmd_coefs(m, r);
+    return m.type == (frames ? CMD_BQ_SWEEP : CMD_SET_COEFS) && m.block == 7u && m.state == 0 && bq_cmd_frames(m) == frames &&
+           fw_bits_of(r[0]) == b0 && fw_bits_of(r[1]) == b1 && fw_bits_of(r[2]) == b2 && fw_bits_of(r[3]) == a1 && fw_bits_of(r[4]) == a2;
+}
+static_assert(bq(NEG0, SNAN32, 0x3f800000u, 0xffffffffu, NEG0, 0u) && bq(SNAN32, NEG0, NEG0, 0x7ff00000u, 0x00000001u, 16777216u) &&
+              bq(0u, 0u, 0u, 0x00000001u, 0x7ff00000u, 0xffffffffu), "CMD_SET_COEFS / CMD_BQ_SWEEP");
+constexpr bool set_sample(int sample, bool stop, uint64_t R, uint64_t W) {
+    const Cmd m = make_smp_set_sample(3u, sample, stop, R, W);
+    return m.type == CMD_SMP_SET_SAMPLE && smp_cmd_sample(m) == sample && smp_cmd_stop(m) == stop && smp_cmd_ring(m) == R && smp_cmd_written(m) == W;
+}
+static_assert(set_sample(5, true, SNAN64, INF64) && set_sample(-1, false, 0ull, ALL64) && set_sample(0x7fffffff, true, 1ull << 33, (1ull << 40) + 1ull),
+              "CMD_SMP_SET_SAMPLE");
+constexpr bool stream(uint64_t W, bool has_end, uint64_t E) {
+    const Cmd m = make_smp_stream(W, has_end, E);
+    return m.type == CMD_SMP_STREAM && m.block == 0u && smp_cmd_stream_written(m) == W && (smp_cmd_stream_has_end(m) != 0) == has_end &&
+           smp_cmd_stream_end(m) == E;
+}
+static_assert(stream(SNAN64, true, INF64) && stream(ALL64, false, 0ull) && stream((1ull << 32) + 170ull, true, SNAN64), "CMD_SMP_STREAM");
+constexpr bool seconds(double a, double b) {
+    const Cmd p = make_smp_set_playhead(1u, a), l = make_smp_set_loop(2u, 2, a, b);
+    return fw_bits_of64(smp_cmd_playhead_secs(p)) == fw_bits_of64(a) && l.i0 == 2 && fw_bits_of64(smp_cmd_loop_start_secs(l)) == fw_bits_of64(a) &&
+           fw_bits_of64(smp_cmd_loop_end_secs(l)) == fw_bits_of64(b);
+}
+static_assert(seconds(-0.0, 1.75) && seconds(fw_double_of(INF64), fw_double_of(SNAN64)), "CMD_SMP_SET_PLAYHEAD / CMD_SMP_SET_LOOP");
+constexpr bool rs(uint64_t u, uint32_t frames) {
+    const Cmd m = make_rs_step(9u, u, frames), k = make_rs_seek(9u, u);
+    return m.type == (frames ? CMD_RS_GLIDE : CMD_RS_STEP) && (uint32_t)m.i0 == frames && rs_cmd_step(m) == u && k.type == CMD_RS_SEEK && rs_cmd_frame(k) == u;
+}
+static_assert(rs(SNAN64, 0u) && rs(INF64, 16777216u) && rs(ALL64, 1u) && rs(1ull << 40, 0u), "CMD_RS_STEP / CMD_RS_GLIDE / CMD_RS_SEEK");
+constexpr bool xf(uint32_t x1, uint32_t y1, uint32_t x2, uint32_t y2) {
+    const Cmd m = make_xf_to(4u, 0.25f, 16777216u, XF_SHAPE_BEZIER, fw_float_of(x1), fw_float_of(y1), fw_float_of(x2), fw_float_of(y2));
+    return m.type == CMD_XF_TO && m.f0 == 0.25f && m.i0 == 16777216 && m.i1 == XF_SHAPE_BEZIER && fw_bits_of(xf_cmd_x1(m)) == x1 &&
+           fw_bits_of(xf_cmd_y1(m)) == y1 && fw_bits_of(xf_cmd_x2(m)) == x2 && fw_bits_of(xf_cmd_y2(m)) == y2;
+}
+static_assert(xf(NEG0, SNAN32, 0x3f800000u, 0x7ff00000u) && xf(0x7ff00000u, 0x00000001u, SNAN32, NEG0), "CMD_XF_TO");
+}  // namespace wire_check
 
 // ---------------------------------------------------------------- fused voice-bank plan
 #define FW_MAX_STAGES 6    // sampler gain + up to 5 chain nodes (volume / pan / width / hard clip) in any order

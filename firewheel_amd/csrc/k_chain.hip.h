@@ -147,12 +147,12 @@ __device__ __forceinline__ void chain_sweep_block(ChSweep& z, const Cmd* cmds, i
         const Cmd c = cmds[i];
         if (c.state != bqs || c.block != block) break;
         if (c.type == CMD_SET_COEFS) {
-            bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, z.hd);
+            bq_cmd_coefs(c, z.hd);
             bq_sweep_stop(z.w);
         } else if (c.type == CMD_BQ_SWEEP) {
             float T[5];
-            bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, T);
-            if (bq_sweep_start(z.w, z.hd, T, bq_cmd_frames(c.d1))) {
+            bq_cmd_coefs(c, T);
+            if (bq_sweep_start(z.w, z.hd, T, bq_cmd_frames(c))) {
 #pragma unroll
                 for (int j = 0; j < 5; ++j) z.hd[j] = T[j];
             }

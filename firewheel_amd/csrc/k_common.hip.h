@@ -201,17 +201,9 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
             case CMD_SET_ENABLED: s.enabled = c.i0; break;
             case CMD_SET_GAIN: s.gain = c.f0; break;
             case CMD_SET_COEFS:  // biquad coefficients live at the head of the node's ext slice
-                if (ext && ext_write) {
-                    float* co = ext + s.ext_off;
-                    co[0] = c.f0;
-                    co[1] = __int_as_float(c.i0);
-                    co[2] = __int_as_float(c.i1);
-                    unsigned long long u = (unsigned long long)__double_as_longlong(c.d0);
-                    co[3] = __int_as_float((int)(u & 0xffffffffull));
-                    co[4] = __int_as_float((int)(u >> 32));
-                }
+                if (ext && ext_write) bq_cmd_coefs(c, ext + s.ext_off);
                 if constexpr (BQ) {  // (a sweep in flight ends here: the node is at rest at the message's five)
-                    bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, bq_head);
+                    bq_cmd_coefs(c, bq_head);
                     bq_head_known = true;
                     s.s0.status = 0;
                     s.s1.status = 0;
@@ -227,9 +219,9 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                             bq_head_known = true;
                         }
                         float T[5];
-                        bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, T);
+                        bq_cmd_coefs(c, T);
                         BqSweep w = bq_sweep_of(s);
-                        if (bq_sweep_start(w, bq_head, T, bq_cmd_frames(c.d1))) {  // (a step: the target is the head)
+                        if (bq_sweep_start(w, bq_head, T, bq_cmd_frames(c))) {  // (a step: the target is the head)
 #pragma unroll
                             for (int j = 0; j < 5; ++j) bq_head[j] = T[j];
                             if (ext_write) {
@@ -242,11 +234,11 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                 }
                 break;
             case CMD_SMP_SET_SAMPLE:  // sampler.rs:333-364
-                s.sample = c.i0;
-                if constexpr (SMP) {  // SPEC streaming source: d0 bits = the ring's frames R (0: no stream), d1 bits = W
+                s.sample = smp_cmd_sample(c);
+                if constexpr (SMP) {  // SPEC streaming source: the ring's frames R (0: no stream) and W
                     if (smp_env) {
-                        const uint64_t R = (uint64_t)__double_as_longlong(c.d0);
-                        if (R) smp_stream_bind(s, R, (uint64_t)__double_as_longlong(c.d1));
+                        const uint64_t R = smp_cmd_ring(c);
+                        if (R) smp_stream_bind(s, R, smp_cmd_written(c));
                         else if (smp_stream_on(s)) smp_stream_unbind(s);
                     }
                 }
@@ -254,7 +246,7 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                     s.loop_start = 0;
                     s.loop_end = samples[s.sample].frames;
                 }
-                if (c.i1) {  // stop_playback
+                if (smp_cmd_stop(c)) {
                     s.playhead = s.has_loop ? s.loop_start : 0;
                     s.playing = 0;
                     if (SMP && smp_env) smp_env_reset(s);
@@ -277,21 +269,21 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                     if (smp_env) smp_env_start(s, c.f0, (uint32_t)c.i0, c.i1);
                 }
                 break;
-            case CMD_SMP_STREAM:  // SPEC streaming source: d0 bits = W, i0 = an end follows, d1 bits = E (smp_stream_msg)
+            case CMD_SMP_STREAM:  // SPEC streaming source (smp_stream_msg)
                 if constexpr (SMP) {
-                    if (smp_env) smp_stream_msg(s, (uint64_t)__double_as_longlong(c.d0), c.i0, (uint64_t)__double_as_longlong(c.d1));
+                    if (smp_env) smp_stream_msg(s, smp_cmd_stream_written(c), smp_cmd_stream_has_end(c), smp_cmd_stream_end(c));
                 }
                 break;
             case CMD_SMP_SET_PLAYHEAD:  // :392-399 (ignored on a stream, like CMD_SMP_SET_LOOP: nothing to seek to, no range to loop)
                 if (SMP && smp_env && smp_stream_on(s)) break;
-                s.playhead = sat_round_u64(c.d0 * (double)s.sample_rate);
+                s.playhead = sat_round_u64(smp_cmd_playhead_secs(c) * (double)s.sample_rate);
                 break;
             case CMD_RS_STEP:  // (a step ends a glide in flight)
-                s.loop_start = (uint64_t)__double_as_longlong(c.d0);
+                s.loop_start = rs_cmd_step(c);
                 s.full_range = 0;
                 break;
-            case CMD_RS_GLIDE: rs_glide_start(s, (uint64_t)__double_as_longlong(c.d0), (uint32_t)c.i0); break;
-            case CMD_RS_SEEK: s.playhead = ((uint64_t)__double_as_longlong(c.d0)) << 32; break;
+            case CMD_RS_GLIDE: rs_glide_start(s, rs_cmd_step(c), (uint32_t)c.i0); break;
+            case CMD_RS_SEEK: s.playhead = rs_cmd_frame(c) << 32; break;
             case CMD_SP_ITD:
                 s.playing = c.i0;
                 s.has_loop = c.i1;
@@ -304,11 +296,10 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                 s.loop_start = s.playhead;
                 s.full_range = c.i0;
                 s.has_loop = c.i1;
-                const unsigned long long u0 = (unsigned long long)__double_as_longlong(c.d0), u1 = (unsigned long long)__double_as_longlong(c.d1);
-                s.phasor = __int_as_float((int)(u0 & 0xffffffffull));
-                s.phasor_inc = __int_as_float((int)(u0 >> 32));
-                s.gain = __int_as_float((int)(u1 & 0xffffffffull));
-                s.aux = __int_as_float((int)(u1 >> 32));
+                s.phasor = xf_cmd_x1(c);
+                s.phasor_inc = xf_cmd_y1(c);
+                s.gain = xf_cmd_x2(c);
+                s.aux = xf_cmd_y2(c);
             }
                 break;  // (compiled out: the message is ignored, it does not fall through)
             case CMD_SMP_SET_LOOP:  // :400-412 + ProcLoopRange::new :241-263
@@ -322,8 +313,8 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                         s.loop_end = s.sample >= 0 ? samples[s.sample].frames : 0;
                         s.full_range = 1;
                     } else {
-                        s.loop_start = sat_round_u64(c.d0 * (double)s.sample_rate);
-                        s.loop_end = sat_round_u64(c.d1 * (double)s.sample_rate);
+                        s.loop_start = sat_round_u64(smp_cmd_loop_start_secs(c) * (double)s.sample_rate);
+                        s.loop_end = sat_round_u64(smp_cmd_loop_end_secs(c) * (double)s.sample_rate);
                         s.full_range = 0;
                     }
                     if (s.playhead >= s.loop_start && s.playhead < s.loop_end) s.playhead = s.loop_start;  // Q7

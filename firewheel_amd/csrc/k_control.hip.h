@@ -18,12 +18,9 @@ __device__ __forceinline__ ChainCoefs chain_find_coefs(const Cmd* cmds, int n_cm
         const Cmd c = cmds[i];
         if (c.state != state_idx || c.block != block) break;
         if (c.type != CMD_SET_COEFS) continue;
-        r.b0 = c.f0;
-        r.b1 = __int_as_float(c.i0);
-        r.b2 = __int_as_float(c.i1);
-        unsigned long long u = (unsigned long long)__double_as_longlong(c.d0);
-        r.a1 = __int_as_float((int)(u & 0xffffffffull));
-        r.a2 = __int_as_float((int)(u >> 32));
+        float co[5];
+        bq_cmd_coefs(c, co);
+        r.b0 = co[0], r.b1 = co[1], r.b2 = co[2], r.a1 = co[3], r.a2 = co[4];
         r.found = true;
     }
     return r;
@@ -902,13 +899,13 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
                         break;
                     }
                     if (c.type == CMD_SET_COEFS) {
-                        bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, head);
+                        bq_cmd_coefs(c, head);
                         bq_sweep_stop(sw);
                         head_new = moved = true;
                     } else if (c.type == CMD_BQ_SWEEP) {
                         float T[5];
-                        bq_cmd_coefs(c.f0, c.i0, c.i1, c.d0, T);
-                        if (bq_sweep_start(sw, head, T, bq_cmd_frames(c.d1))) {
+                        bq_cmd_coefs(c, T);
+                        if (bq_sweep_start(sw, head, T, bq_cmd_frames(c))) {
 #pragma unroll
                             for (int j = 0; j < 5; ++j) head[j] = T[j];
                             head_new = true;

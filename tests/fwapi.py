@@ -655,6 +655,39 @@ def hostonly_lib():
     return _hostonly_lib
 
 
+def peek_lib(name, argtypes=()):
+    """tests/host_harness/<name>.cpp, a companion of the harness library built beside it with its include paths and flags: the messages
+    a ctx keeps for nodes no plan holds yet (early_peek.h: fwp_early_count / fwp_early_msg / fwp_layout_check) and whatever the
+    companion adds — `argtypes` = {function: (restype, [argtypes])}"""
+    d = os.path.join(ROOT, "tests", "host_harness")
+    csrc = os.path.join(ROOT, "firewheel_amd", "csrc")
+    src, so = os.path.join(d, name + ".cpp"), os.path.join(d, "_" + name + ".so")
+    deps = [src, os.path.join(d, "early_peek.h"), os.path.join(ROOT, "include", "fwgpu.h")] + [
+        os.path.join(csrc, h) for h in ("fwgpu_ctx.h", "fwgpu_types.h", "fwgpu_graph.h", "fwgpu_launch.h", "fwgpu_msgq.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(x) > os.path.getmtime(so) for x in deps):
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-Wall", "-Wno-unused-function", "-I",
+                               os.path.join(d, "fakehip"), "-I", os.path.join(ROOT, "include"), "-o", so, src])
+    P = C.CDLL(so)
+    table = {"fwp_early_count": (C.c_uint, [C.c_void_p]), "fwp_early_msg": (C.c_int, [C.c_void_p, C.c_uint, C.POINTER(C.c_uint)]),
+             "fwp_layout_check": (C.c_int, [C.c_void_p] + [C.c_uint] * 5)}
+    table.update(argtypes)
+    for fn, (res, args) in table.items():
+        f = getattr(P, fn)
+        f.restype, f.argtypes = res, args
+    return P
+
+
+def early_msgs(P, c):
+    """the messages waiting for their node's first plan, each as nine words: (type, block, f0 bits, i0, i1, d0 low, d0 high, d1 low,
+    d1 high)"""
+    out = []
+    for i in range(P.fwp_early_count(c)):
+        w = (C.c_uint * 9)()
+        assert P.fwp_early_msg(c, i, w) == 1
+        out.append(tuple(w))
+    return out
+
+
 def hostonly_ctx(**kw):
     """firewheel_amd.FirewheelGpuCtx (the typed host mirror bench.py uses) on the host-only harness library"""
     import firewheel_amd as fa

@@ -1,44 +1,8 @@
-// TEST DOUBLE'S COMPANION (tests/test_bq_sweep.py): reads the messages a host-only ctx keeps for nodes that no built plan holds yet
-// (fwgpu_ctx::early_msgs — the ABI queues them there until the plan that activates the node is published), so that a test can see
-// WHAT fwgpu_biquad_sweep queued, and runs the sweep's ONE statement (fwgpu_types.h bq_sweep_*, the functions the kernels compile) on
-// the host, for the numpy model to be held against.  Header-only access: built on its own, beside the harness library, with the
-// harness's include paths and flags (the layout of fwgpu_ctx is theirs).
-#include <string.h>
+// TEST DOUBLE'S COMPANION (tests/test_bq_sweep.py): the messages a host-only ctx keeps for nodes that no built plan holds yet
+// (early_peek.h), the host's sweep book, and the sweep's ONE statement (fwgpu_types.h bq_sweep_*, the functions the kernels compile) on
+// the host, for the numpy model to be held against.
+#include "early_peek.h"
 
-#include "../../firewheel_amd/csrc/fwgpu_ctx.h"
-
-extern "C" unsigned bsp_early_count(const fwgpu_ctx* c) { return c ? (unsigned)c->early_msgs.size() : 0u; }
-// message i: out[0] = type, out[1] = block, out[2..6] = the bits of the five coefficients as CMD_SET_COEFS packs them (f0, i0, i1, the
-// low and the high word of d0), out[7], out[8] = the low and the high word of d1; 0 = no such message
-extern "C" int bsp_early_msg(const fwgpu_ctx* c, unsigned i, unsigned* out) {
-    if (!c || i >= c->early_msgs.size()) return 0;
-    const fwgpu::Cmd& m = c->early_msgs[i];
-    unsigned long long d0, d1;
-    memcpy(&d0, &m.d0, 8);
-    memcpy(&d1, &m.d1, 8);
-    out[0] = (unsigned)m.type;
-    out[1] = m.block;
-    memcpy(&out[2], &m.f0, 4);
-    out[3] = (unsigned)m.i0;
-    out[4] = (unsigned)m.i1;
-    out[5] = (unsigned)(d0 & 0xffffffffull);
-    out[6] = (unsigned)(d0 >> 32);
-    out[7] = (unsigned)(d1 & 0xffffffffull);
-    out[8] = (unsigned)(d1 >> 32);
-    return 1;
-}
-// the layout handshake (see sampler_fade_peek.cpp): members in FRONT of early_msgs and BEHIND it read as they must; 0 = all do
-extern "C" int bsp_layout_check(const fwgpu_ctx* c, unsigned sample_rate, unsigned mbf, unsigned n_gin, unsigned n_gout) {
-    if (!c) return -1;
-    int bad = 0;
-    if (c->sample_rate != sample_rate) bad |= 1;
-    if (c->mbf != mbf) bad |= 2;
-    if (c->n_gin != n_gin || c->n_gout != n_gout) bad |= 4;
-    if (c->cmds.capacity() != fwgpu_ctx::CMD_CAP || c->cmds.size() > c->cmds.capacity()) bad |= 8;
-    if (c->drain_epoch.load(std::memory_order_relaxed) < 1 || c->drain_epoch.load(std::memory_order_relaxed) > (1ull << 40)) bad |= 16;
-    if (c->early_msgs.size() > fwgpu_ctx::RING_CAP || c->early_msgs.size() > c->early_msgs.capacity()) bad |= 32;
-    return bad;
-}
 // the host's count of frames and of the frame behind which no sweep is in flight (fwgpu_run.cpp note_bq_sweeps)
 extern "C" void bsp_sweep_book(const fwgpu_ctx* c, unsigned long long* out) {
     out[0] = c->frames_done;
@@ -94,14 +58,9 @@ extern "C" int bsp_advance(unsigned* st, unsigned frames) {
 }
 // a message's fields back into (five coefficient bits, frames)
 extern "C" void bsp_unpack(const unsigned* msg, unsigned* out) {
-    float f0;
-    memcpy(&f0, &msg[2], 4);
-    const unsigned long long d0 = ((unsigned long long)msg[6] << 32) | msg[5], d1 = ((unsigned long long)msg[8] << 32) | msg[7];
-    double a, b;
-    memcpy(&a, &d0, 8);
-    memcpy(&b, &d1, 8);
+    const fwgpu::Cmd m = fwp_msg_of(msg);
     float co[5];
-    fwgpu::bq_cmd_coefs(f0, (int)msg[3], (int)msg[4], a, co);
+    bq_cmd_coefs(m, co);
     memcpy(out, co, 20);
-    out[5] = fwgpu::bq_cmd_frames(b);
+    out[5] = bq_cmd_frames(m);
 }

@@ -1,40 +1,11 @@
 // TEST DOUBLE'S COMPANION (tests/test_stream_source.py), header-only access beside the harness library, built on its own with the
-// harness's include paths and flags (as sampler_fade_peek.cpp is):
-//   - the messages a host-only ctx keeps for nodes that no built plan holds yet (fwgpu_ctx::early_msgs), with the 64-bit payloads a
-//     stream's messages carry, and the bytes of a stream's ring (the fake runtime's device memory is host memory);
+// harness's include paths and flags:
+//   - the messages a host-only ctx keeps for nodes that no built plan holds yet (early_peek.h), and the bytes of a stream's
+//     ring (the fake runtime's device memory is host memory);
 //   - the stream's ONE statement (fwgpu_types.h smp_stream_*, the functions the kernels compile) on the host, driven block by block
 //     with the looping sampler's playhead move restated here (k_common.hip.h sampler_advance is device code).
-#include <string.h>
+#include "early_peek.h"
 
-#include "../../firewheel_amd/csrc/fwgpu_ctx.h"
-
-extern "C" unsigned ssp_early_count(const fwgpu_ctx* c) { return c ? (unsigned)c->early_msgs.size() : 0u; }
-// message i: out = {type, block, i0, i1, d0 bits, d1 bits, state}; 0 = no such message
-extern "C" int ssp_early_msg(const fwgpu_ctx* c, unsigned i, unsigned long long* out) {
-    if (!c || i >= c->early_msgs.size()) return 0;
-    const fwgpu::Cmd& m = c->early_msgs[i];
-    out[0] = (unsigned long long)(unsigned)m.type;
-    out[1] = m.block;
-    out[2] = (unsigned long long)(unsigned)m.i0;
-    out[3] = (unsigned long long)(unsigned)m.i1;
-    out[4] = fwgpu::fw_bits_of64(m.d0);
-    out[5] = fwgpu::fw_bits_of64(m.d1);
-    out[6] = (unsigned long long)(unsigned)m.state;
-    return 1;
-}
-// the layout handshake (see sampler_fade_peek.cpp): members in front of and behind what this file reads must read as they must
-extern "C" int ssp_layout_check(const fwgpu_ctx* c, unsigned sample_rate, unsigned mbf, unsigned n_gin, unsigned n_gout, unsigned n_streams) {
-    if (!c) return -1;
-    int bad = 0;
-    if (c->sample_rate != sample_rate) bad |= 1;
-    if (c->mbf != mbf) bad |= 2;
-    if (c->n_gin != n_gin || c->n_gout != n_gout) bad |= 4;
-    if (c->cmds.capacity() != fwgpu_ctx::CMD_CAP || c->cmds.size() > c->cmds.capacity()) bad |= 8;
-    if (c->drain_epoch.load(std::memory_order_relaxed) < 1 || c->drain_epoch.load(std::memory_order_relaxed) > (1ull << 40)) bad |= 16;
-    if (c->early_msgs.size() > fwgpu_ctx::RING_CAP || c->early_msgs.size() > c->early_msgs.capacity()) bad |= 32;
-    if (c->streams.size() != n_streams) bad |= 64;
-    return bad;
-}
 // the ring of stream `sample`: `n` bytes from byte `off` (0: no such stream, or out of range)
 extern "C" int ssp_ring_bytes(const fwgpu_ctx* c, int sample, unsigned long long off, unsigned long long n, unsigned char* out) {
     if (!c || sample < 0 || sample >= (int)c->samples.size() || c->samples[sample].stream < 0 || !c->samples[sample].desc.data) return 0;

@@ -149,27 +149,10 @@ def test_model_at_rest_is_the_biquad_of_refmodel_and_block_splits_do_not_matter(
 def _peek_lib():
     """tests/host_harness/bq_sweep_peek.cpp beside the harness library: the messages a ctx keeps for nodes no plan holds yet, the host's
     sweep book, and the sweep functions of fwgpu_types.h — the ones the kernels compile — built for the host"""
-    import subprocess
-
-    d = os.path.join(ROOT, "tests", "host_harness")
-    src, so = os.path.join(d, "bq_sweep_peek.cpp"), os.path.join(d, "_bq_sweep_peek.so")
-    csrc = os.path.join(ROOT, "firewheel_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "include", "fwgpu.h")] + [os.path.join(csrc, h) for h in ("fwgpu_ctx.h", "fwgpu_types.h", "fwgpu_graph.h",
-                                                                                             "fwgpu_launch.h", "fwgpu_msgq.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(x) > os.path.getmtime(so) for x in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-Wall", "-Wno-unused-function", "-I",
-                               os.path.join(d, "fakehip"), "-I", os.path.join(ROOT, "include"), "-o", so, src])
-    P = C.CDLL(so)
     up = C.POINTER(C.c_uint)
-    P.bsp_early_count.restype, P.bsp_early_count.argtypes = C.c_uint, [C.c_void_p]
-    P.bsp_early_msg.restype, P.bsp_early_msg.argtypes = C.c_int, [C.c_void_p, C.c_uint, up]
-    P.bsp_layout_check.restype, P.bsp_layout_check.argtypes = C.c_int, [C.c_void_p] + [C.c_uint] * 4
-    P.bsp_sweep_book.restype, P.bsp_sweep_book.argtypes = None, [C.c_void_p, C.POINTER(C.c_ulonglong)]
-    P.bsp_values.restype, P.bsp_values.argtypes = None, [up, up, C.c_uint, up]
-    P.bsp_start.restype, P.bsp_start.argtypes = C.c_int, [up, up, up, C.c_uint]
-    P.bsp_advance.restype, P.bsp_advance.argtypes = C.c_int, [up, C.c_uint]
-    P.bsp_unpack.restype, P.bsp_unpack.argtypes = None, [up, up]
-    return P
+    return fwapi.peek_lib("bq_sweep_peek", {"bsp_sweep_book": (None, [C.c_void_p, C.POINTER(C.c_ulonglong)]), "bsp_values": (None, [up, up, C.c_uint, up]),
+                                            "bsp_start": (C.c_int, [up, up, up, C.c_uint]), "bsp_advance": (C.c_int, [up, C.c_uint]),
+                                            "bsp_unpack": (None, [up, up])})
 
 
 def _st(sw):
@@ -218,13 +201,7 @@ def test_the_kernels_own_statement_equals_the_model():
 
 
 # ================================================================================================ CPU tier: the ABI on the harness
-def _early(P, c):
-    out = []
-    for i in range(P.bsp_early_count(c)):
-        w = (C.c_uint * 9)()
-        assert P.bsp_early_msg(c, i, w) == 1
-        out.append(tuple(w))
-    return out
+_early = fwapi.early_msgs
 
 
 def test_abi_what_a_call_queues_and_what_it_refuses():
@@ -233,8 +210,8 @@ def test_abi_what_a_call_queues_and_what_it_refuses():
     P = _peek_lib()
     e = HostOnlyEngine(sample_rate=44100, max_block_frames=96, num_graph_inputs=3, num_graph_outputs=2)
     L, c = e.cx.L, e.cx.c
-    assert P.bsp_layout_check(c, 44100, 96, 3, 2) == 0
-    assert P.bsp_layout_check(c, 44100, 64, 3, 2) == 2          # (and it does look)
+    assert P.fwp_layout_check(c, 44100, 96, 3, 2, 0) == 0
+    assert P.fwp_layout_check(c, 44100, 64, 3, 2, 0) == 2       # (and it does look)
     b = e.biquad(HP, 800.0, 2.0)
     vol = e.volume(50.0)
     assert L.fwgpu_biquad_sweep(c, b, 5000.0, 3.0, bm.FRAMES_MAX, 0) == 0            # the longest sweep

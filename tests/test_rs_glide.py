@@ -202,44 +202,20 @@ def _harness_bank(n=3):
     return e, srcs
 
 
-def _peek_lib():
-    """tests/host_harness/rs_glide_peek.cpp beside the harness library: the messages a ctx keeps for nodes no plan holds yet"""
-    import subprocess
-
-    d = os.path.join(ROOT, "tests", "host_harness")
-    src, so = os.path.join(d, "rs_glide_peek.cpp"), os.path.join(d, "_rs_glide_peek.so")
-    csrc = os.path.join(ROOT, "firewheel_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "include", "fwgpu.h")] + [os.path.join(csrc, h) for h in ("fwgpu_ctx.h", "fwgpu_types.h", "fwgpu_graph.h",
-                                                                                             "fwgpu_launch.h", "fwgpu_msgq.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(x) > os.path.getmtime(so) for x in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-Wall", "-Wno-unused-function", "-I", os.path.join(d, "fakehip"),
-                               "-I", os.path.join(ROOT, "include"), "-o", so, src])
-    P = C.CDLL(so)
-    P.rsg_early_count.restype, P.rsg_early_count.argtypes = C.c_uint, [C.c_void_p]
-    P.rsg_early_msg.restype, P.rsg_early_msg.argtypes = C.c_int, [C.c_void_p, C.c_uint, C.POINTER(C.c_uint)]
-    P.rsg_layout_check.restype, P.rsg_layout_check.argtypes = C.c_int, [C.c_void_p] + [C.c_uint] * 4
-    return P
-
-
 def _early(P, c):
     """[(type, block, i0, d0 bits)] of the messages waiting for their node's first plan"""
-    out = []
-    for i in range(P.rsg_early_count(c)):
-        w = (C.c_uint * 5)()
-        assert P.rsg_early_msg(c, i, w) == 1
-        out.append((w[0], w[1], w[2], w[3] | (w[4] << 32)))
-    return out
+    return [(w[0], w[1], w[3], w[5] | (w[6] << 32)) for w in fwapi.early_msgs(P, c)]
 
 
 def test_abi_what_a_call_queues():
     """one Cmd per call: CMD_RS_GLIDE with S1 = resampler_step(ratio) as the bits of d0 and frames in i0; frames == 0 is CMD_RS_STEP,
     the message param 1 queues.  Read where the ABI keeps the messages of a node that no plan holds yet."""
-    P = _peek_lib()
+    P = fwapi.peek_lib("rs_glide_peek")
     e = HostOnlyEngine(sample_rate=44100, max_block_frames=96, num_graph_inputs=3, num_graph_outputs=2)
     L, c = e.cx.L, e.cx.c
     # the helper and the harness library are two builds of fwgpu_ctx: members in front of and behind early_msgs must read as they were set
-    assert P.rsg_layout_check(c, 44100, 96, 3, 2) == 0
-    assert P.rsg_layout_check(c, 44100, 64, 3, 2) == 2 and P.rsg_layout_check(c, 48000, 96, 2, 2) == 5      # (and it does look)
+    assert P.fwp_layout_check(c, 44100, 96, 3, 2, 0) == 0
+    assert P.fwp_layout_check(c, 44100, 64, 3, 2, 0) == 2 and P.fwp_layout_check(c, 48000, 96, 2, 2, 0) == 5      # (and it does look)
     s = e.resampler(_sample(e, 0, 900), 1.0, loop=True, n_out=2)
     assert _early(P, c) == []
     assert L.fwgpu_resampler_glide(c, s, 2.0, gm.FRAMES_MAX, 0) == 0               # the longest glide

@@ -88,25 +88,9 @@ def test_env_starts_on_e0_is_monotone_stays_inside_and_rests_on_e1():
 def _peek_lib():
     """tests/host_harness/sampler_fade_peek.cpp beside the harness library: the messages a ctx keeps for nodes no plan holds yet, and
     the envelope functions of fwgpu_types.h — the ones the kernels compile — built for the host"""
-    import subprocess
-
-    d = os.path.join(ROOT, "tests", "host_harness")
-    src, so = os.path.join(d, "sampler_fade_peek.cpp"), os.path.join(d, "_sampler_fade_peek.so")
-    csrc = os.path.join(ROOT, "firewheel_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "include", "fwgpu.h")] + [os.path.join(csrc, h) for h in ("fwgpu_ctx.h", "fwgpu_types.h", "fwgpu_graph.h",
-                                                                                             "fwgpu_launch.h", "fwgpu_msgq.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(x) > os.path.getmtime(so) for x in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-Wall", "-Wno-unused-function", "-I",
-                               os.path.join(d, "fakehip"), "-I", os.path.join(ROOT, "include"), "-o", so, src])
-    P = C.CDLL(so)
     up = C.POINTER(C.c_uint)
-    P.sfp_early_count.restype, P.sfp_early_count.argtypes = C.c_uint, [C.c_void_p]
-    P.sfp_early_msg.restype, P.sfp_early_msg.argtypes = C.c_int, [C.c_void_p, C.c_uint, up]
-    P.sfp_layout_check.restype, P.sfp_layout_check.argtypes = C.c_int, [C.c_void_p] + [C.c_uint] * 4
-    P.sfp_env_values.restype, P.sfp_env_values.argtypes = None, [up, C.c_uint, up]
-    P.sfp_env_start.restype, P.sfp_env_start.argtypes = None, [up, C.c_uint, C.c_uint, C.c_int]
-    P.sfp_env_behind_block.restype, P.sfp_env_behind_block.argtypes = None, [up, C.c_uint]
-    return P
+    return fwapi.peek_lib("sampler_fade_peek", {"sfp_env_values": (None, [up, C.c_uint, up]), "sfp_env_start": (None, [up, C.c_uint, C.c_uint, C.c_int]),
+                                                "sfp_env_behind_block": (None, [up, C.c_uint])})
 
 
 def _st(env, playing=1, has_loop=0, playhead=0, loop_start=0):
@@ -363,12 +347,7 @@ def test_model_a_muted_voice_holds_its_playhead_while_the_envelope_runs_on_and_t
 # ================================================================================================ CPU tier: the ABI on the harness
 def _early(P, c):
     """[(type, block, i0, f0 bits, i1)] of the messages waiting for their node's first plan"""
-    out = []
-    for i in range(P.sfp_early_count(c)):
-        w = (C.c_uint * 5)()
-        assert P.sfp_early_msg(c, i, w) == 1
-        out.append(tuple(w))
-    return out
+    return [(w[0], w[1], w[3], w[2], w[4]) for w in fwapi.early_msgs(P, c)]
 
 
 def test_abi_what_a_call_queues():
@@ -377,8 +356,8 @@ def test_abi_what_a_call_queues():
     P = _peek_lib()
     e = HostOnlyEngine(sample_rate=44100, max_block_frames=96, num_graph_inputs=3, num_graph_outputs=2)
     L, c = e.cx.L, e.cx.c
-    assert P.sfp_layout_check(c, 44100, 96, 3, 2) == 0
-    assert P.sfp_layout_check(c, 44100, 64, 3, 2) == 2 and P.sfp_layout_check(c, 48000, 96, 2, 2) == 5      # (and it does look)
+    assert P.fwp_layout_check(c, 44100, 96, 3, 2, 0) == 0
+    assert P.fwp_layout_check(c, 44100, 64, 3, 2, 0) == 2 and P.fwp_layout_check(c, 48000, 96, 2, 2, 0) == 5      # (and it does look)
     s = e.sampler(100.0)
     assert _early(P, c) == []
     assert L.fwgpu_sampler_fade(c, s, 0.0, fm.FRAMES_MAX, STOP, 0) == 0            # the longest fade
@@ -466,7 +445,7 @@ def test_typed_mirror_fade_in_queues_its_three_messages_in_order():
 
     P = _peek_lib()
     cx = fwapi.hostonly_ctx(max_block_frames=64)
-    assert P.sfp_layout_check(cx.c, 48000, 64, 0, 2) == 0
+    assert P.fwp_layout_check(cx.c, 48000, 64, 0, 2, 0) == 0
     node = fa.SamplerNode(100.0)
     nid = cx.add_node(0, 2, node)
     node.fade_in(480, at_block=2)                       # before the first update: the three wait, in order

@@ -55,30 +55,13 @@ def rows_for(fmt, channels, frames, seed):
 
 # ================================================================================================ CPU tier 1: the state machine
 def _peek_lib():
-    d = HARNESS
-    src, so = os.path.join(d, "stream_source_peek.cpp"), os.path.join(d, "_stream_source_peek.so")
-    csrc = os.path.join(ROOT, "firewheel_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "include", "fwgpu.h")] + [os.path.join(csrc, h) for h in ("fwgpu_ctx.h", "fwgpu_types.h", "fwgpu_graph.h",
-                                                                                             "fwgpu_launch.h", "fwgpu_msgq.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(x) > os.path.getmtime(so) for x in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-Wall", "-Wno-unused-function", "-I",
-                               os.path.join(d, "fakehip"), "-I", os.path.join(ROOT, "include"), "-o", so, src])
-    P = C.CDLL(so)
     ull = C.POINTER(C.c_ulonglong)
-    P.ssp_early_count.restype, P.ssp_early_count.argtypes = C.c_uint, [C.c_void_p]
-    P.ssp_early_msg.restype, P.ssp_early_msg.argtypes = C.c_int, [C.c_void_p, C.c_uint, ull]
-    P.ssp_layout_check.restype, P.ssp_layout_check.argtypes = C.c_int, [C.c_void_p] + [C.c_uint] * 5
-    P.ssp_ring_bytes.restype, P.ssp_ring_bytes.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_char_p]
-    P.ssp_stream_rec.restype, P.ssp_stream_rec.argtypes = C.c_int, [C.c_void_p, C.c_int, ull]
-    P.ssp_stream_pub_n.restype, P.ssp_stream_pub_n.argtypes = C.c_int, [C.c_void_p]
-    P.ssp_init.restype, P.ssp_init.argtypes = None, [C.c_void_p]
-    P.ssp_bind.restype, P.ssp_bind.argtypes = None, [C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_int]
-    P.ssp_unbind.restype, P.ssp_unbind.argtypes = None, [C.c_void_p, C.c_int]
-    P.ssp_msg.restype, P.ssp_msg.argtypes = None, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_ulonglong]
-    P.ssp_transport.restype, P.ssp_transport.argtypes = None, [C.c_void_p, C.c_int]
-    P.ssp_block.restype, P.ssp_block.argtypes = C.c_uint, [C.c_void_p, C.c_uint, C.c_int]
-    P.ssp_get.restype, P.ssp_get.argtypes = None, [C.c_void_p, ull]
-    return P
+    return fwapi.peek_lib("stream_source_peek", {
+        "ssp_ring_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_char_p]),
+        "ssp_stream_rec": (C.c_int, [C.c_void_p, C.c_int, ull]), "ssp_stream_pub_n": (C.c_int, [C.c_void_p]), "ssp_init": (None, [C.c_void_p]),
+        "ssp_bind": (None, [C.c_void_p, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_int]), "ssp_unbind": (None, [C.c_void_p, C.c_int]),
+        "ssp_msg": (None, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_ulonglong]), "ssp_transport": (None, [C.c_void_p, C.c_int]),
+        "ssp_block": (C.c_uint, [C.c_void_p, C.c_uint, C.c_int]), "ssp_get": (None, [C.c_void_p, ull])})
 
 
 def _get(P, st):
@@ -281,33 +264,32 @@ def test_host_what_a_write_queues():
     the call returns), the end one more with E"""
     P = _peek_lib()
     e, s = _host(update=False)
-    assert P.ssp_layout_check(e.cx.c, 48000, 64, 0, 2, 0) == 0
+    assert P.fwp_layout_check(e.cx.c, 48000, 64, 0, 2, 0) == 0
     sid = _rc(e, "fwgpu_sample_create_stream", I_I16, 2, 300)
     rows = rows_for(I_I16, 2, 500, 2)
-    assert _write(e, sid, I_I16, rows[:70]) == 70 and P.ssp_early_count(e.cx.c) == 0       # before a sampler holds it: the ring alone
+    assert _write(e, sid, I_I16, rows[:70]) == 70 and P.fwp_early_count(e.cx.c) == 0       # before a sampler holds it: the ring alone
     assert _rc(e, "fwgpu_sampler_set_sample", s, sid, 1, 0) == 0
 
-    def msg(i):
-        o = (C.c_ulonglong * 7)()
-        assert P.ssp_early_msg(e.cx.c, i, o)
-        return list(o)
+    def msg(i, eng=e):
+        """[type, block, i0, i1, d0 bits, d1 bits]"""
+        w = fwapi.early_msgs(P, eng.cx.c)[i]
+        return [w[0], w[1], w[3], w[4], w[5] | (w[6] << 32), w[7] | (w[8] << 32)]
 
-    assert P.ssp_early_count(e.cx.c) == 1
+    assert P.fwp_early_count(e.cx.c) == 1
     assert msg(0)[:6] == [10, 0, sid, 1, 300, 70]                                          # CMD_SMP_SET_SAMPLE: stop flag, R, W
     assert _write(e, sid, I_I16, rows[70:170]) == 100
-    assert P.ssp_early_count(e.cx.c) == 2 and msg(1)[:6] == [sm.CMD_SMP_STREAM, 0, 0, 0, 170, 0]
+    assert P.fwp_early_count(e.cx.c) == 2 and msg(1)[:6] == [sm.CMD_SMP_STREAM, 0, 0, 0, 170, 0]
     got = C.create_string_buffer(170 * 4)
     assert P.ssp_ring_bytes(e.cx.c, sid, 0, 170 * 4, got)
     assert got.raw == rows[:170].tobytes()
     assert _rc(e, "fwgpu_sample_stream_end", sid) == 0
-    assert P.ssp_early_count(e.cx.c) == 3 and msg(2)[:6] == [sm.CMD_SMP_STREAM, 0, 1, 0, 170 + 64, 170]
+    assert P.fwp_early_count(e.cx.c) == 3 and msg(2)[:6] == [sm.CMD_SMP_STREAM, 0, 1, 0, 170 + 64, 170]
     assert _status(e, sid) == (170, 0, 0, 0)
     # a plain sample's binding carries no stream payload
     e2, s2 = _host(update=False)
     plain = e2.new_sample(P_F32, 2, np.zeros((2, 100), dtype=F32))
     assert _rc(e2, "fwgpu_sampler_set_sample", s2, plain, 0, 0) == 0
-    o = (C.c_ulonglong * 7)()
-    assert P.ssp_early_msg(e2.cx.c, 0, o) and list(o)[:6] == [10, 0, plain, 0, 0, 0]
+    assert msg(0, e2)[:6] == [10, 0, plain, 0, 0, 0]
 
 
 @pytest.mark.parametrize("fmt", [I_I16, P_U16])
