@@ -1141,6 +1141,36 @@ int fwgpu_biquad_sweep(fwgpu_ctx* c, int64_t node, float cutoff_hz, float q, uin
     biquad_coefs(n->init.enabled, cutoff_hz, q, c->sample_rate, co);
     return push_cmd(c, node, -1, make_bq_coefs(at_block, co, frames), false);
 }
+// SPEC spatialiser move: one CMD_SP_MOVE to what params 0..2 would set for (x, y, z); frames == 0 is their three
+// position messages (CMD_SET_P0, CMD_SET_P1, CMD_SP_ITD), a step.  Any coordinates but a NaN, at most 2^24 frames
+int fwgpu_spatial_move(fwgpu_ctx* c, int64_t node, float x, float y, float z, uint32_t frames, uint32_t at_block) {
+    static_assert(FWGPU_SPATIAL_MOVE_FRAMES_MAX == SP_MOVE_FRAMES_MAX, "the header's move cap");
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    HostNode* n = c->graph.get(node);
+    if (!n) return fail(c, FWGPU_ERR_INVALID, "unknown node id");
+    if (n->kind != K_SPATIAL) return fail(c, FWGPU_ERR_INVALID, "fwgpu_spatial_move: the node is not a SpatialNode");
+    if (x != x || y != y || z != z) return fail(c, FWGPU_ERR_INVALID, "fwgpu_spatial_move: a coordinate is NaN");
+    if (frames > FWGPU_SPATIAL_MOVE_FRAMES_MAX) return fail(c, FWGPU_ERR_INVALID, "fwgpu_spatial_move: at most 2^24 frames");
+    float gl, gr;
+    int dl, dr;
+    spatial_params(x, y, z, c->sample_rate, &gl, &gr, &dl, &dr);
+    int rc;
+    if (frames != 0u) {
+        rc = push_cmd(c, node, -1, make_sp_move(at_block, gl, gr, dl, dr, frames), false);
+    } else {  // the three messages the LAST of three set_param calls for that position queues (its first two calls' six are overwritten by them)
+        rc = push_cmd(c, node, -1, make_set(CMD_SET_P0, at_block, gl), false);
+        if (!rc) rc = push_cmd(c, node, -1, make_set(CMD_SET_P1, at_block, gr), false);
+        if (!rc) rc = push_cmd(c, node, -1, make_sp_itd(at_block, gr, dl, dr), false);
+    }
+    if (rc) return rc;  // (a refused call leaves the node's recorded position alone)
+    n = c->graph.get(node);
+    if (n) {  // a later set_param of one coordinate starts from these
+        n->init.phasor = x;
+        n->init.phasor_inc = y;
+        n->init.gain = z;
+    }
+    return 0;
+}
 int fwgpu_node_set_params(fwgpu_ctx* c, uint32_t n, const int64_t* nodes, const int* params, const float* values, const uint32_t* at_blocks) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
     if (n && (!nodes || !params || !values || !at_blocks)) return fail(c, FWGPU_ERR_INVALID, "null message list");
@@ -1750,6 +1780,7 @@ int fwgpu_node_process(fwgpu_ctx* c, int64_t node, uint64_t frames, const float*
     v.pool = c->d_scratch_pool.as<float>();
     v.flags = c->d_scratch_flags.as<uint8_t>();
     c->epoch++;
+    v.sp_moves = hn->kind == K_SPATIAL ? 1 : 0;  // (k_single_node_spm: the build that takes CMD_SP_MOVE and renders a move)
     LCHK(c, launch_single_node(c->stream, v, 0));
     for (uint32_t i = 0; i < n_out; ++i)
         HIPC(c, hipMemcpyAsync(outputs[i], c->d_scratch_pool.as<float>() + (1 + n_in + i) * stride, frames * sizeof(float),

@@ -421,6 +421,16 @@ struct fwgpu_ctx : fwgpu::PlanImage {
     // rendered may meet a sweep — no lazy call, no batch walkers (k_level<1> renders the sweep's blocks), k_chain's sweep instantiation
     uint64_t frames_done = 0, bq_sweep_until = 0;
     bool bq_sweep_live = false;
+    // the same for spatialiser moves (CMD_SP_MOVE): sp_move_live — the call being rendered may meet a move: no lazy call, no captured
+    // graph, and the node / control kernels' move instantiations (k_level<1, true>, k_voice_control_spm); a call that cannot meet one
+    // launches exactly the kernels it launched before the move existed
+    uint64_t sp_move_until = 0;
+    bool sp_move_live = false;
+    // The bound assumes the node renders every block from its message on.  A node that leaves the plan in mid-move keeps N != 0 in its
+    // state slot and may come back with a later plan: sp_move_max_n = the longest move noted while one may be in flight,
+    // sp_move_parked_n = the longest one that a plan install may have parked (never cleared: the node may return with any later
+    // plan) — adopt_image extends the bound by it, so the call a parked node returns in runs the move builds until its move is over
+    uint32_t sp_move_max_n = 0, sp_move_parked_n = 0;
     StatCounter lazy_calls, ctl_calls;           // fused batches rendered without / with a control kernel (fwgpu_lazy_stats)
     int ctl_ahead_mode = 2;          // 1 = every qualifying call (round 3), 2 = only calls with messages / continuing glides (round 4)
     hipStream_t ctl_stream = nullptr;

@@ -70,7 +70,9 @@ int launch_level(hipStream_t s, const DevView& v, const int* d_level_nodes, int 
     // the level holds a biquad / delay node — in a batch, the ones that are bus effects go to the walkers' kernel
     const uint32_t walkers = (kinds & LB_WALKERS) && K > 1 && !v.no_walkers ? 1u : 0u;
     if (kinds & LB_SET0) hipLaunchKernelGGL(k_level<0>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, 0u);
-    if (kinds & LB_SET1) hipLaunchKernelGGL(k_level<1>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, walkers);
+    // (a call that may meet a spatialiser move — fwgpu_run.cpp note_sp_moves — takes the instantiation that renders one)
+    if ((kinds & LB_SET1) && v.sp_moves) hipLaunchKernelGGL((k_level<1, true>), grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, walkers);
+    else if (kinds & LB_SET1) hipLaunchKernelGGL(k_level<1>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, walkers);
     if (kinds & LB_SET2) hipLaunchKernelGGL(k_level<2>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, 0u);
     // a look-ahead limiter — a wave per (node, block), its staged gains in LDS of its own
     if (kinds & LB_LIMITER) hipLaunchKernelGGL(k_limiter, dim3(n_nodes, K), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K);
@@ -133,7 +135,9 @@ int launch_fir(hipStream_t s, const DevView& v, const FirRow* d_rows, int n_rows
     return (int)hipGetLastError();
 }
 int launch_single_node(hipStream_t s, const DevView& v, int node_idx) {
-    hipLaunchKernelGGL(k_single_node, dim3(1), dim3(WAVE), 0, s, v, node_idx);
+    // (a spatialiser takes the build that renders a move: fwgpu_node_process sets DevView::sp_moves for that kind alone)
+    if (v.sp_moves) hipLaunchKernelGGL(k_single_node<true>, dim3(1), dim3(WAVE), 0, s, v, node_idx);
+    else hipLaunchKernelGGL(k_single_node<false>, dim3(1), dim3(WAVE), 0, s, v, node_idx);
     return (int)hipGetLastError();
 }
 int launch_scatter_ext(hipStream_t s, float* ext, const void* d_items, int n) {
@@ -178,7 +182,10 @@ int launch_voice_control(hipStream_t s, const FusedView& fv, int K, uint32_t cmd
     static const int occ = [] { const char* e = getenv("FWGPU_CTL_OCC"); return e ? atoi(e) : 0; }();  // experiments: 1 / 3 = force a build
     const bool small = occ ? occ == 3 : beside_render;
     const int wpb = beside_render ? 1 : 4;
-    if (small) hipLaunchKernelGGL(k_voice_control_small, dim3((fv.n_voices + wpb - 1) / wpb), dim3(WAVE * wpb), 0, s, fv, K, cmd_block0);
+    // (a call that may meet a spatialiser move — fwgpu_run.cpp note_sp_moves — takes the instantiations that follow one)
+    if (fv.sp_moves && small) hipLaunchKernelGGL(k_voice_control_small_spm, dim3((fv.n_voices + wpb - 1) / wpb), dim3(WAVE * wpb), 0, s, fv, K, cmd_block0);
+    else if (fv.sp_moves) hipLaunchKernelGGL(k_voice_control_spm, dim3((fv.n_voices + wpb - 1) / wpb), dim3(WAVE * wpb), 0, s, fv, K, cmd_block0);
+    else if (small) hipLaunchKernelGGL(k_voice_control_small, dim3((fv.n_voices + wpb - 1) / wpb), dim3(WAVE * wpb), 0, s, fv, K, cmd_block0);
     else hipLaunchKernelGGL(k_voice_control, dim3((fv.n_voices + wpb - 1) / wpb), dim3(WAVE * wpb), 0, s, fv, K, cmd_block0);
     return (int)hipGetLastError();
 }
@@ -348,7 +355,8 @@ int launch_leaf_sum(hipStream_t s, const FusedView& fv, int K) {
 #else
     dim3 grid((fv.n_leaves + LEAF_WPB - 1) / LEAF_WPB, K);
 #endif
-    if (fv.has_sp && fv.has_rs) hipLaunchKernelGGL((k_leaf_sum<true, true, true>), grid, dim3(WAVE * LEAF_WPB), RS_LDS_BYTES(LEAF_WPB), s, fv, K, wpk);
+    if (fv.has_sp && fv.has_rs && fv.sp_moves) hipLaunchKernelGGL(k_leaf_sum_rs_sp_spm, grid, dim3(WAVE * LEAF_WPB), RS_LDS_BYTES(LEAF_WPB), s, fv, K, wpk);
+    else if (fv.has_sp && fv.has_rs) hipLaunchKernelGGL((k_leaf_sum<true, true, true>), grid, dim3(WAVE * LEAF_WPB), RS_LDS_BYTES(LEAF_WPB), s, fv, K, wpk);
     else if (fv.has_sp) {
         // one-piece blocks: a wave takes up to 8 consecutive blocks of its leaf (k_leaf.hip.h, leaf_kernel_body) while the launch still fills the chip
         int nb = 1;
@@ -357,7 +365,8 @@ int launch_leaf_sum(hipStream_t s, const FusedView& fv, int K) {
             nb = (int)(pairs / 3072 < 1 ? 1 : (pairs / 3072 > 8 ? 8 : pairs / 3072));
         }
         const dim3 g2 = wpk == 1 ? dim3(fv.n_leaves, (K + LEAF_WPB * nb - 1) / (LEAF_WPB * nb)) : grid;
-        hipLaunchKernelGGL(k_leaf_sum_sp, g2, dim3(WAVE * LEAF_WPB), 0, s, fv, K, wpk, nb);
+        if (fv.sp_moves) hipLaunchKernelGGL(k_leaf_sum_sp_spm, g2, dim3(WAVE * LEAF_WPB), 0, s, fv, K, wpk, nb);
+        else hipLaunchKernelGGL(k_leaf_sum_sp, g2, dim3(WAVE * LEAF_WPB), 0, s, fv, K, wpk, nb);
     }
     else if (fv.has_rs) {  // a pair: the resampler-pure leaves (k_leaf_rs), then whatever it put on the work list
         hipLaunchKernelGGL(k_leaf_rs, grid, dim3(WAVE * LEAF_WPB), RS2_LDS_BYTES(LEAF_WPB), s, fv, K, wpk);

@@ -43,6 +43,8 @@ struct DevView {
     // 1: this call may meet a biquad coefficient sweep (fwgpu_run.cpp note_bq_sweeps) — launch_level starts no batch walkers: k_level<1>
     // and k_bus_iir each decide on the device who renders a bus filter, the first moves the sweep's state, and they must decide alike
     int no_walkers = 0;
+    // 1: this call may meet a spatialiser move (fwgpu_run.cpp note_sp_moves) — launch_level renders set 1 with k_level<1, true>
+    int sp_moves = 0;
 };
 
 // The compact records are tiled: 32 voices x 8 blocks per 4 KiB tile, [voice % 32][block % 8].  A voice's 8 consecutive blocks
@@ -88,6 +90,9 @@ struct FusedView {
     int has_prog;           // some voice's program is not 0 (or its source is a resampler): k_leaf_sum<true>
     int has_rs;             // some voice's source is a resampler: the program instantiation stages windows + filter bank in LDS
     int has_sp;             // some voice ends in a spatialiser stage: k_leaf_sum_sp
+    int sp_moves = 0;       // this call may meet a spatialiser move (fwgpu_run.cpp note_sp_moves): launch_voice_control takes the instantiations
+                            // that follow one; a block inside a move is flagged in its VoiceBlk::pad and the leaf kernel reads its delays
+                            // from the last two ramp rows
     int sp_hist_in_render;  // control-ahead mode + spatialiser stages: k_sp_hist_copy makes the history copy, not k_voice_control
     const int* ctl_order;   // k_voice_control: wave w works voice ctl_order[w] (nullptr: w) — voices with messages first
     unsigned int* rs_wl;    // has_rs: work list k_leaf_rs leaves for k_leaf_sum_wl — [0] items, [1] workgroups done, then (leaf, block*4 + piece) pairs

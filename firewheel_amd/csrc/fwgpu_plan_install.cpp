@@ -948,7 +948,9 @@ static int install_voice_bank(ImageBuild& b, FusedBuild& B, bool hybrid) {
     int rc;
     P.n_voices = (int)B.voices.size();
     P.n_leaves = (int)B.leaves.size();
-    P.ramp_slots = 2 * (1 + B.max_stages);
+    // (a bank with spatialiser voices: two more rows per (block, voice), behind the gain rows — the per-frame ear delays of a block
+    //  inside a move, fwgpu_types.h sp_move_word)
+    P.ramp_slots = 2 * (1 + B.max_stages) + (B.has_sp ? 2 : 0);
     P.fused_prog = B.has_prog;
     P.fused_rs = B.has_rs;
     P.fused_sp = B.has_sp;
@@ -1216,6 +1218,11 @@ void adopt_image(fwgpu_ctx* c, PlanImage* n, bool on_audio_thread) {
     (void)lazy_flush(c);       // blocks rendered from the OLD plan's LazyRecs reach node state before the voices are renumbered
     (void)join_streams(c);  // control-ahead mode: the control stream's work so far is ordered before the swap
     c->ahead_seq = 0;
+    // spatialiser moves (fwgpu_ctx.h sp_move_parked_n): a spatialiser may leave the plan here with its move in flight, and one that
+    // left earlier may come back here with its move where it stood — at most its N frames from now
+    if (c->frames_done < c->sp_move_until && c->sp_move_max_n > c->sp_move_parked_n) c->sp_move_parked_n = c->sp_move_max_n;
+    if (c->sp_move_parked_n && c->sp_move_until != ~0ull && c->frames_done + c->sp_move_parked_n > c->sp_move_until)
+        c->sp_move_until = c->frames_done + c->sp_move_parked_n;
     // 1. larger persistent arrays: old contents copied over on the stream, then the pointers change hands
     if (n->grow_states.p) {
         if (c->d_states.p && c->states_cap)

@@ -241,6 +241,7 @@ void retire_cmds_node(fwgpu_ctx* c, int slot) {
                 // (a sweep started by ONE node's process call moves only with that node's calls: the frame count of the process calls
                 //  says nothing about it, so from here on every process call of this ctx counts as one that may meet a sweep)
                 if (m.type == CMD_BQ_SWEEP) c->bq_sweep_until = ~0ull;
+                if (m.type == CMD_SP_MOVE) c->sp_move_until = ~0ull;  // (the same for a spatialiser move)
                 continue;
             }
             Cmd k = m;
@@ -327,6 +328,7 @@ static void fill_fused_view(fwgpu_ctx* c, FusedView& fv) {
     fv.has_prog = c->fused_prog ? 1 : 0;
     fv.has_rs = c->fused_rs ? 1 : 0;
     fv.has_sp = c->fused_sp ? 1 : 0;
+    fv.sp_moves = c->sp_move_live ? 1 : 0;
     fv.rt_parent_leaf = fv.rt_parent_up = fv.rt_kids = nullptr;
     fv.rt_tree_sync = nullptr;
     fv.rt_root = -1;
@@ -347,7 +349,7 @@ static void fill_fused_view(fwgpu_ctx* c, FusedView& fv) {
     fv.ctl_order = c->ctl_order_live ? c->d_ctl_order.as<int>() : nullptr;
     fv.sp_hist_in_render = (c->ahead_this_call && c->fused_sp) ? 1 : 0;
     fv.hist = c->d_hist.as<float>();
-    fv.n_gain_stages = c->ramp_slots / 2;
+    fv.n_gain_stages = (c->ramp_slots - (c->fused_sp ? 2 : 0)) / 2;  // (a spatialiser bank's last two rows hold delays, not gains)
     fv.ramps = c->d_ramps.as<float>();
     fv.ramp_slots = c->ramp_slots;
     fv.bus = c->d_bus.as<float>();
@@ -427,6 +429,17 @@ static void note_bq_sweeps(fwgpu_ctx* c) {
         }
     c->bq_sweep_live = c->frames_done < c->bq_sweep_until;
 }
+// spatialiser moves, the same way: a move that a set_position cuts short leaves the bound standing, which costs kernels, not bits
+static void note_sp_moves(fwgpu_ctx* c) {
+    for (const Cmd& m : c->cmds)
+        if (m.type == CMD_SP_MOVE) {
+            const uint64_t end = c->frames_done + (uint64_t)m.block * c->mbf + (uint64_t)sp_cmd_frames(m);
+            if (end > c->sp_move_until) c->sp_move_until = end;
+            if (sp_cmd_frames(m) > c->sp_move_max_n) c->sp_move_max_n = sp_cmd_frames(m);
+        }
+    c->sp_move_live = c->frames_done < c->sp_move_until;
+    if (!c->sp_move_live) c->sp_move_max_n = 0;
+}
 // K blocks of `frames` frames through the level-batched executor (schedule.rs:289-344 as one launch per level for
 // all K blocks: each block has its own pool slice, a stateful node walks its K blocks in order inside one wave)
 int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const float* d_in, int n_in_ch, float* d_out,
@@ -437,6 +450,7 @@ int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const
     v.meter_blk0 = c->blocks_done;  // level meters record this batch's blocks
     v.meter_K = (uint32_t)K;
     v.no_walkers = c->bq_sweep_live ? 1 : 0;
+    v.sp_moves = c->sp_move_live ? 1 : 0;
     // which gain-like stateful nodes cannot change during this batch (their blocks then run in parallel): decided once,
     // before the first level
     if (K > 1 && c->d_frozen.ensure_n("d_frozen", (size_t)c->plan.nodes.size()) == hipSuccess &&
@@ -777,6 +791,7 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
         v.meter_blk0 = c->blocks_done;  // a master meter: one more launch_level below, its K blocks in parallel
         v.meter_K = (uint32_t)K;
         v.no_walkers = c->bq_sweep_live ? 1 : 0;
+        v.sp_moves = c->sp_move_live ? 1 : 0;
         if (K > 1) {
             LCHK(c, launch_frozen_scan(c->stream, v, c->n_tail, cmd_block0, K, c->d_tail_frozen.as<uint8_t>(),
                                        c->d_tail_frozen.as<unsigned long long>()));
@@ -832,6 +847,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     // kernel of the call before it cost that kernel 7-15 us of co-residency and the step a ~10 us cross-stream event.
     drain_ring(c);
     note_bq_sweeps(c);
+    note_sp_moves(c);
     const bool hot = c->ctl_ahead_mode == 1 || !c->cmds.empty() || !c->hot_prev.empty();
     // (SPEC streaming sources: no ahead mode while a sampler holds a stream.  The control kernel of call N + 1 would move C beside or
     //  before the render of call N, whose publication — a copy of the live NodeStates behind that render — could then hand the writer a
@@ -847,7 +863,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     c->lazy_this_call = false;
     // (one-block callbacks belong to the realtime kernels, which run their own control)
     if (c->lazy_on && can_fuse && c->lazy_capable && !ahead && !(stable_out && frames == mbf) && !c->rt_use_graph && frames % mbf == 0 && c->cmds.empty() &&
-        c->hot_prev.empty() && !c->bq_sweep_live &&  // (a plan with a sweep in flight runs its control kernel)
+        c->hot_prev.empty() && !c->bq_sweep_live && !c->sp_move_live &&  // (a plan with a sweep or a move in flight runs its control kernel)
         c->lazy_valid && c->lazy_epoch == c->epoch && c->h_lazy_pub) {
         const unsigned long long seq = __atomic_load_n(&c->h_lazy_pub[1], __ATOMIC_ACQUIRE);
         const unsigned long long horizon = __atomic_load_n(&c->h_lazy_pub[0], __ATOMIC_RELAXED);
@@ -874,7 +890,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     // steady realtime call: no message on the device, one fused batch, the same output block as last time — every
     // kernel argument repeats (block counters and playheads live in device state), so the launch sequence is replayed
     // from a hipGraph instead of being re-issued kernel by kernel
-    if (stable_out && c->rt_use_graph && c->meters.empty() && can_fuse && !c->timing && c->n_cmds_dev == 0 && !c->bq_sweep_live && frames % mbf == 0 &&
+    if (stable_out && c->rt_use_graph && c->meters.empty() && can_fuse && !c->timing && c->n_cmds_dev == 0 && !c->bq_sweep_live && !c->sp_move_live && frames % mbf == 0 &&
         frames / mbf <= (c->fused_fx ? std::min<uint32_t>(c->kmax, CH_FAST_KMAX) : c->kmax)) {
         const uint32_t K = (uint32_t)(frames / mbf);
         fwgpu_ctx::RtGraph& g = c->rt_graph;

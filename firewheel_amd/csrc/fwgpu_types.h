@@ -157,7 +157,13 @@ struct NodeState {
     //        step behind the glide), enabled / ext_off = the low / high 32 bits of inc, the signed step change per frame (a
     //        resampler has no ext slice: ext_len stays 0).  make_state leaves all four 0; the arithmetic is rs_glide_* below the struct
     //   SPATIAL: p0/p1 = ear gain targets (s0/s1 smooth them), playing = left-ear delay, has_loop = right-ear delay
-    //        (frames), ext = the last SP_HIST mono samples
+    //        (frames), ext = the last SP_HIST mono samples; a move (CMD_SP_MOVE) in fields it has no other use for:
+    //        full_range = N (0: at rest), enabled = k (frames of the move rendered, k < N), phasor / phasor_inc = G0l / G0r, playhead /
+    //        loop_start = Dl / Dr (the 32.32 per-ear delays at the NEXT block's first frame), loop_end = inc_l, sample | gain bits << 32
+    //        = inc_r (signed, as two's-complement bits).  In a move p0 / p1 and both smoothers rest at the target gains and playing /
+    //        has_loop hold the target delays: the move's end only clears N and k.  make_state leaves N = k = 0 (the device copy of
+    //        phasor / phasor_inc / gain then holds the constructor's x / y / z, which no kernel reads; the host keeps its own in
+    //        HostNode::init); a node's state keeps its slot over a plan install.  The arithmetic is sp_move_* below the struct
     //   METER: ext = ring[R][n_in] of MeterRec (4 floats each), loop_end = R (0: the creation parameter was refused)
     //   LIMITER, DUCKER, DELAY_COMP: loop_end = 0 marks a creation parameter that was refused; the valid states and the slice lengths
     //        are lim_/duck_/dcomp_state_ok and _ext_len below the struct
@@ -524,6 +530,118 @@ FW_TYPES_HD inline bool bq_sweep_advance(BqSweep& w, uint32_t frames) {
     return true;
 }
 
+// K_SPATIAL move (SPEC): ONE statement for the message (apply_cmds_from), the node kernels, the control kernel and the
+// leaf kernel.  Per ear e the gain goes G0 -> G1 over N frames in smp_env_value's form — every operation a separately rounded f32
+// operation (-ffp-contract=off), the division IEEE, (float)(k + j) and (float)N exact (both <= 2^24) — and the delay is a 32.32
+// unsigned number D that moves by a signed inc per frame, in wrapping u64 arithmetic (the resampler glide's rule: inc is truncated
+// toward zero, so D stays between its start and d1 << 32, both <= 63 << 32, and the move's last frame is followed by exactly
+// d1 << 32).  A frame reads the mono row at i - (D >> 32) and, when the fraction's top 24 bits are not all zero, blends in the frame
+// before it: at rest the fraction is zero and the output bits are the integer delay's.
+#define SP_MOVE_FRAMES_MAX 16777216u
+struct SpMove {
+    float G0[2], G1[2];
+    uint64_t D[2], inc[2];  // D: at the snapshot's first frame
+    uint32_t d1[2];
+    uint32_t N, k;
+};
+FW_TYPES_HD inline bool sp_move_at_rest(const NodeState& s) { return s.full_range == 0; }
+FW_TYPES_HD inline uint32_t sp_delay_ok(int d) { return d < 0 ? 0u : (d > SP_HIST - 1 ? (uint32_t)(SP_HIST - 1) : (uint32_t)d); }
+// the move as a block's render loop reads it: a snapshot taken BEFORE the block's advance (at rest: N == 0, D = the integer delays)
+FW_TYPES_HD inline SpMove sp_move_of(const NodeState& s) {
+    SpMove m;
+    m.N = (uint32_t)s.full_range;
+    m.k = (uint32_t)s.enabled;
+    m.G0[0] = s.phasor, m.G0[1] = s.phasor_inc;
+    m.G1[0] = s.p0, m.G1[1] = s.p1;
+    m.d1[0] = sp_delay_ok(s.playing), m.d1[1] = sp_delay_ok(s.has_loop);
+    if (m.N != 0u) {
+        m.D[0] = s.playhead, m.D[1] = s.loop_start;
+        m.inc[0] = s.loop_end;
+        m.inc[1] = (uint64_t)(uint32_t)s.sample | ((uint64_t)fw_bits_of(s.gain) << 32);
+    } else {
+        m.D[0] = (uint64_t)m.d1[0] << 32, m.D[1] = (uint64_t)m.d1[1] << 32;
+        m.inc[0] = m.inc[1] = 0ull;
+    }
+    return m;
+}
+// the gain of ear e, j frames ahead of the snapshot (the clamp: G0 + d can round one ulp past G1); behind the move, and at rest: G1
+FW_TYPES_HD inline float sp_move_gain(const SpMove& m, int e, uint32_t j) {
+    const uint32_t t = m.k + j;
+    if (t >= m.N) return m.G1[e];
+    const float a = m.G0[e], b = m.G1[e];
+    const float v = a + ((b - a) * ((float)t / (float)m.N));
+    const float lo = a < b ? a : b, hi = a < b ? b : a;
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+// the 32.32 delay of ear e, j frames ahead of the snapshot; behind the move exactly d1 << 32
+FW_TYPES_HD inline uint64_t sp_move_delay(const SpMove& m, int e, uint32_t j) {
+    return m.k + j >= m.N ? (uint64_t)m.d1[e] << 32 : m.D[e] + (uint64_t)j * m.inc[e];
+}
+// a delay's whole frames q and its fraction f (24 bits: exact in f32); f != 0 implies q <= 62, so q + 1 stays inside SP_HIST
+FW_TYPES_HD inline uint32_t sp_move_whole(uint64_t D) { return (uint32_t)(D >> 32); }
+FW_TYPES_HD inline float sp_move_frac(uint64_t D) { return (float)((uint32_t)D >> 8) * 5.9604644775390625e-08f; }
+// the same two as ONE 32-bit word per frame and ear — q in bits 24..29, the fraction's 24 bits below — which is how a voice bank's
+// control kernel hands a move block's delays to the leaf kernel: in the two rows behind the block's gain rows (FusedView::ramps)
+FW_TYPES_HD inline uint32_t sp_move_word(uint64_t D) { return (uint32_t)(D >> 8); }
+FW_TYPES_HD inline uint32_t sp_word_whole(uint32_t w) { return w >> 24; }
+FW_TYPES_HD inline float sp_word_frac(uint32_t w) { return (float)(w & 0xffffffu) * 5.9604644775390625e-08f; }
+// the frame: a = m[i - q], b = m[i - q - 1] (read only where f != 0)
+FW_TYPES_HD inline float sp_move_tap(float a, float b, float f) { return f == 0.0f ? a : a + ((b - a) * f); }
+// CMD_SET_P0 / _P1 / CMD_SP_ITD in a move (a plain set_position): the move ends — each smoother continues from the move's current
+// gain towards whatever the message sets, the delays step to the move's target until a CMD_SP_ITD says otherwise
+FW_TYPES_HD inline void sp_move_stop(NodeState& s) {
+    if (s.full_range == 0) return;
+    const SpMove m = sp_move_of(s);
+    s.s0.last = sp_move_gain(m, 0, 0u);
+    s.s1.last = sp_move_gain(m, 1, 0u);
+    s.full_range = 0;
+    s.enabled = 0;
+}
+// the message, applied at a block's first frame: N frames from where the node stands to (G1l, G1r, d1l, d1r)
+FW_TYPES_HD inline void sp_move_start(NodeState& s, float G1l, float G1r, int d1l, int d1r, uint32_t N) {
+    const SpMove m = sp_move_of(s);
+    const float G0l = m.N ? sp_move_gain(m, 0, 0u) : (s.s0.status == SM_ACTIVE ? s.s0.last : s.s0.input);
+    const float G0r = m.N ? sp_move_gain(m, 1, 0u) : (s.s1.status == SM_ACTIVE ? s.s1.last : s.s1.input);
+    // the smoothers are put at rest at the target (coefficients untouched)
+    s.p0 = s.s0.input = s.s0.last = G1l;
+    s.p1 = s.s1.input = s.s1.last = G1r;
+    s.s0.status = s.s1.status = SM_INACTIVE;
+    const uint32_t tl = sp_delay_ok(d1l), tr = sp_delay_ok(d1r);
+    s.playing = (int)tl;
+    s.has_loop = (int)tr;
+    s.enabled = 0;
+    // (N == 0 or N > SP_MOVE_FRAMES_MAX is NOT SPEC behaviour: fwgpu_spatial_move sends the step's own three messages for the first
+    //  and refuses the second, so only a corrupted message gets here — a defensive branch, a step)
+    if (N == 0u || N > SP_MOVE_FRAMES_MAX) {
+        s.full_range = 0;
+        return;
+    }
+    const uint64_t il = (uint64_t)((int64_t)(((uint64_t)tl << 32) - m.D[0]) / (int64_t)N);  // truncated toward zero
+    const uint64_t ir = (uint64_t)((int64_t)(((uint64_t)tr << 32) - m.D[1]) / (int64_t)N);
+    s.phasor = G0l;
+    s.phasor_inc = G0r;
+    s.playhead = m.D[0];
+    s.loop_start = m.D[1];
+    s.loop_end = il;
+    s.sample = (int)(uint32_t)ir;
+    s.gain = fw_float_of((uint32_t)(ir >> 32));
+    s.full_range = (int)N;
+}
+// behind a rendered block of `frames` frames (the values are sp_move_gain / sp_move_delay of a snapshot taken BEFORE this)
+FW_TYPES_HD inline void sp_move_advance(NodeState& s, uint32_t frames) {
+    const uint32_t N = (uint32_t)s.full_range;
+    if (N == 0u) return;
+    const uint32_t k = (uint32_t)s.enabled + frames;  // (k < N <= 2^24 and a block has fewer than 2^31 frames)
+    if (k < N) {
+        s.enabled = (int)k;
+        s.playhead += (uint64_t)frames * s.loop_end;
+        s.loop_start += (uint64_t)frames * ((uint64_t)(uint32_t)s.sample | ((uint64_t)fw_bits_of(s.gain) << 32));
+    } else {  // at rest: a spatialiser set to the target whose smoothers have settled
+        s.full_range = 0;
+        s.enabled = 0;
+    }
+}
+
 // K_CROSSFADE (rendered by k_level<0>, no ext slice): the states its case renders.  T never runs behind t0: a message sets t0 = T
 FW_TYPES_HD inline bool xf_state_ok(const NodeState& s, int n_in, int n_out) {
     const auto unit = [](float x) { return x >= 0.0f && x <= 1.0f; };  // (false for a NaN)
@@ -569,6 +687,7 @@ enum : int {
     CMD_XF_TO = 23,
     CMD_RS_GLIDE = 24,
     CMD_BQ_SWEEP = 25,
+    CMD_SP_MOVE = 26,
 };
 struct Cmd {
     int state;
@@ -700,6 +819,20 @@ FW_TYPES_HD constexpr Cmd make_sp_itd(uint32_t block, float gr, int dl, int dr) 
     m.i1 = dr;
     return m;
 }
+// CMD_SP_MOVE (sp_move_start), spatialiser: (G1l, G1r), the target ear gains, as a pair in d0; i0 = the target delays, the left
+// ear's in bits 0..5 and the right ear's in bits 6..11; i1 = the frames to reach them over
+FW_TYPES_HD constexpr Cmd make_sp_move(uint32_t block, float gl, float gr, int dl, int dr, uint32_t frames) {
+    Cmd m = make_cmd(CMD_SP_MOVE, block);
+    m.i0 = (dl & 63) | ((dr & 63) << 6);
+    m.i1 = (int)frames;
+    m.d0 = fw_double_of2(gl, gr);
+    return m;
+}
+#define sp_cmd_gl(c) (fwgpu::fw_lo_float_of((c).d0))
+#define sp_cmd_gr(c) (fwgpu::fw_hi_float_of((c).d0))
+#define sp_cmd_dl(c) ((c).i0 & 63)
+#define sp_cmd_dr(c) (((c).i0 >> 6) & 63)
+#define sp_cmd_frames(c) ((uint32_t)(c).i1)
 // CMD_XF_TO, crossfader: f0 = the target position, i0 = frames, i1 = shape (XF_SHAPE_*), the Bezier's control values as pairs:
 // (x1, y1) in d0, (x2, y2) in d1
 FW_TYPES_HD constexpr Cmd make_xf_to(uint32_t block, float position, uint32_t frames, int shape, float x1, float y1, float x2, float y2) {
@@ -759,6 +892,12 @@ constexpr bool xf(uint32_t x1, uint32_t y1, uint32_t x2, uint32_t y2) {
            fw_bits_of(xf_cmd_y1(m)) == y1 && fw_bits_of(xf_cmd_x2(m)) == x2 && fw_bits_of(xf_cmd_y2(m)) == y2;
 }
 static_assert(xf(NEG0, SNAN32, 0x3f800000u, 0x7ff00000u) && xf(0x7ff00000u, 0x00000001u, SNAN32, NEG0), "CMD_XF_TO");
+constexpr bool sp(uint32_t gl, uint32_t gr, int dl, int dr, uint32_t frames) {
+    const Cmd m = make_sp_move(6u, fw_float_of(gl), fw_float_of(gr), dl, dr, frames);
+    return m.type == CMD_SP_MOVE && m.block == 6u && m.state == 0 && fw_bits_of(sp_cmd_gl(m)) == gl && fw_bits_of(sp_cmd_gr(m)) == gr &&
+           sp_cmd_dl(m) == dl && sp_cmd_dr(m) == dr && sp_cmd_frames(m) == frames;
+}
+static_assert(sp(NEG0, SNAN32, 0, 63, 1u) && sp(0x7ff00000u, 0x00000001u, 63, 0, 16777216u) && sp(0x3f800000u, NEG0, 32, 31, 0xffffffffu), "CMD_SP_MOVE");
 }  // namespace wire_check
 
 // ---------------------------------------------------------------- fused voice-bank plan

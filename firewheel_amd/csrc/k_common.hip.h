@@ -184,9 +184,11 @@ __device__ inline int chain_cmd_lower_bound(const Cmd* cmds, int n_cmds, int sta
 // every pause and stop.  (A resampling source takes pause messages too and keeps a ratio glide in the same fields: never set for one.)
 // BQ: the biquad's coefficient sweep (fwgpu_types.h bq_sweep_*) is compiled in (k_level<1> and k_single_node: the kernels that render a
 // biquad node; the chain plan's control kernel and k_chain replay a biquad's messages themselves)
-template <bool XF = false, bool SMP = false, bool BQ = false>
+// SP: the spatialiser's move (fwgpu_types.h sp_move_*) is compiled in (k_level<1>, k_single_node and the control wave's spatialiser
+// stage); sp_node: the node IS a spatialiser — it takes CMD_SP_MOVE, and a plain set_position ends a move in flight
+template <bool XF = false, bool SMP = false, bool BQ = false, bool SP = false>
 __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t block, const Cmd* cmds, int n_cmds, const SampleDesc* samples,
-                                      int lo, float* ext = nullptr, bool ext_write = false, bool smp_env = false) {
+                                      int lo, float* ext = nullptr, bool ext_write = false, bool smp_env = false, bool sp_node = false) {
     int i = lo;
     // BQ: the head of the ext slice as the messages of this block have left it so far — every lane follows it in registers (lane 0
     // alone stores it, and a later message of the same block must not read the slice back)
@@ -196,8 +198,14 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
         Cmd c = cmds[i];
         if (c.state != state_idx || c.block != block) break;
         switch (c.type) {
-            case CMD_SET_P0: s.p0 = c.f0; break;
-            case CMD_SET_P1: s.p1 = c.f0; break;
+            case CMD_SET_P0:
+                if (SP && sp_node) sp_move_stop(s);
+                s.p0 = c.f0;
+                break;
+            case CMD_SET_P1:
+                if (SP && sp_node) sp_move_stop(s);
+                s.p1 = c.f0;
+                break;
             case CMD_SET_ENABLED: s.enabled = c.i0; break;
             case CMD_SET_GAIN: s.gain = c.f0; break;
             case CMD_SET_COEFS:  // biquad coefficients live at the head of the node's ext slice
@@ -285,8 +293,14 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
             case CMD_RS_GLIDE: rs_glide_start(s, rs_cmd_step(c), (uint32_t)c.i0); break;
             case CMD_RS_SEEK: s.playhead = rs_cmd_frame(c) << 32; break;
             case CMD_SP_ITD:
+                if (SP && sp_node) sp_move_stop(s);
                 s.playing = c.i0;
                 s.has_loop = c.i1;
+                break;
+            case CMD_SP_MOVE:  // SPEC spatialiser move
+                if constexpr (SP) {
+                    if (sp_node) sp_move_start(s, sp_cmd_gl(c), sp_cmd_gr(c), sp_cmd_dl(c), sp_cmd_dr(c), sp_cmd_frames(c));
+                }
                 break;
             case CMD_XF_TO: if constexpr (XF) {  // crossfader: a new segment from where the old one stands at this block's first frame (s.playhead = T)
                 float from[1];
@@ -325,11 +339,11 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
     }
     return i;
 }
-template <bool XF = false, bool SMP = false, bool BQ = false>
+template <bool XF = false, bool SMP = false, bool BQ = false, bool SP = false>
 __device__ inline void apply_cmds(NodeState& s, int state_idx, uint32_t block, const Cmd* cmds, int n_cmds,
-                                  const SampleDesc* samples, float* ext = nullptr, bool ext_write = false, bool smp_env = false) {
+                                  const SampleDesc* samples, float* ext = nullptr, bool ext_write = false, bool smp_env = false, bool sp_node = false) {
     if (n_cmds == 0) return;
-    apply_cmds_from<XF, SMP, BQ>(s, state_idx, block, cmds, n_cmds, samples, chain_cmd_lower_bound(cmds, n_cmds, state_idx, block), ext, ext_write, smp_env);
+    apply_cmds_from<XF, SMP, BQ, SP>(s, state_idx, block, cmds, n_cmds, samples, chain_cmd_lower_bound(cmds, n_cmds, state_idx, block), ext, ext_write, smp_env, sp_node);
 }
 
 // The same lower bound by a whole wave (all 64 lanes active, arguments wave-uniform): 64 pivots per round instead of one —

@@ -209,6 +209,17 @@ __device__ __attribute__((noinline)) void env_rows(float* row0, float* row1, con
     }
 }
 
+// SPEC spatialiser move (fwgpu_types.h sp_move_*): a block inside a move gets its per-frame ear gains in the stage's two
+// ramp rows — the fade's trick — and its per-frame delays as sp_move_word in the two rows behind the gain rows (wl, wr)
+__device__ __attribute__((noinline)) void sp_move_rows(float* gl, float* gr, uint32_t* wl, uint32_t* wr, const int frames, const int lane, const SpMove mv) {
+    for (int i = lane; i < frames; i += WAVE) {
+        gl[i] = sp_move_gain(mv, 0, (uint32_t)i);
+        gr[i] = sp_move_gain(mv, 1, (uint32_t)i);
+        wl[i] = sp_move_word(sp_move_delay(mv, 0, (uint32_t)i));
+        wr[i] = sp_move_word(sp_move_delay(mv, 1, (uint32_t)i));
+    }
+}
+
 // A smoother whose next set_and_process(target) returns the same constant and leaves its state untouched:
 // not Active, or Active but stalled at the f32 fixed point above settle_epsilon (Q28).
 __device__ __forceinline__ bool smoother_is_constant(const Smoother& s, float target) {
@@ -745,7 +756,9 @@ __global__ void k_lazy_publish(unsigned long long* d_horizon, unsigned long long
 // One WAVE per voice: the state machines are run by all 64 lanes redundantly (wave-uniform; lane 0 stores),
 // the steady tail is split across the lanes.  A voice that ended the previous call steady and has no message
 // in this one skips the state machines altogether (VoiceCache): its whole call is a steady tail.
-template <bool EARLY_VC = false>
+// SPM: a spatialiser stage's move (CMD_SP_MOVE; fwgpu_types.h sp_move_*) is compiled in — the _spm kernels, which launch_voice_control
+// picks for a call that may meet a move (FusedView::sp_moves); every other call runs the kernel it ran before the move existed
+template <bool EARLY_VC = false, bool SPM = false>
 __device__ inline void voice_control_wave(const FusedView& fv, const int vi, const int lane, const int K, const uint32_t cmd_block0) {
 #ifdef FW_CTL_TRACE
     unsigned long long tr[12];
@@ -1035,6 +1048,13 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
 #pragma unroll
     for (int j = 0; j < FW_MAX_STAGES - 1; ++j)
         if (j < vd.n_stages) st[j] = *(const StageRegs*)&fv.states[vd.stage_state[j]];
+    // a spatialiser's move (CMD_SP_MOVE; fwgpu_types.h sp_move_*) lives in its state behind the StageRegs prefix: kept whole.  p0 / p1 and
+    // the delays are brought in from st[] / sp_dl / sp_dr wherever the move's functions read them
+    NodeState spn;
+    spn.full_range = 0;
+    if constexpr (SPM) {
+        if (spv) spn = fv.states[sp_state];
+    }
 
     // gain sets used so far in this call (the current one is mirrored in registers)
     int n_gsets = 0;
@@ -1106,17 +1126,34 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
 #pragma unroll
             for (int j = 0; j < FW_MAX_STAGES - 1; ++j) {
                 if (j < vd.n_stages) {
-                    NodeState tmp;  // only p0/p1 apply to gain stages (+ a spatialiser's per-ear delays: CMD_SP_ITD)
+                    // only p0/p1 apply to gain stages; a spatialiser also takes its per-ear delays (CMD_SP_ITD) and its move (CMD_SP_MOVE,
+                    // which puts both smoothers at rest at the target; a set_position in a move hands them the move's current gains)
+                    const bool spj = spv && j == sp_j;
+                    NodeState tmp;
+                    if constexpr (SPM) {
+                        if (spj) {
+                            tmp = spn;
+                            tmp.s0 = st[j].s0;
+                            tmp.s1 = st[j].s1;
+                        }
+                    }
                     tmp.p0 = st[j].p0;
                     tmp.p1 = st[j].p1;
                     tmp.playing = sp_dl;
                     tmp.has_loop = sp_dr;
-                    cur_st[j] = apply_cmds_from(tmp, vd.stage_state[j], cb, fv.cmds, fv.n_cmds, fv.samples, cur_st[j]);
+                    cur_st[j] = apply_cmds_from<false, false, false, SPM>(tmp, vd.stage_state[j], cb, fv.cmds, fv.n_cmds, fv.samples, cur_st[j], nullptr, false, false, SPM && spj);
                     st[j].p0 = tmp.p0;
                     st[j].p1 = tmp.p1;
-                    if (spv && j == sp_j) {
+                    if (spj) {
                         sp_dl = tmp.playing;
                         sp_dr = tmp.has_loop;
+                    }
+                    if constexpr (SPM) {
+                        if (spj) {
+                            st[j].s0 = tmp.s0;
+                            st[j].s1 = tmp.s1;
+                            spn = tmp;
+                        }
                     }
                 }
             }
@@ -1259,18 +1296,34 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
                 // SPEC spatialiser (k_generic.hip.h K_SPATIAL): no silence shortcut — both ear-gain smoothers advance every block,
                 // the node always writes (delayed input x gain: the last 63 frames of a voice that stopped still sound), out mask 0
                 sp_in_zero = silent;
-                GainRun rl = smoother_begin(r.s0, r.p0, frames);
-                GainRun rr = smoother_begin(r.s1, r.p1, frames);
-                if (rl.ramp && ramp_emit(rl, frames, rb, nullptr, lane)) {
-                    d.flags |= 1u << (VB_RAMP_SHIFT + 2 * (j + 1));
-                    r.s0.last = rl.prev;
+                if (SPM && spn.full_range != 0) {
+                    // inside a move: the smoothers rest at the target and are not run; the block's record is flagged by VoiceBlk::pad
+                    // (free on a sampler voice's block) and reads both ears' gains and delays per frame
+                    spn.p0 = r.p0;
+                    spn.p1 = r.p1;
+                    spn.playing = sp_dl;
+                    spn.has_loop = sp_dr;
+                    uint32_t* wrow = (uint32_t*)(ramp_base + (size_t)(fv.ramp_slots - 2) * fv.stride);
+                    sp_move_rows(rb, rb + fv.stride, wrow, wrow + fv.stride, frames, lane, sp_move_of(spn));
+                    sp_move_advance(spn, (uint32_t)frames);
+                    d.flags |= 3u << (VB_RAMP_SHIFT + 2 * (j + 1));
+                    d.pad = 1u;
+                    d.g[j + 1][0] = r.p0;
+                    d.g[j + 1][1] = r.p1;
+                } else {
+                    GainRun rl = smoother_begin(r.s0, r.p0, frames);
+                    GainRun rr = smoother_begin(r.s1, r.p1, frames);
+                    if (rl.ramp && ramp_emit(rl, frames, rb, nullptr, lane)) {
+                        d.flags |= 1u << (VB_RAMP_SHIFT + 2 * (j + 1));
+                        r.s0.last = rl.prev;
+                    }
+                    if (rr.ramp && ramp_emit(rr, frames, rb + fv.stride, nullptr, lane)) {
+                        d.flags |= 2u << (VB_RAMP_SHIFT + 2 * (j + 1));
+                        r.s1.last = rr.prev;
+                    }
+                    d.g[j + 1][0] = rl.c;
+                    d.g[j + 1][1] = rr.c;
                 }
-                if (rr.ramp && ramp_emit(rr, frames, rb + fv.stride, nullptr, lane)) {
-                    d.flags |= 2u << (VB_RAMP_SHIFT + 2 * (j + 1));
-                    r.s1.last = rr.prev;
-                }
-                d.g[j + 1][0] = rl.c;
-                d.g[j + 1][1] = rr.c;
                 silent = false;
             } else if (vd.stage_kind[j] == K_WIDTH) {  // SPEC: silent input -> reset + clear; else mid/side with
                 if (silent) {                           // the smoothed width, out mask 0 — silence passes through unchanged
@@ -1357,7 +1410,8 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
             if (vd.stage_kind[j] == K_SPATIAL) {  // (its smoothers run whatever comes in; what goes out is never flagged silent)
                 sp_zero = sil || upstream_silent;
                 sil = false;
-                if (!smoother_is_constant(r.s0, r.p0) || !smoother_is_constant(r.s1, r.p1)) ramping = true;
+                if (SPM && spn.full_range != 0) steady = false;  // a move in flight: block by block, no lazy record (as a fade or a ratio glide is)
+                else if (!smoother_is_constant(r.s0, r.p0) || !smoother_is_constant(r.s1, r.p1)) ramping = true;
                 continue;
             }
             if (sil) {  // reset() every block: idempotent once applied
@@ -1509,8 +1563,20 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
     for (int j = 0; j < FW_MAX_STAGES - 1; ++j)
         if (j < vd.n_stages) *(StageRegs*)&fv.states[vd.stage_state[j]] = st[j];
     if (spv) {
-        fv.states[sp_state].playing = sp_dl;
-        fv.states[sp_state].has_loop = sp_dr;
+        NodeState* sn = &fv.states[sp_state];
+        sn->playing = sp_dl;
+        sn->has_loop = sp_dr;
+        if constexpr (SPM) {  // (the move: fwgpu_types.h sp_move_*)
+            sn->full_range = spn.full_range;
+            sn->enabled = spn.enabled;
+            sn->phasor = spn.phasor;
+            sn->phasor_inc = spn.phasor_inc;
+            sn->playhead = spn.playhead;
+            sn->loop_start = spn.loop_start;
+            sn->loop_end = spn.loop_end;
+            sn->sample = spn.sample;
+            sn->gain = spn.gain;
+        }
     }
 }
 
@@ -1581,17 +1647,19 @@ __device__ inline bool voice_control_lane_steady(const FusedView& fv, const int 
 // waves per SIMD, ~1 % of the dynamic instructions are scratch traffic — for control-ahead mode, where a control wave has to find its
 // registers on a SIMD that holds five render waves of the call before: two of them retiring make room for the small one, three
 // (without a refill in between) for the big one, which in practice only happens once the render grid has run dry.
-template <int OCC>
+template <int OCC, bool SPM = false>
 __device__ __forceinline__ void voice_control_kernel(const FusedView& fv, const int K, const uint32_t cmd_block0) {
     const int w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (w >= fv.n_voices) return;
     // dispatch order: the voices with a message in this call (or the one before: their glides continue) go first — theirs are the
     // long waves (a glide is 22-25 us of serial latency)
     const int vi = fv.ctl_order ? __builtin_amdgcn_readfirstlane(fv.ctl_order[w]) : w;
-    voice_control_wave<true>(fv, vi, threadIdx.x & (WAVE - 1), K, cmd_block0);
+    voice_control_wave<true, SPM>(fv, vi, threadIdx.x & (WAVE - 1), K, cmd_block0);
 }
 #ifndef CTL_SMALL_OCC
 #define CTL_SMALL_OCC 3
 #endif
 __global__ __launch_bounds__(256) void k_voice_control(FusedView fv, int K, uint32_t cmd_block0) { voice_control_kernel<1>(fv, K, cmd_block0); }
 __global__ __launch_bounds__(256, CTL_SMALL_OCC) void k_voice_control_small(FusedView fv, int K, uint32_t cmd_block0) { voice_control_kernel<3>(fv, K, cmd_block0); }
+__global__ __launch_bounds__(256) void k_voice_control_spm(FusedView fv, int K, uint32_t cmd_block0) { voice_control_kernel<1, true>(fv, K, cmd_block0); }
+__global__ __launch_bounds__(256, CTL_SMALL_OCC) void k_voice_control_small_spm(FusedView fv, int K, uint32_t cmd_block0) { voice_control_kernel<3, true>(fv, K, cmd_block0); }

@@ -294,7 +294,9 @@ __device__ __forceinline__ bool kind_is_stateful(int kind) {
 // crossfader: its node time is the batch's snapshot + adv_blocks blocks
 // (always inlined, and so are spatial_finish and frozen_finish below, as they have been into every kernel that calls them: a kernel
 //  with a call in it hands its DevView over through scratch and is given the registers its launch bounds allow)
-template <int SET>
+// SPM: the spatialiser's move (CMD_SP_MOVE; fwgpu_types.h sp_move_*) is compiled in — k_level<1, true>, which launch_level picks for a
+// call that may meet a move (DevView::sp_moves), and k_single_node; every other call runs the kernel it ran before the move existed
+template <int SET, bool SPM = false>
 __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx, uint32_t blk, uint32_t cmd_block, bool store_state = true,
                                   uint32_t adv_blocks = 0, bool frozen_sampler = false) {
     const NodeDesc nd = v.nodes[node_idx];
@@ -325,7 +327,7 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
     const bool stateful = kind_is_stateful(nd.kind);
     if (stateful) {
         s = v.states[nd.state];
-        apply_cmds<SET == 0 || SET == 3, SET == 2 || SET == 3, SET == 1 || SET == 3>(s, nd.state, cmd_block, v.cmds, v.n_cmds, v.samples, v.ext, lane == 0, nd.kind == K_SAMPLER);
+        apply_cmds<SET == 0 || SET == 3, SET == 2 || SET == 3, SET == 1 || SET == 3, SPM>(s, nd.state, cmd_block, v.cmds, v.n_cmds, v.samples, v.ext, lane == 0, nd.kind == K_SAMPLER, nd.kind == K_SPATIAL);
         if (nd.kind == K_BIQUAD && v.n_cmds) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // lane 0's coefficient stores
     }
 
@@ -871,12 +873,42 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
             } else {
                 hreg = hist[lane];
             }
-            GainRun rl = smoother_begin(s.s0, s.p0, frames);
-            GainRun rr = smoother_begin(s.s1, s.p1, frames);
             const bool two = nd.n_in >= 2;
             auto mono = [&](int j) -> float {  // m[j], j >= 0
                 return two ? (io.in(0)[j] + io.in(1)[j]) * 0.5f : io.in(0)[j];
             };
+            if constexpr (SPM) if (!sp_move_at_rest(s)) {
+                // a move in flight (CMD_SP_MOVE; never frozen): per frame and ear the gain and the 32.32 delay of fwgpu_types.h sp_move_*;
+                // both taps come from where the one tap comes from at rest — history through the wave, this block through memory.  The
+                // smoothers rest at the target and are not run
+                const SpMove mv = sp_move_of(s);
+                for (int base = 0; base < frames; base += 256) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int i = base + lane * 4 + e;
+#pragma unroll
+                        for (int ear = 0; ear < 2; ++ear) {
+                            const uint64_t D = sp_move_delay(mv, ear, (uint32_t)i);
+                            const float f = sp_move_frac(D);
+                            const int ja = i - (int)sp_move_whole(D), jb = ja - 1;
+                            const float ha = __shfl(hreg, (SP_HIST + ja) & 63), hb = __shfl(hreg, (SP_HIST + jb) & 63);
+                            if (i < frames) {
+                                const float a = ja >= 0 ? mono(ja) : ha;
+                                float b = hb;
+                                if (f != 0.0f && jb >= 0) b = mono(jb);
+                                io.out(ear)[i] = sp_move_tap(a, b, f) * sp_move_gain(mv, ear, (uint32_t)i);
+                            }
+                        }
+                    }
+                }
+                sp_move_advance(s, (uint32_t)frames);
+                const int j = frames - SP_HIST + lane;
+                const float keep = __shfl(hreg, (SP_HIST + j) & 63);
+                hist[lane] = j >= 0 ? mono(j) : keep;
+                break;
+            }
+            GainRun rl = smoother_begin(s.s0, s.p0, frames);
+            GainRun rr = smoother_begin(s.s1, s.p1, frames);
             for (int base = 0; base < frames; base += 256) {
                 int n = frames - base < 256 ? frames - base : 256;
                 v4f gl = gain_chunk(rl, n, lane);
@@ -1012,7 +1044,7 @@ __global__ void k_frozen_scan(DevView v, int n_nodes, uint32_t cmd_block0, uint3
                 case K_CROSSFADE: adv = fz = true; break;
                 // SPEC spatialiser: with both gains at rest all that moves is the 64-frame mono history, and that is the
                 // tail of the previous block's input (needs a block of at least SP_HIST frames)
-                case K_SPATIAL: spat = fz = v.frames >= SP_HIST && smoother_at_rest(s.s0, s.p0) && smoother_at_rest(s.s1, s.p1); break;
+                case K_SPATIAL: spat = fz = v.frames >= SP_HIST && smoother_at_rest(s.s0, s.p0) && smoother_at_rest(s.s1, s.p1) && sp_move_at_rest(s); break;  // (a move in flight moves every block: the serial path)
                 // volume.rs:104: a gain below 1e-5 is a mute only while the smoother is Inactive — keep such a node
                 // on the serial path while it is Deactivating (the status matters there)
                 case K_VOLUME: fz = smoother_at_rest(s.s0, s.p0) && (s.s0.status == SM_INACTIVE || !(s.s0.input < 0.00001f)); break;
@@ -1499,7 +1531,7 @@ __device__ __forceinline__ uint32_t frozen_fast(const DevView& v, const int node
 #ifndef LEVEL_MINW
 #define LEVEL_MINW 3
 #endif
-template <int SET>
+template <int SET, bool SPM = false>
 __global__ __launch_bounds__(WAVE* WPB, LEVEL_MINW) void k_level(DevView v, const int* __restrict__ level_nodes, int n_nodes,
                                                       uint32_t cmd_block0, uint32_t K, uint32_t bpw, uint32_t walkers) {
     int w = blockIdx.x * WPB + (threadIdx.x >> 6);
@@ -1525,7 +1557,7 @@ __global__ __launch_bounds__(WAVE* WPB, LEVEL_MINW) void k_level(DevView v, cons
             uint32_t todo = bpw > 1 ? frozen_fast<SET>(v, node, fz, b0, b1, K, skip) : ~0u;  // (what is left goes block by block)
             todo &= ~skip;
             for (uint32_t b = b0; b < b1; ++b)
-                if ((todo >> ((b - b0) & 31u)) & 1u) node_process_wave<SET>(v, node, b, cmd_block0 + b, adv && b + 1 == K, adv ? b : 0u, adv || spat);
+                if ((todo >> ((b - b0) & 31u)) & 1u) node_process_wave<SET, SPM>(v, node, b, cmd_block0 + b, adv && b + 1 == K, adv ? b : 0u, adv || spat);
             if (spat) {
                 if (b0 == 0) spatial_finish(v, node, K);
             } else if (!adv && b0 == 0) {
@@ -1537,9 +1569,9 @@ __global__ __launch_bounds__(WAVE* WPB, LEVEL_MINW) void k_level(DevView v, cons
         if constexpr (SET == 1) {  // (a bus filter / delay the batch walkers take: k_bus_iir, launched next to this kernel)
             if (walkers && (biquad_walk_ok(v, v.nodes[node], cmd_block0, K) || delay_walk_ok(v, v.nodes[node], cmd_block0, K))) return;
         }
-        for (uint32_t b = 0; b < K; ++b) node_process_wave<SET>(v, node, b, cmd_block0 + b);
+        for (uint32_t b = 0; b < K; ++b) node_process_wave<SET, SPM>(v, node, b, cmd_block0 + b);
     } else {
-        for (uint32_t b = b0; b < b1; ++b) node_process_wave<SET>(v, node, b, cmd_block0 + b);
+        for (uint32_t b = b0; b < b1; ++b) node_process_wave<SET, SPM>(v, node, b, cmd_block0 + b);
     }
 }
 

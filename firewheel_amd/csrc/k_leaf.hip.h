@@ -875,7 +875,8 @@ __device__ __forceinline__ void leaf_sp_fast(const FusedView& fv, const LeafDesc
 // p's stage program.  The gains-only instantiation is the headline kernel and does not pay for the other ones' registers.
 // LAZY (round 4, fwgpu_types.h LazyRec): no control kernel ran for this call — lane p computes port p's record from the voice's
 // LazyRec (one 128-byte load: descriptor AND gains) and the block index.
-template <bool PROG, bool RS = false, int U = LEAF_U, bool SP = false, bool LAZY = false>
+// SPM: a spatialiser voice's move blocks (VoiceBlk::pad; fwgpu_types.h sp_move_word) are compiled in — the _spm kernels only
+template <bool PROG, bool RS = false, int U = LEAF_U, bool SP = false, bool LAZY = false, bool SPM = false>
 __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int leaf, const uint32_t k, const int part, const int wpk,
                                               const RsLds rs = RsLds{nullptr, nullptr}, const int K = 1, float* sp_lds = nullptr, float* sp_tails = nullptr,
                                               bool* sp_tails_valid = nullptr) {
@@ -1100,6 +1101,22 @@ __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int lea
                             const VoiceBlk d = fv.blks[row + p];
                             const uint32_t rbits = (d.flags & VB_RAMP_MASK) >> VB_RAMP_SHIFT;
                             const float* rb = fv.ramps + ((size_t)k * fv.n_voices + voice) * (size_t)fv.ramp_slots * (size_t)fv.stride + (act ? f0 : 0);
+                            if constexpr (SPM) if (d.pad != 0u) {
+                                // a block inside a move (SPEC): each frame's delay per ear is a 32-bit word in the two rows behind
+                                // the gain rows (fwgpu_types.h sp_move_word); the second tap comes from the same LDS row as the first
+                                typedef uint32_t v4u_sp __attribute__((ext_vector_type(4)));
+                                const uint32_t* wrow = (const uint32_t*)(rb + (size_t)(fv.ramp_slots - 2) * fv.stride);
+                                const v4u_sp wl = *(const v4u_sp*)wrow, wr = *(const v4u_sp*)(wrow + fv.stride);
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) {
+                                    const float* at = sp_lds + SP_HIST + lane * 4 + e;
+                                    const float fl = sp_word_frac(wl[e]), fr = sp_word_frac(wr[e]);
+                                    const float* al = at - sp_word_whole(wl[e]);
+                                    const float* ar = at - sp_word_whole(wr[e]);
+                                    ml[e] = sp_move_tap(al[0], fl != 0.0f ? al[-1] : 0.0f, fl);
+                                    mr[e] = sp_move_tap(ar[0], fr != 0.0f ? ar[-1] : 0.0f, fr);
+                                }
+                            }
                             gl = gr = splat(1.0f);
 #pragma unroll
                             for (int j = 1; j < FW_MAX_STAGES; ++j)
@@ -1304,7 +1321,7 @@ __device__ __forceinline__ RsLds rs_lds_setup(const FusedView& fv, float* dyn) {
 //   <true,  false>  stage programs (width / hard clip)
 //   <true,  true>   ... and voices whose source is a resampler (LDS-staged polyphase fetch)
 //   <true,  false, true>  ... and voices that end in a spatialiser (a 320-float mono row per wave in LDS)
-template <bool PROG, bool RS, bool SP, bool LAZY = false>
+template <bool PROG, bool RS, bool SP, bool LAZY = false, bool SPM = false>
 __device__ __forceinline__ void leaf_kernel_body(const FusedView& fv, const int K, const int wpk, const int sp_nb = 1) {
     extern __shared__ float s_leaf_dyn[];
     RsLds rs{nullptr, nullptr};
@@ -1324,7 +1341,7 @@ __device__ __forceinline__ void leaf_kernel_body(const FusedView& fv, const int 
             for (uint32_t kk = 0; kk < (uint32_t)sp_nb && k0 + kk < (uint32_t)K; ++kk) {
                 int leaf_k = leaf;  // (opaque per iteration: what a block reads per lane — gain sets, programs — is loaded per block, not
                 asm volatile("" : "+s"(leaf_k));  // hoisted out of the loop into a dozen registers that live across all of it)
-                leaf_sum_wave<PROG, RS, LEAF_U, SP, LAZY>(fv, leaf_k, k0 + kk, 0, 1, rs, K, sp_lds, s_tails + wave * (32 * SP_HIST), &tv);
+                leaf_sum_wave<PROG, RS, LEAF_U, SP, LAZY, SPM>(fv, leaf_k, k0 + kk, 0, 1, rs, K, sp_lds, s_tails + wave * (32 * SP_HIST), &tv);
             }
             return;
         }
@@ -1344,7 +1361,7 @@ __device__ __forceinline__ void leaf_kernel_body(const FusedView& fv, const int 
     if (leaf >= fv.n_leaves) return;
     const uint32_t k = blockIdx.y;
 #endif
-    leaf_sum_wave<PROG, RS, LEAF_U, SP, LAZY>(fv, leaf, k, part, wpk, rs, K, sp_lds);
+    leaf_sum_wave<PROG, RS, LEAF_U, SP, LAZY, SPM>(fv, leaf, k, part, wpk, rs, K, sp_lds);
 }
 template <bool PROG, bool RS, bool SP = false>
 __global__ __launch_bounds__(WAVE* LEAF_WPB) void k_leaf_sum(FusedView fv, int K, int wpk) {
@@ -1357,6 +1374,13 @@ __global__ __launch_bounds__(WAVE* LEAF_WPB) void k_leaf_sum(FusedView fv, int K
 #endif
 __global__ __launch_bounds__(WAVE* LEAF_WPB, SP_OCC) void k_leaf_sum_sp(FusedView fv, int K, int wpk, int sp_nb) {
     leaf_kernel_body<true, false, true>(fv, K, wpk, sp_nb);
+}
+// the two spatialiser kernels for a call that may meet a move (FusedView::sp_moves): the same, with the move blocks' two-tap read
+__global__ __launch_bounds__(WAVE* LEAF_WPB, SP_OCC) void k_leaf_sum_sp_spm(FusedView fv, int K, int wpk, int sp_nb) {
+    leaf_kernel_body<true, false, true, false, true>(fv, K, wpk, sp_nb);
+}
+__global__ __launch_bounds__(WAVE* LEAF_WPB) void k_leaf_sum_rs_sp_spm(FusedView fv, int K, int wpk) {
+    leaf_kernel_body<true, true, true, false, true>(fv, K, wpk);
 }
 // the same kernel for a call no control kernel ran for (plans without resampler sources / spatialiser stages)
 template <bool PROG>

@@ -2,6 +2,9 @@
 // kernels: it runs every node kind, k_level's and the three that bring a kernel of their own.
 // A limiter, a ducker or a latency-compensation delay renders one block through its stored history, which the call leaves advanced; one
 // node never needs both kinds' LDS, and the delay needs none
+// SPM: the build for a spatialiser (launch_single_node: DevView::sp_moves) — it takes CMD_SP_MOVE and renders a move; every other kind
+// runs the build without it
+template <bool SPM>
 __global__ __launch_bounds__(WAVE) void k_single_node(DevView v, int node_idx) {
     __shared__ union {
         LimLds lim;
@@ -29,5 +32,5 @@ __global__ __launch_bounds__(WAVE) void k_single_node(DevView v, int node_idx) {
         dcomp_history(v, p, 1);
         return;
     }
-    node_process_wave<3>(v, node_idx, 0, 0);
+    node_process_wave<3, SPM>(v, node_idx, 0, 0);
 }

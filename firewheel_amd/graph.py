@@ -389,6 +389,26 @@ class SpatialNode(_Node):  # SPEC node: 3D spatialiser — distance gain, equal-
         for i, v in enumerate(self.pos):
             self._set(i, v, at_block)
 
+    MOVE_FRAMES_MAX = 1 << 24
+
+    def move_to(self, x, y, z, frames, at_block=0):
+        """from block `at_block` of the next process call on, move the source to (x, y, z) over `frames` frames (0: a step, as
+        set_position): the ear gains travel linearly and per frame and the per-ear delays glide as 32.32 fractions of a frame, read
+        with a two-tap blend — ONE message for a source that crosses the stereo image without a click, instead of a set_position
+        per block, whose whole-frame delays step (fwgpu_spatial_move).  A second move starts from where the first stands; a
+        set_position during a move ends it.  `self.pos` holds the TARGET from this call on.  A fly-by moves place and pitch in the
+        same tick, the spatialiser and the resampling source in front of it:
+
+            spat.move_to(+8.0, 0.0, -2.0, frames)                                  # from the left of the listener to the right
+            src.glide_to(doppler_ratio(1.0, radial_speed_at_the_end), frames)      # ... while the pitch drops
+        """
+        self.cx._check(self.cx.L.fwgpu_spatial_move(self.cx.c, self.id, x, y, z, frames, at_block))
+        self.pos = [x, y, z]
+
+    def move_to_secs(self, x, y, z, secs, at_block=0):
+        """move_to with the length in seconds of the context's sample rate"""
+        self.move_to(x, y, z, max(0, int(round(secs * self.cx.sample_rate))), at_block)
+
 
 class HostNode(_Node):
     """any other `dyn AudioNodeProcessor` (graph/processor.rs:243) inside a device-resident graph: `process` runs on the host,

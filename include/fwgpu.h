@@ -676,6 +676,27 @@ int fwgpu_crossfade_to(fwgpu_ctx* ctx, int64_t node, float position, uint32_t fr
 #define FWGPU_RESAMPLER_GLIDE_FRAMES_MAX 16777216
 int fwgpu_resampler_glide(fwgpu_ctx* ctx, int64_t node, float ratio, uint32_t frames, uint32_t at_block);
 
+/* ---- spatialiser: a move of the source in one message (SPEC).
+ * fwgpu_spatial_move: from the first frame of block `at_block` of the next process call, move the node from where it stands to what
+ * params 0..2 would set for (x, y, z) — the ear gains G1l, G1r and the whole per-ear delays d1l, d1r (0..63 frames) — over `frames`
+ * frames, per frame.  With, per ear, G0 the gain in force at that block's first frame (a move in flight: its value there; else the
+ * smoother's output), D0 the delay there as an unsigned 32.32 number (at rest d << 32), N = frames, and k the frames of the move
+ * rendered so far:
+ *   inc = (int64)((d1 << 32) - D0) / (int64)N   (truncated toward zero),   both smoothers are put at rest at the target gains
+ *   frame t = k + j < N:  g = clamp(G0 + ((G1 - G0) * ((float)t / (float)N)), min(G0, G1), max(G0, G1)),   D = D0 + t * inc
+ *   frame t >= N:         g = G1,   D = d1 << 32 exactly
+ *   q = D >> 32,  f = (float)((uint32_t)D >> 8) * 2^-24,  a = m[i - q],  x = f == 0 ? a : a + ((m[i - q - 1] - a) * f),  out = x * g
+ * every operation a separately rounded f32 operation, the division IEEE, no FMA; m is the mono row with its 64 frames of history.  D
+ * stays between D0 and d1 << 32, so f != 0 implies q <= 62.  Behind a rendered block k += the block's frames; once k >= N the node is
+ * at rest at the target, bit for bit a spatialiser set there whose smoothers have settled.  There is no silence shortcut: a move
+ * advances in every block.  frames == 0 is a step: it queues the three messages that the last of three param calls for that position queues.  A second move starts from where the first stands;
+ * a param 0 / 1 / 2 during a move ends it: the gains glide on from the move's current values on the smoothers, the delays step.
+ * Several messages for one block apply in send order.  A voice inside a move is not steady: its calls run the control kernel, and
+ * lazy calls resume with the first call behind the move.  The node's position as params 0..2 see it is the move's target from this
+ * call on.  FWGPU_ERR_INVALID for a node of another kind, a NaN coordinate, or frames > FWGPU_SPATIAL_MOVE_FRAMES_MAX. */
+#define FWGPU_SPATIAL_MOVE_FRAMES_MAX 16777216
+int fwgpu_spatial_move(fwgpu_ctx* ctx, int64_t node, float x, float y, float z, uint32_t frames, uint32_t at_block);
+
 /* ---- biquad: a coefficient sweep (a moving cutoff) in one message (SPEC).
  * fwgpu_biquad_sweep: from the first frame of block `at_block` of the next process call, move the node's five coefficients
  * (b0, b1, b2, a1, a2) to the ones params 1 and 2 would set for `cutoff_hz` and `q` — T, computed in f64 with the same clamps and

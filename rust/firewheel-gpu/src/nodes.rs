@@ -500,6 +500,25 @@ param_node!(GpuDelayNode, "delay", ffi::FWGPU_DELAY, io(1, 64, 1, 64, false),
 param_node!(GpuSpatialNode, "spatial", ffi::FWGPU_SPATIAL, io(1, 2, 2, 2, false),
             "3D spatialiser: inverse-distance gain, equal-power pan from the direction cosine, per-ear delay (listener at the origin, -z forward)",
             [x, y, z], {set_x => (0, x), set_y => (1, y), set_z => (2, z)});
+impl GpuSpatialNode {
+    /// the longest move one message takes, in frames
+    pub const MOVE_FRAMES_MAX: u32 = ffi::FWGPU_SPATIAL_MOVE_FRAMES_MAX;
+    /// From the next block on, move the source to (`x`, `y`, `z`) over `frames` frames (0: a step, as the setters): the ear gains
+    /// travel linearly and per frame, the per-ear delays glide as fractions of a frame — one message for a source that crosses the
+    /// stereo image without a click.  A second move starts from where the first stands; a setter during a move ends it.  Before
+    /// activation only the target is kept: the node then starts there.  The node's recorded position is the TARGET from this call on.
+    pub fn move_to(&mut self, x: f32, y: f32, z: f32, frames: u32) -> Result<(), GpuError> {
+        if let Some(node) = self.b.node {
+            let _g = self.b.cx.control();
+            let rc = unsafe { ffi::fwgpu_spatial_move(self.b.cx.as_ptr(), node, x, y, z, frames, 0) };
+            self.b.cx.check(rc as i64)?;
+        }
+        self.x = x;
+        self.y = y;
+        self.z = z;
+        Ok(())
+    }
+}
 
 /// FIR / convolution reverb: the impulse response is a [`GpuSample`] named at construction (kept alive by the node).
 pub struct GpuFirReverbNode {
