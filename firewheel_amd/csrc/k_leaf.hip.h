@@ -28,7 +28,7 @@ __device__ __forceinline__ void apply_stage(uint32_t kind, v4f g0, v4f g1, v4f& 
 // `prog`: the voice's stage program (4 bits per chain stage; 0 everywhere on a gains-only voice)
 // LDS of the leaf kernel's program instantiation, for voices whose source is a resampler: the 2 KiB filter bank once per
 // workgroup, and per wave the window of source frames its 256 output frames of ONE port read (both channels)
-#define RS_WIN 1040  // window frames a wave can stage: 256 output frames x ratio <= 4, + RS_TAPS
+#define RS_WIN 1040  // window frames a wave can stage: 256 output frames x ratio < 4 (ceil(256 x ratio) + 1 + RS_TAPS: up to 3.996; 4.0 needs 1041)
 struct RsLds {
     const float* tab;  // the filter bank in LDS, tap-major [RS_TAPS][RS_PHASES] (nullptr: no resampler voices in the plan)
     float* win;        // this wave's window [2][RS_WIN], then its result rows [2][256]
