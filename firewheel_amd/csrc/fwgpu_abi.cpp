@@ -322,6 +322,8 @@ fwgpu_ctx* fwgpu_ctx_create(int device, uint32_t sample_rate, uint32_t max_block
             c->lazy_on = false;
         }
     }
+    if (const char* e = getenv("FWGPU_LEAF_GROUP")) c->group_on = atoi(e) != 0;
+    if (const char* e = getenv("FWGPU_LEAF_GROUP_MIN")) c->group_min_items = (uint32_t)std::max(1, atoi(e));
     if (const char* e = getenv("FWGPU_RT_PERSIST")) c->rt_persist = atoi(e) != 0;
     if (const char* e = getenv("FWGPU_LEVEL_FUSE")) c->level_fuse = atoi(e) != 0;
     if (const char* e = getenv("FWGPU_GATE_DEFER_US")) c->gate_defer_ns = (uint64_t)std::max(0, atoi(e)) * 1000ull;
@@ -763,6 +765,11 @@ int fwgpu_lazy_stats(fwgpu_ctx* c, uint64_t* lazy_batches, uint64_t* control_bat
     NEED_CTX(c, FWGPU_ERR_INVALID);
     if (lazy_batches) *lazy_batches = c->lazy_calls;
     if (control_batches) *control_batches = c->ctl_calls;
+    return 0;
+}
+int fwgpu_plan_group_stats(fwgpu_ctx* c, uint64_t* grouped_batches) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    if (grouped_batches) *grouped_batches = c->group_calls;
     return 0;
 }
 void* fwgpu_hip_stream(fwgpu_ctx* c) { return c ? (void*)c->stream : nullptr; }

@@ -226,6 +226,7 @@ struct PlanImage {
     int chain_words = 0;
     int up_root_node = -1;  // index (in the upper-tree node table) of the root SumNode when it is alone on the last level
     RootArgs root_args;     // that node's port table, handed to k_root_out in its kernel arguments
+    bool group_ok = false;  // the tree is leaves -> root and root port p is leaf p's bus: a steady call may be rendered by k_leaf_group_lazy
 
     // FIR banks (generic executor): rows grouped by (level, impulse-response channel)
     struct FirGroup {  // one GEMM launch: every FIR row of a level with the same tap count
@@ -432,6 +433,12 @@ struct fwgpu_ctx : fwgpu::PlanImage {
     // plan) — adopt_image extends the bound by it, so the call a parked node returns in runs the move builds until its move is over
     uint32_t sp_move_max_n = 0, sp_move_parked_n = 0;
     StatCounter lazy_calls, ctl_calls;           // fused batches rendered without / with a control kernel (fwgpu_lazy_stats)
+    // Grouped calls: a lazy batch of a voice-bank plan whose tree is leaves -> root -> stereo out is rendered by ONE
+    // kernel, k_leaf_group_lazy — leaf sums stay on chip, k_root_out does not run.  FWGPU_LEAF_GROUP=0|1 (read at creation) switches
+    // it; group_min_items: the smallest K x (256-frame pieces per block) that is grouped (FWGPU_LEAF_GROUP_MIN; profiles/README.md)
+    bool group_on = FWGPU_LEAF_GROUP_DEFAULT;
+    uint32_t group_min_items = FWGPU_LEAF_GROUP_MIN_DEFAULT;
+    StatCounter group_calls;                     // batches rendered that way (fwgpu_plan_group_stats)
     int ctl_ahead_mode = 2;          // 1 = every qualifying call (round 3), 2 = only calls with messages / continuing glides (round 4)
     hipStream_t ctl_stream = nullptr;
     hipEvent_t ev_ctl[2] = {nullptr, nullptr}, ev_render[2] = {nullptr, nullptr}, ev_join = nullptr;

@@ -110,6 +110,7 @@ int launch_bus_sum(hipStream_t s, const DevView& v, const int* d_level_nodes, in
 }
 int launch_root_out(hipStream_t s, const DevView& v, const RootArgs& root, float* d_out, int K) {
     if (v.frames <= 0 || K <= 0) return 0;
+    if (root.grouped) return 0;  // a grouped call: k_leaf_group_lazy added the root and wrote d_out (launch_leaf_sum_lazy below)
     hipLaunchKernelGGL(k_root_out, dim3((v.frames + 255) / 256, K), dim3(256), 0, s, v, root, d_out);
     return (int)hipGetLastError();
 }
@@ -329,6 +330,14 @@ int launch_sp_hist_copy(hipStream_t s, const FusedView& fv) {
 }
 int launch_leaf_sum_lazy(hipStream_t s, const FusedView& fv, int K) {
     if (fv.n_leaves <= 0) return 0;
+    if (fv.group) {  // leaves + root of every (block, 256-frame piece) in one workgroup: no leaf-bus rows, no k_root_out
+        if (K <= 0 || fv.frames <= 0 || fv.n_leaves > 32 || fv.group_out == nullptr || fv.group_ports != fv.n_leaves) return (int)hipErrorInvalidValue;
+        const dim3 grid((fv.frames + 255) / 256, K), block(WAVE * LEAF_GROUP_G);
+        const size_t lds = leaf_group_lds_bytes(fv.n_leaves, LEAF_GROUP_G);
+        if (fv.has_prog) hipLaunchKernelGGL((k_leaf_group_lazy<true, LEAF_GROUP_G, LEAF_GROUP_U>), grid, block, lds, s, fv, K);
+        else hipLaunchKernelGGL((k_leaf_group_lazy<false, LEAF_GROUP_G, LEAF_GROUP_U>), grid, block, lds, s, fv, K);
+        return (int)hipGetLastError();
+    }
     const int wpk = (fv.frames % (256 * LEAF_WPB) == 0) ? LEAF_WPB : (fv.frames % 512 == 0 && LEAF_WPB % 2 == 0) ? 2 : 1;
     const int bpw = LEAF_WPB / wpk;
     dim3 grid(fv.n_leaves, (K + bpw - 1) / bpw);

@@ -126,6 +126,13 @@ struct FusedView {
     const int* rt_kids = nullptr;
     unsigned* rt_tree_sync = nullptr;
     int rt_root = -1;
+    // a grouped call (fwgpu_run.cpp run_fused_batch; k_leaf.hip.h k_leaf_group_lazy): launch_leaf_sum_lazy renders the leaves AND the root
+    // of every block in one kernel — the root's port count, where the interleaved frames go, and the mark.  Zero everywhere else.
+    // (Of the root's RootArgs only `ports` travels: root port p IS leaf p's bus pair on such a plan — PlanImage::group_ok — so the kernel
+    //  needs no port table, and a whole RootArgs here would be 280 bytes of kernel arguments for every kernel that takes a FusedView.)
+    int group_ports = 0;
+    float* group_out = nullptr;
+    int group = 0;
     unsigned long long* trace;  // FW_CHAIN_TRACE builds only: per-step role timestamps of workgroup 0
     int dbg;     // FW_CHAIN_TRACE builds only (env FWGPU_CHAIN_SKIP): bit 0 skip S2, 1 skip S3b, 2 skip source loads,
                  // 3 skip ring RMW, 4 no ring prefetch

@@ -364,6 +364,7 @@ static void reset_for_build(fwgpu_ctx* c, PlanImage& P) {
     P.hot_prev.clear();
     P.hot_now.clear();
     P.ctl_order_live = false;
+    P.group_ok = false;
     P.fused = P.fused_fx = P.ctl_ahead_on = P.fused_rs = P.fused_prog = P.fused_sp = P.hybrid = P.hybrid_fx = P.lazy_capable = false;
     P.generic_k = 1;
     P.chain_nq = 1;
@@ -1091,6 +1092,12 @@ static int install_fused_plan(ImageBuild& b) {
         } else {
             P.up_root_node = -1;
         }
+    }
+    // a grouped call's shape (k_leaf_group_lazy): the root is the only mixer above the leaves and its port p is leaf p's bus pair
+    P.group_ok = P.up_root_node >= 0 && P.up_level_cnt.size() == 1 && P.n_tail == 0 && P.n_leaves >= 1 && P.n_leaves <= 32 && P.root_args.ports == P.n_leaves;
+    for (int p = 0; p < P.n_leaves && P.group_ok; ++p) {
+        const LeafDesc& ld = fb.leaves[(size_t)p];
+        P.group_ok = ld.pad == 0 && ld.ports >= 1 && ld.ports <= 32 && P.root_args.in_buf[2 * p] == ld.out_buf && P.root_args.in_buf[2 * p + 1] == ld.out_buf + 1;
     }
     if ((rc = upload_rt_tree(b))) return rc;
     P.fused = true;

@@ -725,6 +725,18 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
         }
     }
     c->abs_blk += (uint64_t)K;
+    // A grouped call: a steady batch of a plain voice-bank plan whose tree is leaves -> root -> stereo out, and big enough to fill the
+    // chip with one workgroup per (block, 256-frame piece), is rendered by k_leaf_group_lazy alone.  The launch sequence below does not
+    // change: launch_leaf_sum_lazy sees the mark in its FusedView, launch_root_out the one in its RootArgs and launches nothing.
+    RootArgs root = c->root_args;
+    if (lazy && c->group_on && c->group_ok && !c->fused_rs && !c->fused_fx && !c->fused_sp && c->up_level_cnt.size() == 1 && c->up_root_node >= 0 &&
+        n_out_ch == 2 && c->n_tail == 0 && (uint64_t)K * (uint64_t)((c->mbf + 255) / 256) >= (uint64_t)c->group_min_items) {
+        fv.group_ports = c->root_args.ports;
+        fv.group_out = d_out;
+        fv.group = 1;
+        root.grouped = 1;
+        c->group_calls++;
+    }
     timer_begin(c, 0, &e0, &e1);
     if (fv.sp_hist_in_render) LCHK(c, launch_sp_hist_copy(c->stream, fv));
     if (c->fused_fx) LCHK(c, launch_chain(c->stream, fv, K, cmd_block0, c->chain_nq | (c->bq_sweep_live ? 16 : 0)));
@@ -757,7 +769,7 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
         for (size_t l = 0; l < n_levels; ++l)
             LCHK(c, launch_bus_sum(c->stream, v, c->d_up_level_nodes.as<int>() + c->up_level_off[l], c->up_level_cnt[l], K, 2));
         if (fuse_root) {
-            LCHK(c, launch_root_out(c->stream, v, c->root_args, d_out, K));
+            LCHK(c, launch_root_out(c->stream, v, root, d_out, K));
             if (c->out_sil)  // the root's out-mask (k_root_out keeps it in registers): recomputed from its inputs' flags
                 LCHK(c, launch_out_flags(c->stream, v.flags, v.flags_blk_stride, c->root_args.in_tab, c->root_args.n_in, 1, n_out_ch, K,
                                          c->out_sil + (size_t)cmd_block0 * n_out_ch));

@@ -1097,11 +1097,24 @@ struct FirRow {  // one GEMM row = one channel of one FIR node
 #define CH_FAST_KMAX 64  // blocks per k_chain launch its steady-call loop keeps per-block source addresses for (LDS);
                          // the host never batches more blocks than this into one chain-plan launch
 
+// grouped calls (k_leaf.hip.h k_leaf_group_lazy): the default of the FWGPU_LEAF_GROUP switch, and the smallest K x pieces that is grouped
+#ifndef FWGPU_LEAF_GROUP_DEFAULT
+#define FWGPU_LEAF_GROUP_DEFAULT true
+#endif
+#ifndef FWGPU_LEAF_GROUP_MIN_DEFAULT
+// measured (profiles/leaf_group_sizes.jsonl; ms per call grouped / two kernels): 16 items 0.133 / 0.019, 64 items 0.135 / 0.032, 256 items
+// (block 1024 x K = 64) 0.150 / 0.102, 768 items 0.260 / 0.288 — a workgroup walks all the root's leaves, ~130 us whatever the grid, so the
+// call pays only once the grid gives every CU work: 768 is the smallest measured size at which the grouped call is not slower
+#define FWGPU_LEAF_GROUP_MIN_DEFAULT 768u
+#endif
 // the root SumNode of a fused plan, passed to k_root_out by value (kernel arguments: scalar loads, no dependent fetch)
 struct RootArgs {
     int n_in, ports;  // ports = n_in / 2 stereo ports (<= 32)
     int in_buf[64];   // bus buffer of input channel i
     const int* in_tab;  // the same table in device memory (for per-lane indexing)
+    int grouped;        // 1: k_leaf_group_lazy rendered this batch's root already (a grouped call, fwgpu_run.cpp): launch_root_out launches
+                        // nothing.  0 in the plan's own copy and on every other path.
+    int pad_;
 };
 
 // k_chain plan: what the two channel workgroups of a voice share, as it stood at the START of the current call

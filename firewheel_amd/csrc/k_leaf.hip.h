@@ -876,67 +876,99 @@ __device__ __forceinline__ void leaf_sp_fast(const FusedView& fv, const LeafDesc
 // LAZY (round 4, fwgpu_types.h LazyRec): no control kernel ran for this call — lane p computes port p's record from the voice's
 // LazyRec (one 128-byte load: descriptor AND gains) and the block index.
 // SPM: a spatialiser voice's move blocks (VoiceBlk::pad; fwgpu_types.h sp_move_word) are compiled in — the _spm kernels only
-template <bool PROG, bool RS = false, int U = LEAF_U, bool SP = false, bool LAZY = false, bool SPM = false>
-__device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int leaf, const uint32_t k, const int part, const int wpk,
-                                              const RsLds rs = RsLds{nullptr, nullptr}, const int K = 1, float* sp_lds = nullptr, float* sp_tails = nullptr,
-                                              bool* sp_tails_valid = nullptr) {
-    const int lane = threadIdx.x & (WAVE - 1);
-    const LeafDesc ld = fv.leaves[leaf];
-    const int frames = fv.frames;
-    const size_t row = (size_t)k * fv.n_voices + ld.first_voice;
-    float* bus = fv.bus + (size_t)k * fv.bus_blk_stride;
-    uint8_t* bflags = fv.bus_flags + (size_t)k * fv.bus_flags_blk_stride;
-    float* outl = bus + (size_t)ld.out_buf * fv.stride;
-    float* outr = outl + fv.stride;
-
-    // lane p loads the compact record of port p (ports <= 32); in_silence_mask: both channels share one flag
-    VoiceRef ref;
-    ref.src_l = nullptr;
-    ref.r_delta = 0;
-    ref.flags_gset = VB_SILENT;
+// A leaf wave's work in three parts (k_leaf_sum and its kin run them back to back for one leaf; k_leaf_group_lazy walks a run of
+// leaves, with the NEXT leaf's record loads issued before the current leaf streams):
+//   1. the records: lane p loads port p's (leaf_recs_issue: the loads alone, nothing waited for) and makes of them what the frame
+//      loop reads with v_readlane (leaf_recs_finish: source address, gains, the pinning under the full exec mask);
+//   2. one 256-frame piece: leaf_classify (which ports are silent / plain / resampler voices: ballots, once per leaf) and leaf_piece
+//      (the ports added in order into accl / accr);
+//   3. the store of the two bus rows and the out flags — leaf_sum_wave's own.
+struct LeafRaw {     // what lane p loaded for port p
+    VoiceRef ref;    // non-lazy: the block's compact record; lazy: r_delta and flags_gset of the LazyRec (src_l follows in finish)
+    GainSet g0;      // gain set 0 (lazy: the LazyRec's gains)
+    uint64_t base, off0;  // lazy: LazyRec fields the block's source address is computed from
+    uint32_t q, r0b, bpf;
+    int mode;
+    uint32_t prog;
+};
+struct LeafLane {    // what lane p holds of port p, pinned
+    uint32_t flags_gset;
+    const float* my_l;
+    const float* my_r;  // planar f32 class only
+    uint32_t my_rd, my_cls, my_prog;
     GainSet my_g;
+};
+template <bool PROG, bool LAZY>
+__device__ __forceinline__ LeafRaw leaf_recs_issue(const FusedView& fv, const LeafDesc& ld, const uint32_t k, const int lane) {
+    // lane p loads the compact record of port p (ports <= 32); in_silence_mask: both channels share one flag
+    LeafRaw w;
+    w.ref.src_l = nullptr;
+    w.ref.r_delta = 0;
+    w.ref.flags_gset = VB_SILENT;
 #pragma unroll
-    for (int j = 0; j < FW_MAX_STAGES; ++j) my_g.g[j][0] = my_g.g[j][1] = 1.0f;
+    for (int j = 0; j < FW_MAX_STAGES; ++j) w.g0.g[j][0] = w.g0.g[j][1] = 1.0f;
+    w.base = w.off0 = 0ull;
+    w.q = 1u;
+    w.r0b = w.bpf = 0u;
+    w.mode = 0;
+    w.prog = 0u;
 #if LEAF_SPEC_GSET
-    GainSet g0 = my_g;
     if constexpr (LAZY) {
         if (lane < ld.ports) {
             const LazyRec* lr = fv.lazy + (ld.first_voice + lane);
-            const uint64_t base = lr->base, off0 = lr->off0;
-            const uint32_t q = lr->q, r0b = lr->r0b, bpf = lr->bpf;
-            const int mode = lr->mode;
-            ref.r_delta = lr->r_delta;
-            ref.flags_gset = lr->flags_gset;
-            g0 = lr->g;
-            // the block's source address: what steady_tail's lean record would hold — (r0 + block * frames) mod L from the loop
-            // start (L a whole number of blocks: no block wraps inside itself), or straight on for a one-shot
-            const uint64_t bi = fv.lazy_blk0 + (uint64_t)k;
-            if (ref.flags_gset & VB_SIMPLE) {  // (frames into the record's source, then bytes: the classes differ in bytes per frame)
-                const uint64_t fo = mode == 1 ? (uint64_t)((r0b + bi) % q) * (uint64_t)(uint32_t)frames : off0 + bi * (uint64_t)(uint32_t)frames;
-                ref.src_l = (const float*)(base + fo * bpf);
-            }
+            w.base = lr->base;
+            w.off0 = lr->off0;
+            w.q = lr->q;
+            w.r0b = lr->r0b;
+            w.bpf = lr->bpf;
+            w.mode = lr->mode;
+            w.ref.r_delta = lr->r_delta;
+            w.ref.flags_gset = lr->flags_gset;
+            w.g0 = lr->g;
         }
     } else if (lane < ld.ports) {  // (slot 0 may hold anything on a voice that is not VB_SIMPLE this block: then it is not used)
-        g0 = fv.gsets[(size_t)(ld.first_voice + lane) * FW_GSETS];
-        ref = fv.refs[ref_index(ld.first_voice + lane, (int)k, fv.ref_kgroups)];
-    }
-    const uint32_t my_flags = ref.flags_gset & 0xffu;
-    if (my_flags & VB_SIMPLE) {
-        const uint32_t gi = LAZY ? 0u : (ref.flags_gset >> 8) & 0xffu;
-        my_g = g0;
-        if (gi != 0) my_g = fv.gsets[(size_t)(ld.first_voice + lane) * FW_GSETS + gi];
+        w.g0 = fv.gsets[(size_t)(ld.first_voice + lane) * FW_GSETS];
+        w.ref = fv.refs[ref_index(ld.first_voice + lane, (int)k, fv.ref_kgroups)];
     }
 #else
     // (the LAZY derivation is written for the LEAF_SPEC_GSET layout only: without it this branch would read refs / gsets an old
     //  control run left behind while the host skips the control kernel — ADVICE r4)
     static_assert(!LAZY, "k_leaf_sum_lazy needs LEAF_SPEC_GSET=1");
-    if (lane < ld.ports) ref = fv.refs[ref_index(ld.first_voice + lane, (int)k, fv.ref_kgroups)];
+    if (lane < ld.ports) w.ref = fv.refs[ref_index(ld.first_voice + lane, (int)k, fv.ref_kgroups)];
+#endif
+    if constexpr (PROG) {
+        if (lane < ld.ports) w.prog = fv.progs[ld.first_voice + lane];
+    }
+    return w;
+}
+template <bool PROG, bool LAZY>
+__device__ __forceinline__ LeafLane leaf_recs_finish(const FusedView& fv, const LeafDesc& ld, const uint32_t k, const int lane, const int frames, const LeafRaw& w) {
+    VoiceRef ref = w.ref;
+    GainSet my_g;
+#pragma unroll
+    for (int j = 0; j < FW_MAX_STAGES; ++j) my_g.g[j][0] = my_g.g[j][1] = 1.0f;
+#if LEAF_SPEC_GSET
+    if constexpr (LAZY) {
+        // the block's source address: what steady_tail's lean record would hold — (r0 + block * frames) mod L from the loop
+        // start (L a whole number of blocks: no block wraps inside itself), or straight on for a one-shot
+        const uint64_t bi = fv.lazy_blk0 + (uint64_t)k;
+        if (lane < ld.ports && (ref.flags_gset & VB_SIMPLE)) {  // (frames into the record's source, then bytes: the classes differ in bytes per frame)
+            const uint64_t fo = w.mode == 1 ? (uint64_t)((w.r0b + bi) % w.q) * (uint64_t)(uint32_t)frames : w.off0 + bi * (uint64_t)(uint32_t)frames;
+            ref.src_l = (const float*)(w.base + fo * w.bpf);
+        }
+    }
+    const uint32_t my_flags = ref.flags_gset & 0xffu;
+    if (my_flags & VB_SIMPLE) {
+        const uint32_t gi = LAZY ? 0u : (ref.flags_gset >> 8) & 0xffu;
+        my_g = w.g0;
+        if (gi != 0) my_g = fv.gsets[(size_t)(ld.first_voice + lane) * FW_GSETS + gi];
+    }
+#else
     const uint32_t my_flags = ref.flags_gset & 0xffu;
     if (my_flags & VB_SIMPLE) my_g = fv.gsets[(size_t)(ld.first_voice + lane) * FW_GSETS + ((ref.flags_gset >> 8) & 0xffu)];
 #endif
-    uint32_t my_prog = 0u;
+    uint32_t my_prog = w.prog;
     if constexpr (PROG) {
-        if (lane < ld.ports) my_prog = fv.progs[ld.first_voice + lane];
         asm volatile("" : "+v"(my_prog));  // (read with v_readlane inside the frame loop: see below)
     }
     const float* my_l = ref.src_l;
@@ -958,28 +990,224 @@ __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int lea
 #pragma unroll
         for (int j = 0; j < FW_MAX_STAGES; ++j) asm volatile("" : "+v"(my_g.g[j][0]), "+v"(my_g.g[j][1]));
     }
+    LeafLane L;
+    L.flags_gset = ref.flags_gset;
+    L.my_l = my_l;
+    L.my_r = my_r;
+    L.my_rd = my_rd;
+    L.my_cls = my_cls;
+    L.my_prog = my_prog;
+    L.my_g = my_g;
+    return L;
+}
+// which ports of the leaf take which path: wave-uniform, computed once per (leaf, block) under the full exec mask
+struct LeafMasks {
+    uint64_t silent_ports, simple_ports, rs_ports, lean_ports, batch_ports;
+    uint64_t my_off0, my_off1;  // (per lane) a resampler port's 32.32 position and step
+    uint32_t my_df;             // (per lane) ... and its VoiceBlk::flags
+    uint32_t cls0;
+    bool all_silent, masked, fast_cls;
+};
+template <bool PROG, bool RS>
+__device__ __forceinline__ LeafMasks leaf_classify(const FusedView& fv, const LeafDesc& ld, const size_t row, const int lane, const int frames, const RsLds rs,
+                                                   LeafLane& L) {
+    const float*& my_l = L.my_l;
+    uint32_t& my_rd = L.my_rd;
+    const uint32_t my_cls = L.my_cls;
+    GainSet& my_g = L.my_g;
+    const uint32_t my_flags = L.flags_gset & 0xffu;
+    const uint64_t lanes_in = mask_all_silent_bits(ld.ports);
+    const uint64_t silent_ports = __ballot((my_flags & VB_SILENT) != 0) & lanes_in;
+    const uint64_t simple_ports = __ballot((my_flags & VB_SIMPLE) != 0) & lanes_in;
+    const bool all_silent = silent_ports == lanes_in;
+    // resampler ports: lane p takes what the fetch of port p needs out of its full descriptor — sample data and length, 32.32
+    // position and step, flags, the constant gains — and says whether the staged path can render it (leaf_rs_piece)
+    uint64_t rs_ports = 0ull, my_off0 = 0ull, my_off1 = 0ull;
+    uint32_t my_df = 0u;
+    const uint64_t lean_ports = RS ? __ballot((my_flags & VB_RS_LEAN) != 0) & lanes_in : 0ull;
+    if constexpr (RS) {
+        bool el = false;
+        if (rs.tab != nullptr && lane < ld.ports && !(my_flags & (VB_SILENT | VB_SIMPLE))) {
+            const bool lean = (my_flags & VB_RS_LEAN) != 0;
+            const VoiceBlk* b = lean ? fv.rs_tmpl + (ld.first_voice + lane) : fv.blks + row + lane;
+            const uint32_t df = b->flags;
+            if (df & VB_RESAMPLE) {
+                const uint32_t len = b->pad;
+                const uint64_t off0 = lean ? (uint64_t)my_l : b->off0, step = b->off1;
+                const bool loop = b->n1 != 0;
+                const int nfr = frames < 256 ? frames : 256;
+                const uint64_t w_max = (((uint64_t)nfr * step + 0xffffffffull) >> 32) + 1 + RS_TAPS;  // any piece of the block
+                const uint64_t i_end = (off0 + (uint64_t)frames * step) >> 32;
+                // (a VB_RS_GLIDE block takes the frame-by-frame fetch: the window below is sized for ONE step)
+                el = !(df & VB_RS_GLIDE) && ((df >> VB_FMT_SHIFT) & 7u) == (uint32_t)FMT_P_F32 && w_max <= RS_WIN && (step >> 32) < 8 && i_end < (1ull << 30) && len < (1u << 30) &&
+                     len >= 1u && (!loop || len >= (uint32_t)RS_WIN + RS_TAPS);
+                if (el) {
+                    my_l = b->src_l;
+                    my_rd = len;
+                    my_off0 = off0;
+                    my_off1 = step;
+                    my_df = (df & ~RS_LOOP_BIT) | (loop ? RS_LOOP_BIT : 0u);
+#pragma unroll
+                    for (int j = 0; j < FW_MAX_STAGES; ++j) {
+                        my_g.g[j][0] = b->g[j][0];
+                        my_g.g[j][1] = b->g[j][1];
+                    }
+                }
+            }
+        }
+        rs_ports = __ballot(el) & lanes_in;
+        {  // (read with v_readlane inside the frame loop: pinned under the full exec mask, as above)
+            uint64_t pl = (uint64_t)my_l;
+            uint32_t o0l = (uint32_t)my_off0, o0h = (uint32_t)(my_off0 >> 32), o1l = (uint32_t)my_off1, o1h = (uint32_t)(my_off1 >> 32);
+            asm volatile("" : "+v"(pl), "+v"(my_rd), "+v"(o0l), "+v"(o0h), "+v"(o1l), "+v"(o1h), "+v"(my_df));
+            my_l = (const float*)pl;
+            my_off0 = ((uint64_t)o0h << 32) | o0l;
+            my_off1 = ((uint64_t)o1h << 32) | o1l;
+#pragma unroll
+            for (int j = 0; j < FW_MAX_STAGES; ++j) asm volatile("" : "+v"(my_g.g[j][0]), "+v"(my_g.g[j][1]));
+        }
+    }
+    const int path_ports = ld.pad ? ld.pad : ld.ports;  // (a leaf that is the leading voice ports of a wider SumNode takes ITS path)
+    LeafMasks M;
+    M.masked = !(path_ports == 2 || path_ports == 3 || path_ports == 4);  // sum.rs:67-133 (Q13)
+    const bool all_simple = simple_ports == lanes_in && (frames & 3) == 0;
+    M.cls0 = (uint32_t)__builtin_amdgcn_readlane((int)my_cls, 0);  // ports >= 1
+    const bool one_class = (__ballot(my_cls == M.cls0) & lanes_in) == lanes_in;
+    M.fast_cls = !PROG && all_simple && one_class && M.cls0 != SF_P_F32;  // (program voices on other formats: port by port)
+    // ports of a mixed leaf whose source loads are batched: VB_SIMPLE (so frames % 4 == 0, not silent) planar f32
+    M.batch_ports = (frames & 3) == 0 ? simple_ports & ~silent_ports & __ballot(my_cls == SF_P_F32) : 0ull;
+    M.silent_ports = silent_ports;
+    M.simple_ports = simple_ports;
+    M.rs_ports = rs_ports;
+    M.lean_ports = lean_ports;
+    M.my_off0 = my_off0;
+    M.my_off1 = my_off1;
+    M.my_df = my_df;
+    M.all_silent = all_silent;
+    return M;
+}
+// the leaf's ports added in port order for the quad of frames at f0 (all_silent: +0.0)
+template <bool PROG, bool RS, int U>
+__device__ __forceinline__ void leaf_piece(const FusedView& fv, const LeafDesc& ld, const uint32_t k, const size_t row, const int f0, const int frames,
+                                           const RsLds rs, const LeafLane& L, const LeafMasks& M, v4f& accl, v4f& accr) {
+    const float* const my_l = L.my_l;
+    const float* const my_r = L.my_r;
+    const uint32_t my_rd = L.my_rd, my_cls = L.my_cls, my_prog = L.my_prog;
+    const GainSet& my_g = L.my_g;
+    const uint64_t silent_ports = M.silent_ports, simple_ports = M.simple_ports, lean_ports = M.lean_ports;
+    const bool masked = M.masked;
+    accl = splat(0.f);
+    accr = splat(0.f);
+    bool rs_done = false;
+    if constexpr (RS) {
+        if (M.rs_ports) {
+            leaf_rs_piece<PROG, RS>(fv, ld, k, row, f0, frames, rs, my_l, my_rd, my_cls, my_g, my_prog, M.my_off0, M.my_off1, M.my_df, silent_ports,
+                                    simple_ports, M.rs_ports, lean_ports, masked, accl, accr);
+            rs_done = true;
+        }
+    }
+    if (rs_done) {
+    } else if (M.fast_cls) {
+        const int ng = fv.n_gain_stages;
+        switch (M.cls0) {
+            case SF_P_I16: leaf_fast_cls<SF_P_I16>(my_l, my_rd, my_g, ng, ld.ports, f0, accl, accr); break;
+            case SF_P_U16: leaf_fast_cls<SF_P_U16>(my_l, my_rd, my_g, ng, ld.ports, f0, accl, accr); break;
+            case SF_I_I16: leaf_fast_cls<SF_I_I16>(my_l, my_rd, my_g, ng, ld.ports, f0, accl, accr); break;
+            case SF_I_U16: leaf_fast_cls<SF_I_U16>(my_l, my_rd, my_g, ng, ld.ports, f0, accl, accr); break;
+            default: leaf_fast_cls<SF_I_F32>(my_l, my_rd, my_g, ng, ld.ports, f0, accl, accr); break;
+        }
+    } else if (!M.all_silent) {
+        // The ports are added in port order.  A RUN of plain ports (VB_SIMPLE planar f32 — on a steady bank the whole
+        // leaf is one run) has its source loads issued LEAF_U ports at a time; a port that ramps, wraps, is silent or of
+        // another source class is evaluated on its own, between two runs.  (A leaf with ONE gliding voice used to go
+        // port by port altogether: 64 dependent memory round trips in a row made such a wave ~60 us long, and the 1 500
+        // of them in a step of config 2's variant B — 68 gliding voices x 21 blocks — stretched the render kernel by 13 %.)
+        int p = 0;
+        while (p < ld.ports) {
+            const uint64_t rest = ~(M.batch_ports >> p);
+            int run = rest ? __builtin_ctzll(rest) : 64;
+            run = run < ld.ports - p ? run : ld.ports - p;
+            if (run > 0) {
+                if constexpr (PROG) {
+                    leaf_fast_prog<U>(my_l, my_r, my_g, my_prog, fv.n_gain_stages, p, p + run, f0, accl, accr);
+                } else {
+                    switch (fv.n_gain_stages) {
+                        case 1: leaf_fast<1, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                        case 2: leaf_fast<2, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                        case 3: leaf_fast<3, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                        case 4: leaf_fast<4, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                        case 5: leaf_fast<5, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                        default: leaf_fast<6, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                    }
+                }
+                p += run;
+                continue;
+            }
+            const bool psil = (silent_ports >> p) & 1ull;
+            v4f xl = splat(0.f), xr = splat(0.f);  // a silent chain's buffers hold cleared zeros
+            if (!psil) {
+                const uint32_t prog = PROG ? (uint32_t)__builtin_amdgcn_readlane((int)my_prog, p) : 0u;
+                if ((simple_ports >> p) & 1ull) {  // VB_SIMPLE implies frames % 4 == 0
+                    simple_fetch((uint32_t)__builtin_amdgcn_readlane((int)my_cls, p), readlane_ptr(my_l, p),
+                                 (uint32_t)__builtin_amdgcn_readlane((int)my_rd, p), f0, xl, xr);
+#pragma unroll
+                    for (int j = 0; j < FW_MAX_STAGES; ++j)
+                        if (j < fv.n_gain_stages)
+                            apply_stage(((prog << 4) >> (4 * j)) & 15u, splat(readlane_f(my_g.g[j][0], p)), splat(readlane_f(my_g.g[j][1], p)),
+                                        xl, xr);
+                } else {
+                    const VoiceBlk d = blk_load<RS>(fv, k, ld.first_voice + p, (lean_ports >> p) & 1ull ? VB_RS_LEAN : 0u, readlane_ptr(my_l, p));
+                    voice_eval<RS>(fv, d, k, ld.first_voice + p, f0, frames, xl, xr, prog, rs);
+                }
+            }
+            if (p == 0) {  // sum.rs:117 copy_from_slice(port 0) — also when silent; 2/3/4-port: in1
+                accl = xl;
+                accr = xr;
+            } else if (!(masked && psil)) {  // :122-124 skip silent ports (n-port path only)
+                accl = accl + xl;
+                accr = accr + xr;
+            }
+            ++p;
+        }
+    }
+}
+
+template <bool PROG, bool RS = false, int U = LEAF_U, bool SP = false, bool LAZY = false, bool SPM = false>
+__device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int leaf, const uint32_t k, const int part, const int wpk,
+                                              const RsLds rs = RsLds{nullptr, nullptr}, const int K = 1, float* sp_lds = nullptr, float* sp_tails = nullptr,
+                                              bool* sp_tails_valid = nullptr) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const LeafDesc ld = fv.leaves[leaf];
+    const int frames = fv.frames;
+    const size_t row = (size_t)k * fv.n_voices + ld.first_voice;
+    float* bus = fv.bus + (size_t)k * fv.bus_blk_stride;
+    uint8_t* bflags = fv.bus_flags + (size_t)k * fv.bus_flags_blk_stride;
+    float* outl = bus + (size_t)ld.out_buf * fv.stride;
+    float* outr = outl + fv.stride;
+
+    LeafLane L = leaf_recs_finish<PROG, LAZY>(fv, ld, k, lane, frames, leaf_recs_issue<PROG, LAZY>(fv, ld, k, lane));
     if constexpr (SP) {
         // a leaf with a spatialiser voice among its ports goes port by port (leaf_sp below); the other leaves of the plan take
         // the batched paths as before
         bool my_sp = false;
 #pragma unroll
-        for (int j = 0; j < FW_MAX_STAGES - 1; ++j) my_sp = my_sp || ((my_prog >> (4 * j)) & 15u) == SK_SPATIAL;
+        for (int j = 0; j < FW_MAX_STAGES - 1; ++j) my_sp = my_sp || ((L.my_prog >> (4 * j)) & 15u) == SK_SPATIAL;
         if (__ballot(my_sp && lane < ld.ports)) {
             // lane p also keeps port p's record of the block BEFORE (the history of the wave's first piece is re-rendered from it)
             VoiceRef refp;
             refp.src_l = nullptr;
             refp.r_delta = 0;
             refp.flags_gset = VB_SRC_ZERO;
-            GainSet gp = my_g;
+            GainSet gp = L.my_g;
             // (the wave rendered the block before this one itself, on the batched path, and kept its tails: no record of that block needed
             //  — IF this block takes the batched path too: a block with a wrap, a ramp or a silent port goes port by port below and
             //  re-renders its history from the record of the block before, tails or not)
             bool tv = sp_tails_valid != nullptr && *sp_tails_valid;
             if (sp_tails_valid != nullptr) *sp_tails_valid = false;
             if (tv) {
-                const uint32_t cls_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)my_cls);
-                const uint32_t prog_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)my_prog);
-                const bool now_a = (ref.flags_gset & (VB_SIMPLE | VB_SRC_ZERO | VB_SILENT)) == VB_SIMPLE && my_cls == cls_a && my_prog == prog_a && my_sp;
+                const uint32_t cls_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.my_cls);
+                const uint32_t prog_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.my_prog);
+                const bool now_a = (L.flags_gset & (VB_SIMPLE | VB_SRC_ZERO | VB_SILENT)) == VB_SIMPLE && L.my_cls == cls_a && L.my_prog == prog_a && my_sp;
                 const uint64_t lin_a = mask_all_silent_bits(ld.ports);
                 tv = (__ballot(now_a) & lin_a) == lin_a;
             }
@@ -987,7 +1215,7 @@ __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int lea
                 refp = fv.refs[ref_index(ld.first_voice + lane, (int)k - 1, fv.ref_kgroups)];
                 if (refp.flags_gset & VB_SIMPLE) gp = fv.gsets[(size_t)(ld.first_voice + lane) * FW_GSETS + ((refp.flags_gset >> 8) & 0xffu)];
             }
-            uint32_t fg = ref.flags_gset, fgp = refp.flags_gset, rdp = refp.r_delta;
+            uint32_t fg = L.flags_gset, fgp = refp.flags_gset, rdp = refp.r_delta;
             uint64_t plp = (uint64_t)refp.src_l;
             asm volatile("" : "+v"(fg), "+v"(fgp), "+v"(rdp), "+v"(plp));
 #pragma unroll
@@ -996,16 +1224,16 @@ __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int lea
                 // steady leaf: every port a spatialiser voice, VB_SIMPLE with a live source in this block (and in the block before, whose
                 // last 64 frames are the history), one source class, one stage program -> the batched path
                 const uint64_t lin = mask_all_silent_bits(ld.ports);
-                const uint32_t cls0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)my_cls);
-                const uint32_t prog0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)my_prog);
-                const bool ok_now = (fg & (VB_SIMPLE | VB_SRC_ZERO | VB_SILENT)) == VB_SIMPLE && my_cls == cls0 && my_prog == prog0 && my_sp;
+                const uint32_t cls0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.my_cls);
+                const uint32_t prog0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.my_prog);
+                const bool ok_now = (fg & (VB_SIMPLE | VB_SRC_ZERO | VB_SILENT)) == VB_SIMPLE && L.my_cls == cls0 && L.my_prog == prog0 && my_sp;
                 const bool ok_prev = k == 0 || tv || ((fgp & (VB_SIMPLE | VB_SRC_ZERO)) == VB_SIMPLE && ((fgp >> 16) & 7u) == cls0);
                 if ((__ballot(ok_now && ok_prev) & lin) == lin) {
                     int jn0 = 0;
 #pragma unroll
                     for (int j = 0; j < FW_MAX_STAGES - 1; ++j)
                         if (((prog0 >> (4 * j)) & 15u) == SK_SPATIAL) jn0 = j;
-#define SP_FAST(C) leaf_sp_fast<C>(fv, ld, k, K, part, wpk, prog0, jn0, my_l, my_rd, my_g, fg, plp, rdp, gp, sp_lds, outl, outr, sp_tails, tv)
+#define SP_FAST(C) leaf_sp_fast<C>(fv, ld, k, K, part, wpk, prog0, jn0, L.my_l, L.my_rd, L.my_g, fg, plp, rdp, gp, sp_lds, outl, outr, sp_tails, tv)
                     switch (cls0) {
                         case SF_P_F32: SP_FAST(SF_P_F32); break;
                         case SF_P_I16: SP_FAST(SF_P_I16); break;
@@ -1029,7 +1257,7 @@ __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int lea
                 bool any_live = false;
                 for (int p = 0; p < ld.ports; ++p) {
                     const uint32_t pfg = (uint32_t)__builtin_amdgcn_readlane((int)fg, p);
-                    const uint32_t prog = (uint32_t)__builtin_amdgcn_readlane((int)my_prog, p);
+                    const uint32_t prog = (uint32_t)__builtin_amdgcn_readlane((int)L.my_prog, p);
                     const int voice = ld.first_voice + p;
                     const bool psil = (pfg & VB_SILENT) != 0;
                     int jn = -1;  // chain-stage index of the spatialiser
@@ -1040,20 +1268,20 @@ __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int lea
                     if (jn < 0) {  // an ordinary voice under the same mixer
                         if (!psil && act) {
                             if (pfg & VB_SIMPLE) {
-                                simple_fetch((pfg >> 16) & 7u, readlane_ptr(my_l, p), (uint32_t)__builtin_amdgcn_readlane((int)my_rd, p), f0, xl, xr);
+                                simple_fetch((pfg >> 16) & 7u, readlane_ptr(L.my_l, p), (uint32_t)__builtin_amdgcn_readlane((int)L.my_rd, p), f0, xl, xr);
 #pragma unroll
                                 for (int j = 0; j < FW_MAX_STAGES; ++j)
                                     if (j < fv.n_gain_stages)
-                                        apply_stage(((prog << 4) >> (4 * j)) & 15u, splat(readlane_f(my_g.g[j][0], p)), splat(readlane_f(my_g.g[j][1], p)), xl, xr);
+                                        apply_stage(((prog << 4) >> (4 * j)) & 15u, splat(readlane_f(L.my_g.g[j][0], p)), splat(readlane_f(L.my_g.g[j][1], p)), xl, xr);
                             } else {
-                                const VoiceBlk d = blk_load<RS>(fv, k, voice, pfg, readlane_ptr(my_l, p));
+                                const VoiceBlk d = blk_load<RS>(fv, k, voice, pfg, readlane_ptr(L.my_l, p));
                                 voice_eval<RS>(fv, d, k, voice, f0, frames, xl, xr, prog, rs);
                             }
                         }
                     } else {
                         // what reaches the spatialiser: this piece ...
                         v4f a, b;
-                        sp_upstream<RS>(fv, pfg, readlane_ptr(my_l, p), (uint32_t)__builtin_amdgcn_readlane((int)my_rd, p), &my_g, p, k, voice, f0, frames,
+                        sp_upstream<RS>(fv, pfg, readlane_ptr(L.my_l, p), (uint32_t)__builtin_amdgcn_readlane((int)L.my_rd, p), &L.my_g, p, k, voice, f0, frames,
                                         prog, jn, act, a, b);
                         const v4f m = (a + b) * 0.5f;
                         // ... and the 64 frames in front of it (every group of 16 lanes renders the same 16 quads)
@@ -1061,7 +1289,7 @@ __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int lea
                         const int tq = (lane & 15) * 4;
                         if (fb > 0) {
                             v4f ta, tb;
-                            sp_upstream<RS>(fv, pfg, readlane_ptr(my_l, p), (uint32_t)__builtin_amdgcn_readlane((int)my_rd, p), &my_g, p, k, voice,
+                            sp_upstream<RS>(fv, pfg, readlane_ptr(L.my_l, p), (uint32_t)__builtin_amdgcn_readlane((int)L.my_rd, p), &L.my_g, p, k, voice,
                                             fb - SP_HIST + tq, frames, prog, jn, true, ta, tb);
                             tm = (ta + tb) * 0.5f;
                         } else if (k > 0) {
@@ -1094,8 +1322,8 @@ __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int lea
 #pragma unroll
                             for (int j = 1; j < FW_MAX_STAGES; ++j)
                                 if (j == jn + 1) {
-                                    gl = splat(readlane_f(my_g.g[j][0], p));
-                                    gr = splat(readlane_f(my_g.g[j][1], p));
+                                    gl = splat(readlane_f(L.my_g.g[j][0], p));
+                                    gr = splat(readlane_f(L.my_g.g[j][1], p));
                                 }
                         } else {
                             const VoiceBlk d = fv.blks[row + p];
@@ -1150,141 +1378,12 @@ __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int lea
             return;
         }
     }
-    const uint64_t lanes_in = mask_all_silent_bits(ld.ports);
-    const uint64_t silent_ports = __ballot((my_flags & VB_SILENT) != 0) & lanes_in;
-    const uint64_t simple_ports = __ballot((my_flags & VB_SIMPLE) != 0) & lanes_in;
-    const bool all_silent = silent_ports == lanes_in;
-    // resampler ports: lane p takes what the fetch of port p needs out of its full descriptor — sample data and length, 32.32
-    // position and step, flags, the constant gains — and says whether the staged path can render it (leaf_rs_piece)
-    uint64_t rs_ports = 0ull, my_off0 = 0ull, my_off1 = 0ull;
-    uint32_t my_df = 0u;
-    const uint64_t lean_ports = RS ? __ballot((my_flags & VB_RS_LEAN) != 0) & lanes_in : 0ull;
-    if constexpr (RS) {
-        bool el = false;
-        if (rs.tab != nullptr && lane < ld.ports && !(my_flags & (VB_SILENT | VB_SIMPLE))) {
-            const bool lean = (my_flags & VB_RS_LEAN) != 0;
-            const VoiceBlk* b = lean ? fv.rs_tmpl + (ld.first_voice + lane) : fv.blks + row + lane;
-            const uint32_t df = b->flags;
-            if (df & VB_RESAMPLE) {
-                const uint32_t len = b->pad;
-                const uint64_t off0 = lean ? (uint64_t)ref.src_l : b->off0, step = b->off1;
-                const bool loop = b->n1 != 0;
-                const int nfr = frames < 256 ? frames : 256;
-                const uint64_t w_max = (((uint64_t)nfr * step + 0xffffffffull) >> 32) + 1 + RS_TAPS;  // any piece of the block
-                const uint64_t i_end = (off0 + (uint64_t)frames * step) >> 32;
-                // (a VB_RS_GLIDE block takes the frame-by-frame fetch: the window below is sized for ONE step)
-                el = !(df & VB_RS_GLIDE) && ((df >> VB_FMT_SHIFT) & 7u) == (uint32_t)FMT_P_F32 && w_max <= RS_WIN && (step >> 32) < 8 && i_end < (1ull << 30) && len < (1u << 30) &&
-                     len >= 1u && (!loop || len >= (uint32_t)RS_WIN + RS_TAPS);
-                if (el) {
-                    my_l = b->src_l;
-                    my_rd = len;
-                    my_off0 = off0;
-                    my_off1 = step;
-                    my_df = (df & ~RS_LOOP_BIT) | (loop ? RS_LOOP_BIT : 0u);
-#pragma unroll
-                    for (int j = 0; j < FW_MAX_STAGES; ++j) {
-                        my_g.g[j][0] = b->g[j][0];
-                        my_g.g[j][1] = b->g[j][1];
-                    }
-                }
-            }
-        }
-        rs_ports = __ballot(el) & lanes_in;
-        {  // (read with v_readlane inside the frame loop: pinned under the full exec mask, as above)
-            uint64_t pl = (uint64_t)my_l;
-            uint32_t o0l = (uint32_t)my_off0, o0h = (uint32_t)(my_off0 >> 32), o1l = (uint32_t)my_off1, o1h = (uint32_t)(my_off1 >> 32);
-            asm volatile("" : "+v"(pl), "+v"(my_rd), "+v"(o0l), "+v"(o0h), "+v"(o1l), "+v"(o1h), "+v"(my_df));
-            my_l = (const float*)pl;
-            my_off0 = ((uint64_t)o0h << 32) | o0l;
-            my_off1 = ((uint64_t)o1h << 32) | o1l;
-#pragma unroll
-            for (int j = 0; j < FW_MAX_STAGES; ++j) asm volatile("" : "+v"(my_g.g[j][0]), "+v"(my_g.g[j][1]));
-        }
-    }
-    const int path_ports = ld.pad ? ld.pad : ld.ports;  // (a leaf that is the leading voice ports of a wider SumNode takes ITS path)
-    const bool masked = !(path_ports == 2 || path_ports == 3 || path_ports == 4);  // sum.rs:67-133 (Q13)
-    const bool all_simple = simple_ports == lanes_in && (frames & 3) == 0;
-    const uint32_t cls0 = (uint32_t)__builtin_amdgcn_readlane((int)my_cls, 0);  // ports >= 1
-    const bool one_class = (__ballot(my_cls == cls0) & lanes_in) == lanes_in;
-    const bool fast_cls = !PROG && all_simple && one_class && cls0 != SF_P_F32;  // (program voices on other formats: port by port)
-    // ports of a mixed leaf whose source loads are batched: VB_SIMPLE (so frames % 4 == 0, not silent) planar f32
-    const uint64_t batch_ports = (frames & 3) == 0 ? simple_ports & ~silent_ports & __ballot(my_cls == SF_P_F32) : 0ull;
+    const LeafMasks M = leaf_classify<PROG, RS>(fv, ld, row, lane, frames, rs, L);
 
     const int f_first = lane * 4 + part * 256;
     for (int f0 = f_first; f0 < frames; f0 += 256 * wpk) {
-        v4f accl = splat(0.f), accr = splat(0.f);
-        bool rs_done = false;
-        if constexpr (RS) {
-            if (rs_ports) {
-                leaf_rs_piece<PROG, RS>(fv, ld, k, row, f0, frames, rs, my_l, my_rd, my_cls, my_g, my_prog, my_off0, my_off1, my_df, silent_ports,
-                                        simple_ports, rs_ports, lean_ports, masked, accl, accr);
-                rs_done = true;
-            }
-        }
-        if (rs_done) {
-        } else if (fast_cls) {
-            const int ng = fv.n_gain_stages;
-            switch (cls0) {
-                case SF_P_I16: leaf_fast_cls<SF_P_I16>(my_l, my_rd, my_g, ng, ld.ports, f0, accl, accr); break;
-                case SF_P_U16: leaf_fast_cls<SF_P_U16>(my_l, my_rd, my_g, ng, ld.ports, f0, accl, accr); break;
-                case SF_I_I16: leaf_fast_cls<SF_I_I16>(my_l, my_rd, my_g, ng, ld.ports, f0, accl, accr); break;
-                case SF_I_U16: leaf_fast_cls<SF_I_U16>(my_l, my_rd, my_g, ng, ld.ports, f0, accl, accr); break;
-                default: leaf_fast_cls<SF_I_F32>(my_l, my_rd, my_g, ng, ld.ports, f0, accl, accr); break;
-            }
-        } else if (!all_silent) {
-            // The ports are added in port order.  A RUN of plain ports (VB_SIMPLE planar f32 — on a steady bank the whole
-            // leaf is one run) has its source loads issued LEAF_U ports at a time; a port that ramps, wraps, is silent or of
-            // another source class is evaluated on its own, between two runs.  (A leaf with ONE gliding voice used to go
-            // port by port altogether: 64 dependent memory round trips in a row made such a wave ~60 us long, and the 1 500
-            // of them in a step of config 2's variant B — 68 gliding voices x 21 blocks — stretched the render kernel by 13 %.)
-            int p = 0;
-            while (p < ld.ports) {
-                const uint64_t rest = ~(batch_ports >> p);
-                int run = rest ? __builtin_ctzll(rest) : 64;
-                run = run < ld.ports - p ? run : ld.ports - p;
-                if (run > 0) {
-                    if constexpr (PROG) {
-                        leaf_fast_prog<U>(my_l, my_r, my_g, my_prog, fv.n_gain_stages, p, p + run, f0, accl, accr);
-                    } else {
-                        switch (fv.n_gain_stages) {
-                            case 1: leaf_fast<1, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
-                            case 2: leaf_fast<2, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
-                            case 3: leaf_fast<3, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
-                            case 4: leaf_fast<4, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
-                            case 5: leaf_fast<5, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
-                            default: leaf_fast<6, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
-                        }
-                    }
-                    p += run;
-                    continue;
-                }
-                const bool psil = (silent_ports >> p) & 1ull;
-                v4f xl = splat(0.f), xr = splat(0.f);  // a silent chain's buffers hold cleared zeros
-                if (!psil) {
-                    const uint32_t prog = PROG ? (uint32_t)__builtin_amdgcn_readlane((int)my_prog, p) : 0u;
-                    if ((simple_ports >> p) & 1ull) {  // VB_SIMPLE implies frames % 4 == 0
-                        simple_fetch((uint32_t)__builtin_amdgcn_readlane((int)my_cls, p), readlane_ptr(my_l, p),
-                                     (uint32_t)__builtin_amdgcn_readlane((int)my_rd, p), f0, xl, xr);
-#pragma unroll
-                        for (int j = 0; j < FW_MAX_STAGES; ++j)
-                            if (j < fv.n_gain_stages)
-                                apply_stage(((prog << 4) >> (4 * j)) & 15u, splat(readlane_f(my_g.g[j][0], p)), splat(readlane_f(my_g.g[j][1], p)),
-                                            xl, xr);
-                    } else {
-                        const VoiceBlk d = blk_load<RS>(fv, k, ld.first_voice + p, (lean_ports >> p) & 1ull ? VB_RS_LEAN : 0u, readlane_ptr(my_l, p));
-                        voice_eval<RS>(fv, d, k, ld.first_voice + p, f0, frames, xl, xr, prog, rs);
-                    }
-                }
-                if (p == 0) {  // sum.rs:117 copy_from_slice(port 0) — also when silent; 2/3/4-port: in1
-                    accl = xl;
-                    accr = xr;
-                } else if (!(masked && psil)) {  // :122-124 skip silent ports (n-port path only)
-                    accl = accl + xl;
-                    accr = accr + xr;
-                }
-                ++p;
-            }
-        }
+        v4f accl, accr;
+        leaf_piece<PROG, RS, U>(fv, ld, k, row, f0, frames, rs, L, M, accl, accr);
 #if LEAF_NT_STORE == 2
         bus_store_pair(outl + f0, outr + f0, accl, accr);
 #elif LEAF_NT_STORE
@@ -1296,7 +1395,7 @@ __device__ __forceinline__ void leaf_sum_wave(const FusedView& fv, const int lea
 #endif
     }
     // out mask: all-silent -> both flagged; 1-port copy -> passthrough (sum.rs:58-65); else 0
-    if (lane < 2 && part == 0) bflags[ld.out_buf + lane] = all_silent ? 1 : 0;
+    if (lane < 2 && part == 0) bflags[ld.out_buf + lane] = M.all_silent ? 1 : 0;
 }
 
 // dynamic LDS of the program instantiations (launched with 0 bytes when the plan has no resampler voice): filter bank, then
@@ -1896,5 +1995,117 @@ __device__ __forceinline__ void root_out_any(const DevView& v, const RootArgs& r
 }
 __global__ __launch_bounds__(256) void k_root_out(DevView v, RootArgs ra, float* __restrict__ out) {
     root_out_any(v, ra, out, blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
+}
+
+// ---- a steady (lazy) call of a pure voice-bank plan whose tree is leaves -> root -> stereo graph_out, in ONE launch:
+// a workgroup of G waves owns one (block, 256-frame piece) and renders every leaf of the root for it.  Wave g takes a contiguous run of
+// the root's ports, walks it in port order and renders each leaf with the parts of leaf_sum_wave above (records, classify, piece); the
+// NEXT leaf's LeafDesc and record loads are issued before the current leaf streams, so the record -> source chain is one round trip
+// per run of leaves, not one per leaf.  The root is a left fold — ((L0 + L1) + L2) + ... — so only wave 0, which holds the prefix, adds
+// as it goes; waves 1 .. G-1 put each finished leaf sum in a 2 KiB row of LDS, and behind ONE workgroup barrier wave 0 adds those rows
+// in leaf order and stores the interleaved frames.  The fold is root_out_body's arithmetic, select for select.  The leaf-bus ROWS are
+// never written (nor read: k_root_out does not run for such a call); the two FLAGS per (leaf, block) are, for k_out_flags.
+// No workgroup waits for another one: a workgroup reads only what its own waves wrote, behind its own barrier.
+#ifndef LEAF_GROUP_G
+#define LEAF_GROUP_G 2  // waves per (block, piece): (2, 8) had the lowest median of the five geometries measured (profiles/README.md, leaf_group_sweep)
+#endif
+#ifndef LEAF_GROUP_U
+#define LEAF_GROUP_U 8  // ports whose source loads a wave keeps in flight together
+#endif
+__host__ __device__ inline int leaf_group_run(int n_leaves, int G) { return (n_leaves + G - 1) / G; }  // leaves per wave (wave 0 always has some)
+__host__ __device__ inline size_t leaf_group_lds_bytes(int n_leaves, int G) {  // rows of waves 1 .. G-1, then a word of silence bits per wave
+    return G == 1 ? 0 : ((size_t)(n_leaves - leaf_group_run(n_leaves, G)) * 512 + 64) * sizeof(float);
+}
+// one step of the root's fold: port p's stereo quad x, silent or not (sum.rs:111-133 as root_out_body has it: port 0 is copied even
+// when silent, later silent ports are skipped on the n-port path only)
+__device__ __forceinline__ void group_fold(v4f& accl, v4f& accr, const v4f xl, const v4f xr, const int p, const bool silent, const bool masked) {
+    const v4f sl = accl + xl, sr = accr + xr;
+    const bool use = !(masked && silent);
+    accl = p == 0 ? xl : (use ? sl : accl);
+    accr = p == 0 ? xr : (use ? sr : accr);
+}
+template <bool PROG, int G, int U>
+__global__ __launch_bounds__(WAVE* G) void k_leaf_group_lazy(FusedView fv, int K) {
+    extern __shared__ float s_grp[];
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = (int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t k = blockIdx.y;  // (the grid is exactly pieces x K)
+    const int frames = fv.frames;
+    const int n = fv.n_leaves;      // = the root's ports, in leaf order (the host checked)
+    const int per = leaf_group_run(n, G);
+    const int l_begin = wave * per, l_end = (wave + 1) * per < n ? (wave + 1) * per : n;
+    const int f0 = lane * 4 + (int)blockIdx.x * 256;
+    const bool act = f0 < frames;
+    const bool masked_root = !(n == 2 || n == 3 || n == 4);
+    uint32_t* s_sil = (uint32_t*)(s_grp + (size_t)(n - per) * 512);
+    uint8_t* bflags = fv.bus_flags + (size_t)k * fv.bus_flags_blk_stride;
+    v4f rl = splat(0.f), rr = splat(0.f);  // wave 0: the root's running sum
+    uint32_t sil_bits = 0u;                // bit i: leaf l_begin + i is all-silent in this block
+    if (l_begin < l_end) {
+        LeafDesc ld = fv.leaves[l_begin];
+        LeafDesc ld_next = fv.leaves[l_begin + 1 < n ? l_begin + 1 : n - 1];
+        LeafRaw raw = leaf_recs_issue<PROG, true>(fv, ld, k, lane);
+        for (int l = l_begin; l < l_end; ++l) {
+            LeafLane L = leaf_recs_finish<PROG, true>(fv, ld, k, lane, frames, raw);
+            const LeafDesc cur = ld;
+            if (l + 1 < l_end) {  // the next leaf's records travel while this one streams
+                ld = ld_next;
+                raw = leaf_recs_issue<PROG, true>(fv, ld, k, lane);
+                ld_next = fv.leaves[l + 2 < n ? l + 2 : n - 1];
+            }
+            const size_t row = (size_t)k * fv.n_voices + cur.first_voice;
+            const LeafMasks M = leaf_classify<PROG, false>(fv, cur, row, lane, frames, RsLds{nullptr, nullptr}, L);
+            v4f al = splat(0.f), ar = splat(0.f);
+            if (act) leaf_piece<PROG, false, U>(fv, cur, k, row, f0, frames, RsLds{nullptr, nullptr}, L, M, al, ar);
+            // out mask of the leaf, as leaf_sum_wave leaves it
+            if (lane < 2 && blockIdx.x == 0) bflags[cur.out_buf + lane] = M.all_silent ? 1 : 0;
+            sil_bits |= M.all_silent ? 1u << (l - l_begin) : 0u;
+            if (wave == 0) {
+                group_fold(rl, rr, al, ar, l, M.all_silent, masked_root);
+            } else if (act) {
+                float* r = s_grp + (size_t)(l - per) * 512 + lane * 4;
+                *(v4f*)r = al;
+                *(v4f*)(r + 256) = ar;
+            }
+        }
+    }
+    if constexpr (G > 1) {
+        if (lane == 0) s_sil[wave] = sil_bits;
+        __syncthreads();
+        if (wave != 0) return;
+    }
+    bool all_sil = sil_bits == (l_end - l_begin >= 32 ? ~0u : (1u << (l_end - l_begin)) - 1u);
+    if constexpr (G > 1) {
+        for (int g = 1; g < G; ++g) {
+            const int b = g * per, e = (g + 1) * per < n ? (g + 1) * per : n;
+            if (b >= e) break;
+            const uint32_t sb = s_sil[g];
+            all_sil = all_sil && sb == (1u << (e - b)) - 1u;  // (per < 32 when G > 1 and e > b for g >= 1)
+            for (int l = b; l < e; ++l) {
+                v4f xl = splat(0.f), xr = splat(0.f);
+                if (act) {
+                    const float* r = s_grp + (size_t)(l - per) * 512 + lane * 4;
+                    xl = *(const v4f*)r;
+                    xr = *(const v4f*)(r + 256);
+                }
+                group_fold(rl, rr, xl, xr, l, (sb >> (l - b)) & 1u, masked_root);
+            }
+        }
+    }
+    if (!act) return;
+    if (all_sil) rl = rr = splat(0.f);  // sum.rs:52-56 then util.rs:129-134 (one port: the copy of port 0 is what rl / rr hold)
+    float* o = fv.group_out + ((size_t)k * (size_t)frames + (size_t)f0) * 2;
+    typedef v4f_u __attribute__((address_space(1)))* gs4p;
+    if (f0 + 4 <= frames) {
+        *(gs4p)(uint64_t)o = (v4f){rl[0], rr[0], rl[1], rr[1]};
+        *(gs4p)(uint64_t)(o + 4) = (v4f){rl[2], rr[2], rl[3], rr[3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (f0 + j < frames) {
+                o[2 * j] = rl[j];
+                o[2 * j + 1] = rr[j];
+            }
+    }
 }
 // (the top-level R-port SumNode of a voice-sharded graph, k_bus_sum_ordered, lives in k_exchange.hip.h)

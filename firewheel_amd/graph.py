@@ -848,6 +848,12 @@ class FirewheelGpuCtx(object):
         self._check(self.L.fwgpu_lazy_stats(self.c, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def group_stats(self):
+        """launch batches rendered by the one-pass kernel (leaves + root in one launch) — include/fwgpu.h fwgpu_plan_group_stats"""
+        a = C.c_uint64(0)
+        self._check(self.L.fwgpu_plan_group_stats(self.c, C.byref(a)))
+        return a.value
+
     def plan_handover_stats(self):
         """(plans adopted so far, those adopted by a process call, the longest one of those held up its call in ns)"""
         a, b, m = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)

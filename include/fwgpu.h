@@ -194,6 +194,11 @@ int fwgpu_plan_pending(fwgpu_ctx* ctx);
  * record; the host skips the control kernel once it has SEEN (pinned memory) that the last one found every voice so.  A host that
  * never waits for the device between calls sees no difference but the time.  FWGPU_LAZY=0 switches it off.  Either may be NULL. */
 int fwgpu_lazy_stats(fwgpu_ctx* ctx, uint64_t* lazy_batches, uint64_t* control_batches);
+/* Voice-bank plans, diagnostics: launch batches since creation that ONE kernel rendered — leaves, root sum and interleave per
+ * (block, 256-frame piece), the leaf sums never leaving the chip.  Only a batch counted in *lazy_batches above can be one, and only of a
+ * plan whose mixer tree is leaves -> root -> stereo output, from a size up (FWGPU_LEAF_GROUP=0|1, read at creation, switches it;
+ * FWGPU_LEAF_GROUP_MIN sets the smallest blocks x pieces).  The output is the same bit for bit either way.  May be NULL. */
+int fwgpu_plan_group_stats(fwgpu_ctx* ctx, uint64_t* grouped_batches);
 /* The hipStream_t every process call of this ctx launches on (the caller's, or the one fwgpu_ctx_create made): for callers that
  * order their own device work or events against the engine's (bench.py's per-step time distribution).  NULL ctx -> NULL. */
 void* fwgpu_hip_stream(fwgpu_ctx* ctx);
