@@ -254,6 +254,88 @@ __device__ __forceinline__ void leaf_fast(const float* my_l, const float* my_r, 
     }
 }
 
+// ---- the grouped kernel's run of plain ports (k_leaf_group_lazy, LEAF_GROUP_PIPE below).  Every grouped workgroup is
+// resident at once, 1.5 waves per SIMD: what a wave does not keep in flight itself, nobody covers.  leaf_fast above guards every load
+// and every port with `p0 + u < ports`: each load sits in a basic block of its own, the compiler cannot count loads across the
+// branches and waits for ALL of a batch (vmcnt(0)) before the first port is used.  Here a batch of U whole ports is straight-line
+// code — the first port is used behind vmcnt(2U-2), the next behind vmcnt(2U-4), ... — and the guards are left to the last, partial
+// batch of a run.  The copy of port 0 (sum.rs:117) is decided once per run, not with eight selects per port.
+// Same operations per sample in the same order as leaf_fast.
+template <int NG>
+__device__ __forceinline__ void pipe_gains(const GainSet& my_g, const int p, v4f& a, v4f& b) {
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {  // sampler.rs:530-533, volume.rs:123-126, pan: one rounding each
+        a = a * readlane_f(my_g.g[j][0], p);
+        b = b * readlane_f(my_g.g[j][1], p);
+    }
+}
+template <int U>
+__device__ __forceinline__ void pipe_issue(const float* my_l, const float* my_r, const int p0, const int f0, v4f (&xl)[U], v4f (&xr)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        xl[u] = gload4(readlane_ptr(my_l, p0 + u) + f0);
+        xr[u] = gload4(readlane_ptr(my_r, p0 + u) + f0);
+    }
+}
+// ports p0 .. p0+U-1, whose quads are in flight in xl / xr, are added in order.  FIRST: the run's first batch (its first port is the
+// leaf's port 0 when copy0: copied).
+template <int NG, int U, bool FIRST>
+__device__ __forceinline__ void pipe_batch(const GainSet& my_g, const int p0, const bool copy0, const v4f (&xl)[U], const v4f (&xr)[U], v4f& accl,
+                                           v4f& accr) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        v4f a = xl[u], b = xr[u];
+        pipe_gains<NG>(my_g, p0 + u, a, b);
+        if (FIRST && u == 0) {
+            accl = copy0 ? a : accl + a;
+            accr = copy0 ? b : accr + b;
+        } else {
+            accl = accl + a;
+            accr = accr + b;
+        }
+    }
+}
+template <int NG, int U>
+__device__ __forceinline__ void leaf_fast_pipe(const float* my_l, const float* my_r, const GainSet& my_g, int p_begin, int ports, int f0,
+                                               v4f& accl, v4f& accr) {
+    int p0 = p_begin;
+    if (ports - p0 >= U) {
+        v4f xl[U], xr[U];
+        pipe_issue<U>(my_l, my_r, p0, f0, xl, xr);
+        pipe_batch<NG, U, true>(my_g, p0, p_begin == 0, xl, xr, accl, accr);
+        p0 += U;
+        while (ports - p0 >= U) {
+            pipe_issue<U>(my_l, my_r, p0, f0, xl, xr);
+            pipe_batch<NG, U, false>(my_g, p0, false, xl, xr, accl, accr);
+            p0 += U;
+        }
+    }
+    if (p0 < ports) {  // the last ports of the run, fewer than U: guarded
+        v4f xl[U], xr[U];
+#pragma unroll
+        for (int u = 0; u < U - 1; ++u) {
+            if (p0 + u < ports) {
+                xl[u] = gload4(readlane_ptr(my_l, p0 + u) + f0);
+                xr[u] = gload4(readlane_ptr(my_r, p0 + u) + f0);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U - 1; ++u) {
+            if (p0 + u < ports) {
+                v4f a = xl[u], b = xr[u];
+                pipe_gains<NG>(my_g, p0 + u, a, b);
+                if (u == 0 && p0 == 0) {  // (nothing was added before: p_begin == 0 too)
+                    accl = a;
+                    accr = b;
+                } else {
+                    accl = accl + a;
+                    accr = accr + b;
+                }
+            }
+        }
+    }
+}
+
 // the same with a stage program per voice (width / hard clip among the stages): lane p also holds port p's program; the
 // stage kind of (port, stage) is wave-uniform, so the dispatch is a scalar branch
 template <int U>
@@ -1087,7 +1169,8 @@ __device__ __forceinline__ LeafMasks leaf_classify(const FusedView& fv, const Le
     return M;
 }
 // the leaf's ports added in port order for the quad of frames at f0 (all_silent: +0.0)
-template <bool PROG, bool RS, int U>
+// PIPE: how a run of plain ports is streamed — 0: leaf_fast; 1: leaf_fast_pipe (the grouped kernel's gains-only instantiation alone)
+template <bool PROG, bool RS, int U, int PIPE = 0>
 __device__ __forceinline__ void leaf_piece(const FusedView& fv, const LeafDesc& ld, const uint32_t k, const size_t row, const int f0, const int frames,
                                            const RsLds rs, const LeafLane& L, const LeafMasks& M, v4f& accl, v4f& accr) {
     const float* const my_l = L.my_l;
@@ -1130,6 +1213,15 @@ __device__ __forceinline__ void leaf_piece(const FusedView& fv, const LeafDesc& 
             if (run > 0) {
                 if constexpr (PROG) {
                     leaf_fast_prog<U>(my_l, my_r, my_g, my_prog, fv.n_gain_stages, p, p + run, f0, accl, accr);
+                } else if constexpr (PIPE != 0) {
+                    switch (fv.n_gain_stages) {
+                        case 1: leaf_fast_pipe<1, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                        case 2: leaf_fast_pipe<2, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                        case 3: leaf_fast_pipe<3, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                        case 4: leaf_fast_pipe<4, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                        case 5: leaf_fast_pipe<5, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                        default: leaf_fast_pipe<6, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
+                    }
                 } else {
                     switch (fv.n_gain_stages) {
                         case 1: leaf_fast<1, U>(my_l, my_r, my_g, p, p + run, f0, accl, accr); break;
@@ -2012,6 +2104,10 @@ __global__ __launch_bounds__(256) void k_root_out(DevView v, RootArgs ra, float*
 #ifndef LEAF_GROUP_U
 #define LEAF_GROUP_U 8  // ports whose source loads a wave keeps in flight together
 #endif
+#ifndef LEAF_GROUP_PIPE
+#define LEAF_GROUP_PIPE 1  // how a wave streams a run of plain ports: 0 = leaf_fast (a batch waits for all of its loads), 1 = whole batches in
+                           // straight-line code, each port behind its own two loads (leaf_fast_pipe; profiles/leaf_pipe_sweep.jsonl)
+#endif
 __host__ __device__ inline int leaf_group_run(int n_leaves, int G) { return (n_leaves + G - 1) / G; }  // leaves per wave (wave 0 always has some)
 __host__ __device__ inline size_t leaf_group_lds_bytes(int n_leaves, int G) {  // rows of waves 1 .. G-1, then a word of silence bits per wave
     return G == 1 ? 0 : ((size_t)(n_leaves - leaf_group_run(n_leaves, G)) * 512 + 64) * sizeof(float);
@@ -2056,7 +2152,7 @@ __global__ __launch_bounds__(WAVE* G) void k_leaf_group_lazy(FusedView fv, int K
             const size_t row = (size_t)k * fv.n_voices + cur.first_voice;
             const LeafMasks M = leaf_classify<PROG, false>(fv, cur, row, lane, frames, RsLds{nullptr, nullptr}, L);
             v4f al = splat(0.f), ar = splat(0.f);
-            if (act) leaf_piece<PROG, false, U>(fv, cur, k, row, f0, frames, RsLds{nullptr, nullptr}, L, M, al, ar);
+            if (act) leaf_piece<PROG, false, U, PROG ? 0 : LEAF_GROUP_PIPE>(fv, cur, k, row, f0, frames, RsLds{nullptr, nullptr}, L, M, al, ar);
             // out mask of the leaf, as leaf_sum_wave leaves it
             if (lane < 2 && blockIdx.x == 0) bflags[cur.out_buf + lane] = M.all_silent ? 1 : 0;
             sil_bits |= M.all_silent ? 1u << (l - l_begin) : 0u;
