@@ -153,6 +153,7 @@ SIGNATURES = {
     "fwgpu_graph_output_latency": (ci, [vp, C.POINTER(u32)]),
     "fwgpu_crossfade_to": (ci, [vp, i64, f32, u32, ci, f32, f32, f32, f32, u32]),
     "fwgpu_resampler_glide": (ci, [vp, i64, f32, u32, u32]),
+    "fwgpu_gain_ride": (ci, [vp, i64, f32, u32, ci, f32, f32, f32, f32, u32]),
     "fwgpu_spatial_move": (ci, [vp, i64, f32, f32, f32, u32, u32]),
     "fwgpu_biquad_sweep": (ci, [vp, i64, f32, f32, u32, u32]),
     "fwgpu_node_process": (ci, [vp, i64, u64, C.POINTER(fp), u32, C.POINTER(fp), u32, u64, C.POINTER(u64), f64, u32]),

@@ -1178,6 +1178,24 @@ int fwgpu_spatial_move(fwgpu_ctx* c, int64_t node, float x, float y, float z, ui
     }
     return 0;
 }
+// SPEC gain ride: one CMD_GAIN_RIDE to the gain or gains param 0 would set for `value`; frames == 0 is a step with no
+// glide.  The curve is the crossfader's and is validated as fwgpu_crossfade_to validates it; at most 2^24 frames
+int fwgpu_gain_ride(fwgpu_ctx* c, int64_t node, float value, uint32_t frames, int shape, float x1, float y1, float x2, float y2, uint32_t at_block) {
+    static_assert(FWGPU_GAIN_RIDE_FRAMES_MAX == GAIN_RIDE_FRAMES_MAX, "the header's ride cap");
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    HostNode* n = c->graph.get(node);
+    if (!n) return fail(c, FWGPU_ERR_INVALID, "unknown node id");
+    if (n->kind != K_VOLUME && n->kind != K_PAN) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: the node is not a VolumeNode or a StereoPanNode");
+    if (!(value - value == 0.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: value is NaN or infinite");
+    if (frames > FWGPU_GAIN_RIDE_FRAMES_MAX) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: at most 2^24 frames");
+    if (shape != XF_SHAPE_LINEAR && shape != XF_SHAPE_BEZIER) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: shape must be 0 (linear) or 1 (Bezier)");
+    if (!(x1 >= 0.0f && x1 <= 1.0f && x2 >= 0.0f && x2 <= 1.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: x1 and x2 must be in 0..1");
+    if (!(y1 >= -1.0f && y1 <= 2.0f && y2 >= -1.0f && y2 <= 2.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: y1 and y2 must be in -1..2");
+    float g0, g1 = 0.0f;  // (a volume has one gain: its second target stays where make_state leaves p1)
+    if (n->kind == K_VOLUME) g0 = percent_volume_to_raw_gain(value);
+    else pan_to_gains(value, &g0, &g1);
+    return push_cmd(c, node, -1, make_gain_ride(at_block, g0, g1, frames, shape, x1, y1, x2, y2), false);
+}
 int fwgpu_node_set_params(fwgpu_ctx* c, uint32_t n, const int64_t* nodes, const int* params, const float* values, const uint32_t* at_blocks) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
     if (n && (!nodes || !params || !values || !at_blocks)) return fail(c, FWGPU_ERR_INVALID, "null message list");
@@ -1787,6 +1805,7 @@ int fwgpu_node_process(fwgpu_ctx* c, int64_t node, uint64_t frames, const float*
     v.pool = c->d_scratch_pool.as<float>();
     v.flags = c->d_scratch_flags.as<uint8_t>();
     c->epoch++;
+    v.gain_rides = hn->kind == K_VOLUME || hn->kind == K_PAN ? 1 : 0;  // (k_single_node<false, true>: CMD_GAIN_RIDE and a ride's blocks)
     v.sp_moves = hn->kind == K_SPATIAL ? 1 : 0;  // (k_single_node_spm: the build that takes CMD_SP_MOVE and renders a move)
     LCHK(c, launch_single_node(c->stream, v, 0));
     for (uint32_t i = 0; i < n_out; ++i)

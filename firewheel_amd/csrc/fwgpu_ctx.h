@@ -432,6 +432,12 @@ struct fwgpu_ctx : fwgpu::PlanImage {
     // sp_move_parked_n = the longest one that a plan install may have parked (never cleared: the node may return with any later
     // plan) — adopt_image extends the bound by it, so the call a parked node returns in runs the move builds until its move is over
     uint32_t sp_move_max_n = 0, sp_move_parked_n = 0;
+    // the same for gain rides of volume / pan nodes (CMD_GAIN_RIDE): gain_ride_live — the call being rendered may meet a ride: no lazy
+    // call, no captured graph, no resident realtime kernel, and the ride instantiations (k_level<0, false, true>, k_voice_control_ride);
+    // a call that cannot meet one launches exactly the kernels it launched before the ride existed.  _max_n / _parked_n as the move's
+    uint64_t gain_ride_until = 0;
+    bool gain_ride_live = false;
+    uint32_t gain_ride_max_n = 0, gain_ride_parked_n = 0;
     StatCounter lazy_calls, ctl_calls;           // fused batches rendered without / with a control kernel (fwgpu_lazy_stats)
     // Grouped calls: a lazy batch of a voice-bank plan whose tree is leaves -> root -> stereo out is rendered by ONE
     // kernel, k_leaf_group_lazy — leaf sums stay on chip, k_root_out does not run.  FWGPU_LEAF_GROUP=0|1 (read at creation) switches

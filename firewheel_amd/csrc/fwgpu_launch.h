@@ -45,6 +45,9 @@ struct DevView {
     int no_walkers = 0;
     // 1: this call may meet a spatialiser move (fwgpu_run.cpp note_sp_moves) — launch_level renders set 1 with k_level<1, true>
     int sp_moves = 0;
+    // 1: this call may meet a gain ride of a volume / pan node (fwgpu_run.cpp note_gain_rides) — launch_level renders set 0 with
+    // k_level<0, false, true>; fwgpu_node_process sets it for these two kinds (k_single_node<false, true>)
+    int gain_rides = 0;
 };
 
 // The compact records are tiled: 32 voices x 8 blocks per 4 KiB tile, [voice % 32][block % 8].  A voice's 8 consecutive blocks
@@ -94,6 +97,9 @@ struct FusedView {
                             // that follow one; a block inside a move is flagged in its VoiceBlk::pad and the leaf kernel reads its delays
                             // from the last two ramp rows
     int sp_hist_in_render;  // control-ahead mode + spatialiser stages: k_sp_hist_copy makes the history copy, not k_voice_control
+    int gain_rides = 0;     // this call may meet a gain ride (fwgpu_run.cpp note_gain_rides): launch_voice_control takes the ride builds; a
+                            // stage in a ride gets its per-frame gains in its ramp rows, which every render kernel reads as it reads a ramp
+                            // (in what was padding: every other field keeps its offset)
     const int* ctl_order;   // k_voice_control: wave w works voice ctl_order[w] (nullptr: w) — voices with messages first
     unsigned int* rs_wl;    // has_rs: work list k_leaf_rs leaves for k_leaf_sum_wl — [0] items, [1] workgroups done, then (leaf, block*4 + piece) pairs
     float* hist;            // [n_voices][SP_HIST]: the mono history each spatialiser voice enters THIS call with (copied from the ext

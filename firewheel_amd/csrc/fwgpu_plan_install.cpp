@@ -1230,6 +1230,10 @@ void adopt_image(fwgpu_ctx* c, PlanImage* n, bool on_audio_thread) {
     if (c->frames_done < c->sp_move_until && c->sp_move_max_n > c->sp_move_parked_n) c->sp_move_parked_n = c->sp_move_max_n;
     if (c->sp_move_parked_n && c->sp_move_until != ~0ull && c->frames_done + c->sp_move_parked_n > c->sp_move_until)
         c->sp_move_until = c->frames_done + c->sp_move_parked_n;
+    // gain rides (fwgpu_ctx.h gain_ride_parked_n): the same for a volume / pan node that leaves or returns in mid-ride
+    if (c->frames_done < c->gain_ride_until && c->gain_ride_max_n > c->gain_ride_parked_n) c->gain_ride_parked_n = c->gain_ride_max_n;
+    if (c->gain_ride_parked_n && c->gain_ride_until != ~0ull && c->frames_done + c->gain_ride_parked_n > c->gain_ride_until)
+        c->gain_ride_until = c->frames_done + c->gain_ride_parked_n;
     // 1. larger persistent arrays: old contents copied over on the stream, then the pointers change hands
     if (n->grow_states.p) {
         if (c->d_states.p && c->states_cap)

@@ -242,6 +242,7 @@ void retire_cmds_node(fwgpu_ctx* c, int slot) {
                 //  says nothing about it, so from here on every process call of this ctx counts as one that may meet a sweep)
                 if (m.type == CMD_BQ_SWEEP) c->bq_sweep_until = ~0ull;
                 if (m.type == CMD_SP_MOVE) c->sp_move_until = ~0ull;  // (the same for a spatialiser move)
+                if (m.type == CMD_GAIN_RIDE && gr_cmd_frames(m) != 0u) c->gain_ride_until = ~0ull;  // (and for a gain ride)
                 continue;
             }
             Cmd k = m;
@@ -329,6 +330,7 @@ static void fill_fused_view(fwgpu_ctx* c, FusedView& fv) {
     fv.has_rs = c->fused_rs ? 1 : 0;
     fv.has_sp = c->fused_sp ? 1 : 0;
     fv.sp_moves = c->sp_move_live ? 1 : 0;
+    fv.gain_rides = c->gain_ride_live ? 1 : 0;
     fv.rt_parent_leaf = fv.rt_parent_up = fv.rt_kids = nullptr;
     fv.rt_tree_sync = nullptr;
     fv.rt_root = -1;
@@ -440,6 +442,20 @@ static void note_sp_moves(fwgpu_ctx* c) {
     c->sp_move_live = c->frames_done < c->sp_move_until;
     if (!c->sp_move_live) c->sp_move_max_n = 0;
 }
+// gain rides of volume / pan nodes, the same way: a ride that a param 0 cuts short leaves the bound standing, which costs kernels, not
+// bits.  (A step, frames == 0, is a message too: the ride builds are the ones that apply it, for the call that holds it)
+static void note_gain_rides(fwgpu_ctx* c) {
+    bool step = false;
+    for (const Cmd& m : c->cmds)
+        if (m.type == CMD_GAIN_RIDE) {
+            const uint64_t end = c->frames_done + (uint64_t)m.block * c->mbf + (uint64_t)gr_cmd_frames(m);
+            if (end > c->gain_ride_until) c->gain_ride_until = end;
+            if (gr_cmd_frames(m) > c->gain_ride_max_n) c->gain_ride_max_n = gr_cmd_frames(m);
+            if (gr_cmd_frames(m) == 0u) step = true;
+        }
+    c->gain_ride_live = step || c->frames_done < c->gain_ride_until;
+    if (!c->gain_ride_live) c->gain_ride_max_n = 0;
+}
 // K blocks of `frames` frames through the level-batched executor (schedule.rs:289-344 as one launch per level for
 // all K blocks: each block has its own pool slice, a stateful node walks its K blocks in order inside one wave)
 int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const float* d_in, int n_in_ch, float* d_out,
@@ -451,6 +467,7 @@ int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const
     v.meter_K = (uint32_t)K;
     v.no_walkers = c->bq_sweep_live ? 1 : 0;
     v.sp_moves = c->sp_move_live ? 1 : 0;
+    v.gain_rides = c->gain_ride_live ? 1 : 0;
     // which gain-like stateful nodes cannot change during this batch (their blocks then run in parallel): decided once,
     // before the first level
     if (K > 1 && c->d_frozen.ensure_n("d_frozen", (size_t)c->plan.nodes.size()) == hipSuccess &&
@@ -627,7 +644,13 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
     FusedView fv;
     fill_fused_view(c, fv);
     // realtime edge: one block, tree = leaves + root, stereo stream -> the whole callback is ONE launch (k_rt_block)
-    if (K == 1 && c->rt_one_launch && !c->lazy_this_call && !c->fused_sp && !c->out_sil && !c->ahead_this_call && !c->fused_fx && !c->timing && c->n_tail == 0 && c->up_root_node >= 0 && n_out_ch == 2 &&
+    // (a call that may meet a gain ride takes the launch sequence below: k_rt_block and k_rt_persist keep the control code they had;
+    //  a resident kernel owns the voice state between two steady callbacks, so it ends first)
+    if (c->gain_ride_live && c->rtp.launched) {
+        const int rc = rt_persist_stop(c);
+        if (rc) return rc;
+    }
+    if (K == 1 && c->rt_one_launch && !c->gain_ride_live && !c->lazy_this_call && !c->fused_sp &&!c->out_sil && !c->ahead_this_call && !c->fused_fx && !c->timing && c->n_tail == 0 && c->up_root_node >= 0 && n_out_ch == 2 &&
         c->rt_tree_leaves > 0 && c->rt_tree_leaves == c->n_leaves && c->d_rt_sync.p) {
         DevView v;
         rt_root_view(c, fv, v);
@@ -804,6 +827,7 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
         v.meter_K = (uint32_t)K;
         v.no_walkers = c->bq_sweep_live ? 1 : 0;
         v.sp_moves = c->sp_move_live ? 1 : 0;
+        v.gain_rides = c->gain_ride_live ? 1 : 0;
         if (K > 1) {
             LCHK(c, launch_frozen_scan(c->stream, v, c->n_tail, cmd_block0, K, c->d_tail_frozen.as<uint8_t>(),
                                        c->d_tail_frozen.as<unsigned long long>()));
@@ -860,6 +884,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     drain_ring(c);
     note_bq_sweeps(c);
     note_sp_moves(c);
+    note_gain_rides(c);
     const bool hot = c->ctl_ahead_mode == 1 || !c->cmds.empty() || !c->hot_prev.empty();
     // (SPEC streaming sources: no ahead mode while a sampler holds a stream.  The control kernel of call N + 1 would move C beside or
     //  before the render of call N, whose publication — a copy of the live NodeStates behind that render — could then hand the writer a
@@ -875,7 +900,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     c->lazy_this_call = false;
     // (one-block callbacks belong to the realtime kernels, which run their own control)
     if (c->lazy_on && can_fuse && c->lazy_capable && !ahead && !(stable_out && frames == mbf) && !c->rt_use_graph && frames % mbf == 0 && c->cmds.empty() &&
-        c->hot_prev.empty() && !c->bq_sweep_live && !c->sp_move_live &&  // (a plan with a sweep or a move in flight runs its control kernel)
+        c->hot_prev.empty() && !c->bq_sweep_live && !c->sp_move_live && !c->gain_ride_live &&  // (a plan with a sweep, a move or a ride in flight runs its control kernel)
         c->lazy_valid && c->lazy_epoch == c->epoch && c->h_lazy_pub) {
         const unsigned long long seq = __atomic_load_n(&c->h_lazy_pub[1], __ATOMIC_ACQUIRE);
         const unsigned long long horizon = __atomic_load_n(&c->h_lazy_pub[0], __ATOMIC_RELAXED);
@@ -902,7 +927,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     // steady realtime call: no message on the device, one fused batch, the same output block as last time — every
     // kernel argument repeats (block counters and playheads live in device state), so the launch sequence is replayed
     // from a hipGraph instead of being re-issued kernel by kernel
-    if (stable_out && c->rt_use_graph && c->meters.empty() && can_fuse && !c->timing && c->n_cmds_dev == 0 && !c->bq_sweep_live && !c->sp_move_live && frames % mbf == 0 &&
+    if (stable_out && c->rt_use_graph && c->meters.empty() && can_fuse && !c->timing && c->n_cmds_dev == 0 && !c->bq_sweep_live && !c->sp_move_live && !c->gain_ride_live && frames % mbf == 0 &&
         frames / mbf <= (c->fused_fx ? std::min<uint32_t>(c->kmax, CH_FAST_KMAX) : c->kmax)) {
         const uint32_t K = (uint32_t)(frames / mbf);
         fwgpu_ctx::RtGraph& g = c->rt_graph;

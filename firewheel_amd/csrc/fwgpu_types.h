@@ -164,6 +164,12 @@ struct NodeState {
     //        has_loop hold the target delays: the move's end only clears N and k.  make_state leaves N = k = 0 (the device copy of
     //        phasor / phasor_inc / gain then holds the constructor's x / y / z, which no kernel reads; the host keeps its own in
     //        HostNode::init); a node's state keeps its slot over a plan install.  The arithmetic is sp_move_* below the struct
+    //   VOLUME, PAN: a gain ride (CMD_GAIN_RIDE) in fields neither kind has another use for, ONE layout for both:
+    //        full_range = N (0: at rest), enabled = k (frames of the ride rendered, k < N), phasor / phasor_inc = G0_0 / G0_1 (a volume:
+    //        G0_1 = 0), has_loop = shape (XF_SHAPE_*), playhead = x1 bits | y1 bits << 32, loop_start = x2 bits | y2 bits << 32.  In a
+    //        ride p0 / p1 and both smoothers rest at the targets G1_0 / G1_1 (a volume's p1 and s1 stay at 0, as make_state leaves
+    //        them): the ride's end only clears these seven fields, back to make_state's zeros.  No other message reaches them; a
+    //        node's state keeps its slot over a plan install.  The arithmetic is gain_ride_* below the struct
     //   METER: ext = ring[R][n_in] of MeterRec (4 floats each), loop_end = R (0: the creation parameter was refused)
     //   LIMITER, DUCKER, DELAY_COMP: loop_end = 0 marks a creation parameter that was refused; the valid states and the slice lengths
     //        are lim_/duck_/dcomp_state_ok and _ext_len below the struct
@@ -642,6 +648,155 @@ FW_TYPES_HD inline void sp_move_advance(NodeState& s, uint32_t frames) {
     }
 }
 
+// The automation curve y(u) of the crossfader (SPEC) and of a gain ride: ONE statement for xf_positions (k_common.hip.h)
+// and gain_ride_value.  Shape 0: y = u.  Shape 1: y = 0 at u == 0, else XF_ITERS bisection steps on B(t; x1, x2) < u, then B(t; y1, y2),
+// with B(t; a, d) = ((q*t + b)*t + c)*t, the cubic Bezier coordinate through 0, a, d, 1.  Every operation is a separately rounded f32
+// operation (-ffp-contract=off).  The solver runs on W frames at once, its loop rolled: the same trip count for every frame, nothing
+// indexed by a variable.  Always inlined: the crossfader's kernels keep the code they had when the solver stood inside xf_positions
+#if defined(__HIPCC__)
+#define FW_TYPES_UNROLL _Pragma("unroll")
+#define FW_TYPES_ROLLED _Pragma("unroll 1")
+#else
+#define FW_TYPES_UNROLL
+#define FW_TYPES_ROLLED
+#endif
+#define FW_TYPES_HD_INLINE FW_TYPES_HD inline __attribute__((always_inline))
+struct XfCubic {
+    float q, b, c;
+};
+FW_TYPES_HD_INLINE XfCubic xf_cubic(float a, float d) {
+    const float c = 3.0f * a;
+    const float b = (3.0f * (d - a)) - c;
+    return XfCubic{(1.0f - c) - b, b, c};
+}
+FW_TYPES_HD_INLINE float xf_bezier(const XfCubic& k, float t) { return (((k.q * t) + k.b) * t + k.c) * t; }
+template <int W>
+FW_TYPES_HD_INLINE void fw_curve_y(int shape, float x1, float y1, float x2, float y2, const float (&u)[W], float (&y)[W]) {
+    FW_TYPES_UNROLL
+    for (int e = 0; e < W; ++e) y[e] = u[e];
+    if (shape == XF_SHAPE_BEZIER) {
+        const XfCubic kx = xf_cubic(x1, x2), ky = xf_cubic(y1, y2);
+        float lo[W], hi[W];
+        FW_TYPES_UNROLL
+        for (int e = 0; e < W; ++e) lo[e] = 0.0f, hi[e] = 1.0f;
+        FW_TYPES_ROLLED
+        for (int i = 0; i < XF_ITERS; ++i) {
+            FW_TYPES_UNROLL
+            for (int e = 0; e < W; ++e) {
+                const float m = (lo[e] + hi[e]) * 0.5f;
+                const bool below = xf_bezier(kx, m) < u[e];
+                lo[e] = below ? m : lo[e];
+                hi[e] = below ? hi[e] : m;
+            }
+        }
+        FW_TYPES_UNROLL
+        for (int e = 0; e < W; ++e) y[e] = u[e] == 0.0f ? 0.0f : xf_bezier(ky, (lo[e] + hi[e]) * 0.5f);
+    }
+}
+
+// K_VOLUME / K_PAN gain ride (SPEC): ONE statement for the message (apply_cmds_from), the node kernels, the control
+// kernel and the host.  Per gain c (a volume: c = 0 alone; a pan: the left and the right ear) the gain goes G0_c -> G1_c over N frames
+// along the curve y: every operation a separately rounded f32 operation (-ffp-contract=off), the division IEEE, (float)(k + j) and
+// (float)N exact (both <= 2^24).  The layout is NodeState's comment block's (VOLUME, PAN); G1 = p0 / p1
+#define GAIN_RIDE_FRAMES_MAX 16777216u
+struct GainRide {
+    float G0[2], G1[2], d[2];  // d = G1 - G0, computed once
+    float x1, y1, x2, y2;
+    uint32_t N, k;
+    int shape;
+};
+FW_TYPES_HD_INLINE bool gain_ride_at_rest(const NodeState& s) { return s.full_range == 0; }
+// the ride as a block's render loop reads it: a snapshot taken BEFORE the block's advance (at rest: N == 0, every value is G1)
+FW_TYPES_HD_INLINE GainRide gain_ride_of(const NodeState& s) {
+    GainRide r;
+    r.N = (uint32_t)s.full_range;
+    r.k = (uint32_t)s.enabled;
+    r.shape = s.has_loop;
+    r.G0[0] = s.phasor, r.G0[1] = s.phasor_inc;
+    r.G1[0] = s.p0, r.G1[1] = s.p1;
+    r.d[0] = r.G1[0] - r.G0[0], r.d[1] = r.G1[1] - r.G0[1];
+    r.x1 = fw_float_of((uint32_t)s.playhead), r.y1 = fw_float_of((uint32_t)(s.playhead >> 32));
+    r.x2 = fw_float_of((uint32_t)s.loop_start), r.y2 = fw_float_of((uint32_t)(s.loop_start >> 32));
+    return r;
+}
+// ride_c(j) .. ride_c(j + W - 1), the gains of W consecutive frames from j frames ahead of the snapshot: behind the ride, and at rest,
+// G1; the clamp keeps an overshooting curve (and G0 + d rounding one ulp past G1) inside [min(G0, G1), max(G0, G1)]
+template <int W>
+FW_TYPES_HD_INLINE void gain_ride_values(const GainRide& r, int c, uint32_t j, float (&g)[W]) {
+    FW_TYPES_UNROLL
+    for (int e = 0; e < W; ++e) g[e] = r.G1[c];
+    const uint64_t t0 = (uint64_t)r.k + (uint64_t)j;
+    if (r.N == 0u || t0 >= (uint64_t)r.N) return;
+    const float fN = (float)r.N;
+    float u[W], y[W];
+    FW_TYPES_UNROLL
+    for (int e = 0; e < W; ++e) u[e] = (float)((uint32_t)t0 + (uint32_t)e) / fN;
+    fw_curve_y<W>(r.shape, r.x1, r.y1, r.x2, r.y2, u, y);
+    const float a = r.G0[c], b = r.G1[c];
+    const float lo = a < b ? a : b, hi = a < b ? b : a;
+    FW_TYPES_UNROLL
+    for (int e = 0; e < W; ++e)
+        if (t0 + (uint64_t)e < (uint64_t)r.N) {  // (the ride may end among the W frames)
+            const float v = a + (r.d[c] * y[e]);
+            g[e] = v < lo ? lo : (v > hi ? hi : v);
+        }
+}
+FW_TYPES_HD inline float gain_ride_value(const GainRide& r, int c, uint32_t j) {
+    float g[1];
+    gain_ride_values<1>(r, c, j, g);
+    return g[0];
+}
+// param 0 in a ride (CMD_SET_P0 / _P1): the ride ends — each smoother is reset to the ride's current gain and continues from there
+// towards whatever the message sets
+FW_TYPES_HD inline void gain_ride_clear(NodeState& s) {  // at rest: every field of the ride as make_state leaves it
+    s.full_range = 0;
+    s.enabled = 0;
+    s.has_loop = 0;
+    s.phasor = s.phasor_inc = 0.0f;
+    s.playhead = s.loop_start = 0ull;
+}
+FW_TYPES_HD inline void gain_ride_end(NodeState& s) {
+    if (s.full_range == 0) return;
+    const GainRide r = gain_ride_of(s);
+    s.s0.input = s.s0.last = gain_ride_value(r, 0, 0u);
+    s.s1.input = s.s1.last = gain_ride_value(r, 1, 0u);
+    s.s0.status = s.s1.status = SM_INACTIVE;
+    gain_ride_clear(s);
+}
+// the message, applied at a block's first frame: N frames from where the node stands to (G1_0, G1_1) along the curve.  N == 0 is the
+// SPEC's step: the gains are set hard, with no glide of the smoothers
+FW_TYPES_HD inline void gain_ride_start(NodeState& s, float G1_0, float G1_1, uint32_t N, int shape, float x1, float y1, float x2, float y2) {
+    const GainRide r = gain_ride_of(s);
+    const float G0_0 = r.N ? gain_ride_value(r, 0, 0u) : (s.s0.status == SM_ACTIVE ? s.s0.last : s.s0.input);
+    const float G0_1 = r.N ? gain_ride_value(r, 1, 0u) : (s.s1.status == SM_ACTIVE ? s.s1.last : s.s1.input);
+    // the smoothers are put at rest at the targets (coefficients untouched)
+    s.p0 = s.s0.input = s.s0.last = G1_0;
+    s.p1 = s.s1.input = s.s1.last = G1_1;
+    s.s0.status = s.s1.status = SM_INACTIVE;
+    gain_ride_clear(s);
+    // (N > GAIN_RIDE_FRAMES_MAX or a shape outside 0..1 is NOT SPEC behaviour: fwgpu_gain_ride refuses such a call, so only a
+    //  corrupted message gets here — a defensive branch, a step)
+    if (N == 0u || N > GAIN_RIDE_FRAMES_MAX || (shape != XF_SHAPE_LINEAR && shape != XF_SHAPE_BEZIER)) return;
+    s.phasor = G0_0;
+    s.phasor_inc = G0_1;
+    s.has_loop = shape;
+    s.playhead = (uint64_t)fw_bits_of(x1) | ((uint64_t)fw_bits_of(y1) << 32);
+    s.loop_start = (uint64_t)fw_bits_of(x2) | ((uint64_t)fw_bits_of(y2) << 32);
+    s.full_range = (int)N;
+}
+// behind a block of `frames` frames the node was processed in, silent input or not (the values are gain_ride_value of a snapshot
+// taken BEFORE this)
+FW_TYPES_HD inline void gain_ride_behind_block(NodeState& s, uint32_t frames) {
+    const uint32_t N = (uint32_t)s.full_range;
+    if (N == 0u) return;
+    const uint32_t k = (uint32_t)s.enabled + frames;  // (k < N <= 2^24 and a block has fewer than 2^31 frames)
+    if (k < N) {
+        s.enabled = (int)k;
+    } else {  // at rest: a node set to the target whose smoother has settled
+        gain_ride_clear(s);
+    }
+}
+
 // K_CROSSFADE (rendered by k_level<0>, no ext slice): the states its case renders.  T never runs behind t0: a message sets t0 = T
 FW_TYPES_HD inline bool xf_state_ok(const NodeState& s, int n_in, int n_out) {
     const auto unit = [](float x) { return x >= 0.0f && x <= 1.0f; };  // (false for a NaN)
@@ -688,6 +843,7 @@ enum : int {
     CMD_RS_GLIDE = 24,
     CMD_BQ_SWEEP = 25,
     CMD_SP_MOVE = 26,
+    CMD_GAIN_RIDE = 27,
 };
 struct Cmd {
     int state;
@@ -848,6 +1004,21 @@ FW_TYPES_HD constexpr Cmd make_xf_to(uint32_t block, float position, uint32_t fr
 #define xf_cmd_y1(c) (fwgpu::fw_hi_float_of((c).d0))
 #define xf_cmd_x2(c) (fwgpu::fw_lo_float_of((c).d1))
 #define xf_cmd_y2(c) (fwgpu::fw_hi_float_of((c).d1))
+// CMD_GAIN_RIDE (gain_ride_start), volume / pan: i0 = the frames in bits 0..24 and the shape (XF_SHAPE_*) in bit 28, f0 = G1_0, i1 =
+// G1_1 as float bits (a volume: 0.0f), the Bezier's control values as CMD_XF_TO carries them (the xf_cmd_* readers)
+FW_TYPES_HD constexpr Cmd make_gain_ride(uint32_t block, float g0, float g1, uint32_t frames, int shape, float x1, float y1, float x2, float y2) {
+    Cmd m = make_cmd(CMD_GAIN_RIDE, block);
+    m.i0 = (int)((frames & 0x1ffffffu) | ((uint32_t)(shape & 1) << 28));
+    m.f0 = g0;
+    m.i1 = (int)fw_bits_of(g1);
+    m.d0 = fw_double_of2(x1, y1);
+    m.d1 = fw_double_of2(x2, y2);
+    return m;
+}
+#define gr_cmd_frames(c) ((uint32_t)(c).i0 & 0x1ffffffu)
+#define gr_cmd_shape(c) (((c).i0 >> 28) & 1)
+#define gr_cmd_g0(c) ((c).f0)
+#define gr_cmd_g1(c) (fwgpu::fw_float_of((uint32_t)(c).i1))
 // Round trips, maker to reader, in every build: payload bits that read as a NaN or an infinity when viewed as a double or a float
 // (0x7ff0000000000001 is a signalling NaN, 0x7fa00001 too) and -0.0f come back as they went in.
 namespace wire_check {
@@ -898,6 +1069,14 @@ constexpr bool sp(uint32_t gl, uint32_t gr, int dl, int dr, uint32_t frames) {
            sp_cmd_dl(m) == dl && sp_cmd_dr(m) == dr && sp_cmd_frames(m) == frames;
 }
 static_assert(sp(NEG0, SNAN32, 0, 63, 1u) && sp(0x7ff00000u, 0x00000001u, 63, 0, 16777216u) && sp(0x3f800000u, NEG0, 32, 31, 0xffffffffu), "CMD_SP_MOVE");
+constexpr bool gr(uint32_t g0, uint32_t g1, uint32_t frames, int shape, uint32_t x1, uint32_t y1, uint32_t x2, uint32_t y2) {
+    const Cmd m = make_gain_ride(5u, fw_float_of(g0), fw_float_of(g1), frames, shape, fw_float_of(x1), fw_float_of(y1), fw_float_of(x2), fw_float_of(y2));
+    return m.type == CMD_GAIN_RIDE && m.block == 5u && m.state == 0 && fw_bits_of(gr_cmd_g0(m)) == g0 && fw_bits_of(gr_cmd_g1(m)) == g1 &&
+           gr_cmd_frames(m) == frames && gr_cmd_shape(m) == shape && fw_bits_of(xf_cmd_x1(m)) == x1 && fw_bits_of(xf_cmd_y1(m)) == y1 &&
+           fw_bits_of(xf_cmd_x2(m)) == x2 && fw_bits_of(xf_cmd_y2(m)) == y2;
+}
+static_assert(gr(NEG0, SNAN32, 0u, 1, 0x3f800000u, 0x7ff00000u, NEG0, SNAN32) && gr(0x7ff00000u, 0x00000001u, 16777216u, 0, SNAN32, NEG0, 0u, 1u) &&
+              gr(0x3f800000u, NEG0, 1u, 1, 0x3ed70a3du, 0u, 0x3f147ae1u, 0x3f800000u), "CMD_GAIN_RIDE");
 }  // namespace wire_check
 
 // ---------------------------------------------------------------- fused voice-bank plan

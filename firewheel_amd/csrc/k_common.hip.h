@@ -99,15 +99,7 @@ __device__ __forceinline__ uint64_t sat_round_u64(double x) {  // `(x).round() a
 // ONE statement of the curve for the message (CMD_XF_TO takes P0 from it: W = 1) and for the render case of node_process_wave (W = 4:
 // the four consecutive frames a lane renders).  Every operation is a separately rounded f32 operation (-ffp-contract=off), the
 // division and the square roots are IEEE.  B(t; a, d) = ((q*t + b)*t + c)*t, the cubic Bezier coordinate through 0, a, d, 1
-struct XfCubic {
-    float q, b, c;
-};
-__device__ __forceinline__ XfCubic xf_cubic(float a, float d) {
-    const float c = 3.0f * a;
-    const float b = (3.0f * (d - a)) - c;
-    return XfCubic{(1.0f - c) - b, b, c};
-}
-__device__ __forceinline__ float xf_bezier(const XfCubic& k, float t) { return (((k.q * t) + k.b) * t + k.c) * t; }
+// (XfCubic, xf_cubic, xf_bezier and the solver fw_curve_y: fwgpu_types.h — the gain ride reads the same curve)
 // the segment as the position rule reads it
 struct XfSeg {
     float P0, P1, x1, y1, x2, y2;
@@ -130,25 +122,8 @@ __device__ __forceinline__ void xf_positions(const XfSeg& g, uint64_t n, float (
     const float fdur = (float)dur;  // (exact: dur <= 2^24; so is every k < dur)
     float u[W], y[W];
 #pragma unroll
-    for (int e = 0; e < W; ++e) y[e] = u[e] = (float)((uint32_t)k0 + (uint32_t)e) / fdur;
-    if (g.shape == XF_SHAPE_BEZIER) {
-        const XfCubic kx = xf_cubic(g.x1, g.x2), ky = xf_cubic(g.y1, g.y2);
-        float lo[W], hi[W];
-#pragma unroll
-        for (int e = 0; e < W; ++e) lo[e] = 0.0f, hi[e] = 1.0f;
-#pragma unroll 1
-        for (int i = 0; i < XF_ITERS; ++i) {
-#pragma unroll
-            for (int e = 0; e < W; ++e) {
-                const float m = (lo[e] + hi[e]) * 0.5f;
-                const bool below = xf_bezier(kx, m) < u[e];
-                lo[e] = below ? m : lo[e];
-                hi[e] = below ? hi[e] : m;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < W; ++e) y[e] = u[e] == 0.0f ? 0.0f : xf_bezier(ky, (lo[e] + hi[e]) * 0.5f);
-    }
+    for (int e = 0; e < W; ++e) u[e] = (float)((uint32_t)k0 + (uint32_t)e) / fdur;
+    fw_curve_y<W>(g.shape, g.x1, g.y1, g.x2, g.y2, u, y);
     const float span = g.P1 - g.P0;
 #pragma unroll
     for (int e = 0; e < W; ++e)
@@ -186,9 +161,12 @@ __device__ inline int chain_cmd_lower_bound(const Cmd* cmds, int n_cmds, int sta
 // biquad node; the chain plan's control kernel and k_chain replay a biquad's messages themselves)
 // SP: the spatialiser's move (fwgpu_types.h sp_move_*) is compiled in (k_level<1>, k_single_node and the control wave's spatialiser
 // stage); sp_node: the node IS a spatialiser — it takes CMD_SP_MOVE, and a plain set_position ends a move in flight
-template <bool XF = false, bool SMP = false, bool BQ = false, bool SP = false>
+// GR: the gain ride of a volume / pan node (fwgpu_types.h gain_ride_*) is compiled in (k_level<0, false, true>, k_single_node<false, true> and the
+// ride builds of the control wave); gr_node: the node IS a volume or a pan — it takes CMD_GAIN_RIDE, and param 0 ends a ride in flight
+template <bool XF = false, bool SMP = false, bool BQ = false, bool SP = false, bool GR = false>
 __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t block, const Cmd* cmds, int n_cmds, const SampleDesc* samples,
-                                      int lo, float* ext = nullptr, bool ext_write = false, bool smp_env = false, bool sp_node = false) {
+                                      int lo, float* ext = nullptr, bool ext_write = false, bool smp_env = false, bool sp_node = false,
+                                      bool gr_node = false) {
     int i = lo;
     // BQ: the head of the ext slice as the messages of this block have left it so far — every lane follows it in registers (lane 0
     // alone stores it, and a later message of the same block must not read the slice back)
@@ -200,10 +178,12 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
         switch (c.type) {
             case CMD_SET_P0:
                 if (SP && sp_node) sp_move_stop(s);
+                if (GR && gr_node) gain_ride_end(s);
                 s.p0 = c.f0;
                 break;
             case CMD_SET_P1:
                 if (SP && sp_node) sp_move_stop(s);
+                if (GR && gr_node) gain_ride_end(s);
                 s.p1 = c.f0;
                 break;
             case CMD_SET_ENABLED: s.enabled = c.i0; break;
@@ -302,6 +282,11 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
                     if (sp_node) sp_move_start(s, sp_cmd_gl(c), sp_cmd_gr(c), sp_cmd_dl(c), sp_cmd_dr(c), sp_cmd_frames(c));
                 }
                 break;
+            case CMD_GAIN_RIDE:  // SPEC gain ride
+                if constexpr (GR) {
+                    if (gr_node) gain_ride_start(s, gr_cmd_g0(c), gr_cmd_g1(c), gr_cmd_frames(c), gr_cmd_shape(c), xf_cmd_x1(c), xf_cmd_y1(c), xf_cmd_x2(c), xf_cmd_y2(c));
+                }
+                break;
             case CMD_XF_TO: if constexpr (XF) {  // crossfader: a new segment from where the old one stands at this block's first frame (s.playhead = T)
                 float from[1];
                 xf_positions<1>(xf_seg(s), s.playhead, from);
@@ -339,11 +324,12 @@ __device__ inline int apply_cmds_from(NodeState& s, int state_idx, uint32_t bloc
     }
     return i;
 }
-template <bool XF = false, bool SMP = false, bool BQ = false, bool SP = false>
+template <bool XF = false, bool SMP = false, bool BQ = false, bool SP = false, bool GR = false>
 __device__ inline void apply_cmds(NodeState& s, int state_idx, uint32_t block, const Cmd* cmds, int n_cmds,
-                                  const SampleDesc* samples, float* ext = nullptr, bool ext_write = false, bool smp_env = false, bool sp_node = false) {
+                                  const SampleDesc* samples, float* ext = nullptr, bool ext_write = false, bool smp_env = false, bool sp_node = false,
+                                  bool gr_node = false) {
     if (n_cmds == 0) return;
-    apply_cmds_from<XF, SMP, BQ, SP>(s, state_idx, block, cmds, n_cmds, samples, chain_cmd_lower_bound(cmds, n_cmds, state_idx, block), ext, ext_write, smp_env, sp_node);
+    apply_cmds_from<XF, SMP, BQ, SP, GR>(s, state_idx, block, cmds, n_cmds, samples, chain_cmd_lower_bound(cmds, n_cmds, state_idx, block), ext, ext_write, smp_env, sp_node, gr_node);
 }
 
 // The same lower bound by a whole wave (all 64 lanes active, arguments wave-uniform): 64 pivots per round instead of one —

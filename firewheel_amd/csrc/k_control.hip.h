@@ -220,6 +220,50 @@ __device__ __attribute__((noinline)) void sp_move_rows(float* gl, float* gr, uin
     }
 }
 
+// SPEC gain ride (fwgpu_types.h gain_ride_*): a volume / pan stage inside a ride gets its per-frame gains in its two ramp
+// rows — the fade's trick: both rows from the one gain of a volume, one row per ear of a pan.  What the control wave keeps of a
+// stage's ride between blocks is RideRegs, the seven fields of NodeState's layout
+struct RideRegs {
+    int N, k, shape;
+    float G0[2];
+    uint64_t c1, c2;
+};
+// (per stage of a voice; empty in the builds without the ride, whose code reads as it read before the ride existed)
+template <bool ON>
+struct RideSet {
+    RideRegs r[FW_MAX_STAGES - 1];
+};
+template <>
+struct RideSet<false> {};
+__device__ __forceinline__ void ride_regs_get(RideRegs& q, const NodeState& s) {
+    q.N = s.full_range, q.k = s.enabled, q.shape = s.has_loop;
+    q.G0[0] = s.phasor, q.G0[1] = s.phasor_inc;
+    q.c1 = s.playhead, q.c2 = s.loop_start;
+}
+__device__ __forceinline__ void ride_regs_put(NodeState& s, const RideRegs& q) {
+    s.full_range = q.N, s.enabled = q.k, s.has_loop = q.shape;
+    s.phasor = q.G0[0], s.phasor_inc = q.G0[1];
+    s.playhead = q.c1, s.loop_start = q.c2;
+}
+__device__ __attribute__((noinline)) void gain_ride_rows(float* row0, float* row1, const int frames, const int lane, const GainRide rd, const int pan) {
+    for (int i = lane; i < frames; i += WAVE) {
+        const float g0 = gain_ride_value(rd, 0, (uint32_t)i);
+        row0[i] = g0;
+        row1[i] = pan ? gain_ride_value(rd, 1, (uint32_t)i) : g0;
+    }
+}
+// a stage's block inside a ride: the rows (unless what comes in is flagged silent), then the ride moves on behind the block
+__device__ __forceinline__ void gain_ride_stage(RideRegs& q, const float p0, const float p1, float* rb, const size_t stride, const int frames, const int lane,
+                                                const bool silent, const int pan) {
+    NodeState t;
+    ride_regs_put(t, q);
+    t.p0 = p0;
+    t.p1 = p1;
+    if (!silent) gain_ride_rows(rb, rb + stride, frames, lane, gain_ride_of(t), pan);
+    gain_ride_behind_block(t, (uint32_t)frames);
+    ride_regs_get(q, t);
+}
+
 // A smoother whose next set_and_process(target) returns the same constant and leaves its state untouched:
 // not Active, or Active but stalled at the f32 fixed point above settle_epsilon (Q28).
 __device__ __forceinline__ bool smoother_is_constant(const Smoother& s, float target) {
@@ -758,7 +802,9 @@ __global__ void k_lazy_publish(unsigned long long* d_horizon, unsigned long long
 // in this one skips the state machines altogether (VoiceCache): its whole call is a steady tail.
 // SPM: a spatialiser stage's move (CMD_SP_MOVE; fwgpu_types.h sp_move_*) is compiled in — the _spm kernels, which launch_voice_control
 // picks for a call that may meet a move (FusedView::sp_moves); every other call runs the kernel it ran before the move existed
-template <bool EARLY_VC = false, bool SPM = false>
+// RIDE: a volume / pan stage's gain ride (CMD_GAIN_RIDE; fwgpu_types.h gain_ride_*) is compiled in — the _ride kernels, which
+// launch_voice_control picks for a call that may meet a ride (FusedView::gain_rides); they have the move compiled in as well
+template <bool EARLY_VC = false, bool SPM = false, bool RIDE = false>
 __device__ inline void voice_control_wave(const FusedView& fv, const int vi, const int lane, const int K, const uint32_t cmd_block0) {
 #ifdef FW_CTL_TRACE
     unsigned long long tr[12];
@@ -1055,6 +1101,15 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
     if constexpr (SPM) {
         if (spv) spn = fv.states[sp_state];
     }
+    // a volume / pan stage's ride (CMD_GAIN_RIDE) lives behind the StageRegs prefix too: its seven fields per stage
+    RideSet<RIDE> rd;
+    if constexpr (RIDE) {
+#pragma unroll
+        for (int j = 0; j < FW_MAX_STAGES - 1; ++j) {
+            rd.r[j].N = 0;
+            if (j < vd.n_stages && (vd.stage_kind[j] == K_VOLUME || vd.stage_kind[j] == K_PAN)) ride_regs_get(rd.r[j], fv.states[vd.stage_state[j]]);
+        }
+    }
 
     // gain sets used so far in this call (the current one is mirrored in registers)
     int n_gsets = 0;
@@ -1141,7 +1196,24 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
                     tmp.p1 = st[j].p1;
                     tmp.playing = sp_dl;
                     tmp.has_loop = sp_dr;
-                    cur_st[j] = apply_cmds_from<false, false, false, SPM>(tmp, vd.stage_state[j], cb, fv.cmds, fv.n_cmds, fv.samples, cur_st[j], nullptr, false, false, SPM && spj);
+                    if constexpr (RIDE) {
+                        // a volume or a pan also takes its ride, CMD_GAIN_RIDE, which puts the smoothers at rest at the targets; param 0 in
+                        // a ride hands them the ride's current gains
+                        const bool grj = vd.stage_kind[j] == K_VOLUME || vd.stage_kind[j] == K_PAN;
+                        if (grj) {
+                            ride_regs_put(tmp, rd.r[j]);
+                            tmp.s0 = st[j].s0;
+                            tmp.s1 = st[j].s1;
+                        }
+                        cur_st[j] = apply_cmds_from<false, false, false, SPM, true>(tmp, vd.stage_state[j], cb, fv.cmds, fv.n_cmds, fv.samples, cur_st[j], nullptr, false, false, SPM && spj, grj);
+                        if (grj) {
+                            st[j].s0 = tmp.s0;
+                            st[j].s1 = tmp.s1;
+                            ride_regs_get(rd.r[j], tmp);
+                        }
+                    } else {
+                        cur_st[j] = apply_cmds_from<false, false, false, SPM>(tmp, vd.stage_state[j], cb, fv.cmds, fv.n_cmds, fv.samples, cur_st[j], nullptr, false, false, SPM && spj);
+                    }
                     st[j].p0 = tmp.p0;
                     st[j].p1 = tmp.p1;
                     if (spj) {
@@ -1258,6 +1330,19 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
             float* rb = ramp_base + (size_t)(j + 1) * 2 * fv.stride;
             const bool between = fx && j >= fb1 && j < (fb3 != 0x7fff ? fb3 : (fb2 != 0x7fff ? fb2 : fb1));  // a stage between two filters
             if (between && silent) d.g[j + 1][0] = d.g[j + 1][1] = -1.0f;  // (behind a muted stage of its segment: cleared in, cleared out)
+            if constexpr (RIDE) {
+                if (rd.r[j].N != 0) {
+                    // inside a ride (volume or pan): the smoothers rest at the targets and are not run, the mute test is not applied; a
+                    // silent input stays silent, and the ride moves on behind the block either way
+                    gain_ride_stage(rd.r[j], r.p0, r.p1, rb, (size_t)fv.stride, frames, lane, silent, vd.stage_kind[j] == K_PAN ? 1 : 0);
+                    if (!silent) {
+                        d.flags |= 3u << (VB_RAMP_SHIFT + 2 * (j + 1));
+                        d.g[j + 1][0] = r.p0;
+                        d.g[j + 1][1] = vd.stage_kind[j] == K_PAN ? r.p1 : r.p0;
+                    }
+                    continue;
+                }
+            }
             if (vd.stage_kind[j] == K_VOLUME) {  // nodes/volume.rs:84-145
                 if (silent) {
                     smoother_reset(r.s0, r.p0);
@@ -1407,6 +1492,12 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
             if (j >= vd.n_stages || !steady) break;
             mid_sil[j] = fx && j >= fb1 && j < (fb3 != 0x7fff ? fb3 : (fb2 != 0x7fff ? fb2 : fb1)) && sil;  // (cleared in: cleared out)
             const StageRegs& r = st[j];
+            if constexpr (RIDE) {
+                if (rd.r[j].N != 0) {  // a ride in flight: block by block, no steady cache, no lazy record, no ramp continuation
+                    steady = false;
+                    break;
+                }
+            }
             if (vd.stage_kind[j] == K_SPATIAL) {  // (its smoothers run whatever comes in; what goes out is never flagged silent)
                 sp_zero = sil || upstream_silent;
                 sil = false;
@@ -1562,6 +1653,11 @@ __device__ inline void voice_control_wave(const FusedView& fv, const int vi, con
 #pragma unroll
     for (int j = 0; j < FW_MAX_STAGES - 1; ++j)
         if (j < vd.n_stages) *(StageRegs*)&fv.states[vd.stage_state[j]] = st[j];
+    if constexpr (RIDE) {  // (the rides: fwgpu_types.h gain_ride_*)
+#pragma unroll
+        for (int j = 0; j < FW_MAX_STAGES - 1; ++j)
+            if (j < vd.n_stages && (vd.stage_kind[j] == K_VOLUME || vd.stage_kind[j] == K_PAN)) ride_regs_put(fv.states[vd.stage_state[j]], rd.r[j]);
+    }
     if (spv) {
         NodeState* sn = &fv.states[sp_state];
         sn->playing = sp_dl;
@@ -1647,14 +1743,14 @@ __device__ inline bool voice_control_lane_steady(const FusedView& fv, const int 
 // waves per SIMD, ~1 % of the dynamic instructions are scratch traffic — for control-ahead mode, where a control wave has to find its
 // registers on a SIMD that holds five render waves of the call before: two of them retiring make room for the small one, three
 // (without a refill in between) for the big one, which in practice only happens once the render grid has run dry.
-template <int OCC, bool SPM = false>
+template <int OCC, bool SPM = false, bool RIDE = false>
 __device__ __forceinline__ void voice_control_kernel(const FusedView& fv, const int K, const uint32_t cmd_block0) {
     const int w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (w >= fv.n_voices) return;
     // dispatch order: the voices with a message in this call (or the one before: their glides continue) go first — theirs are the
     // long waves (a glide is 22-25 us of serial latency)
     const int vi = fv.ctl_order ? __builtin_amdgcn_readfirstlane(fv.ctl_order[w]) : w;
-    voice_control_wave<true, SPM>(fv, vi, threadIdx.x & (WAVE - 1), K, cmd_block0);
+    voice_control_wave<true, SPM, RIDE>(fv, vi, threadIdx.x & (WAVE - 1), K, cmd_block0);
 }
 #ifndef CTL_SMALL_OCC
 #define CTL_SMALL_OCC 3
@@ -1663,3 +1759,8 @@ __global__ __launch_bounds__(256) void k_voice_control(FusedView fv, int K, uint
 __global__ __launch_bounds__(256, CTL_SMALL_OCC) void k_voice_control_small(FusedView fv, int K, uint32_t cmd_block0) { voice_control_kernel<3>(fv, K, cmd_block0); }
 __global__ __launch_bounds__(256) void k_voice_control_spm(FusedView fv, int K, uint32_t cmd_block0) { voice_control_kernel<1, true>(fv, K, cmd_block0); }
 __global__ __launch_bounds__(256, CTL_SMALL_OCC) void k_voice_control_small_spm(FusedView fv, int K, uint32_t cmd_block0) { voice_control_kernel<3, true>(fv, K, cmd_block0); }
+__global__ __launch_bounds__(256) void k_voice_control_ride(FusedView fv, int K, uint32_t cmd_block0) { voice_control_kernel<1, true, true>(fv, K, cmd_block0); }
+// (the small build's place in launch_voice_control's rule — a control wave beside the render of the call before — WITHOUT its register
+//  cap: five stages' rides on top of the state machines do not fit three waves per SIMD, the compiler says so when asked, and a capped
+//  build would spill the block loop.  It takes the registers it needs and runs at the big build's occupancy)
+__global__ __launch_bounds__(256) void k_voice_control_small_ride(FusedView fv, int K, uint32_t cmd_block0) { voice_control_kernel<3, true, true>(fv, K, cmd_block0); }

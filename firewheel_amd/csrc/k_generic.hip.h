@@ -296,7 +296,9 @@ __device__ __forceinline__ bool kind_is_stateful(int kind) {
 //  with a call in it hands its DevView over through scratch and is given the registers its launch bounds allow)
 // SPM: the spatialiser's move (CMD_SP_MOVE; fwgpu_types.h sp_move_*) is compiled in — k_level<1, true>, which launch_level picks for a
 // call that may meet a move (DevView::sp_moves), and k_single_node; every other call runs the kernel it ran before the move existed
-template <int SET, bool SPM = false>
+// GR: the gain ride of a volume / pan node (CMD_GAIN_RIDE; fwgpu_types.h gain_ride_*) is compiled in — k_level<0, false, true>, which
+// launch_level picks for a call that may meet a ride (DevView::gain_rides), and k_single_node's build for these two kinds
+template <int SET, bool SPM = false, bool GR = false>
 __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx, uint32_t blk, uint32_t cmd_block, bool store_state = true,
                                   uint32_t adv_blocks = 0, bool frozen_sampler = false) {
     const NodeDesc nd = v.nodes[node_idx];
@@ -327,7 +329,8 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
     const bool stateful = kind_is_stateful(nd.kind);
     if (stateful) {
         s = v.states[nd.state];
-        apply_cmds<SET == 0 || SET == 3, SET == 2 || SET == 3, SET == 1 || SET == 3, SPM>(s, nd.state, cmd_block, v.cmds, v.n_cmds, v.samples, v.ext, lane == 0, nd.kind == K_SAMPLER, nd.kind == K_SPATIAL);
+        apply_cmds<SET == 0 || SET == 3, SET == 2 || SET == 3, SET == 1 || SET == 3, SPM, GR>(s, nd.state, cmd_block, v.cmds, v.n_cmds, v.samples, v.ext, lane == 0, nd.kind == K_SAMPLER, nd.kind == K_SPATIAL,
+                                                                                                nd.kind == K_VOLUME || nd.kind == K_PAN);
         if (nd.kind == K_BIQUAD && v.n_cmds) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // lane 0's coefficient stores
     }
 
@@ -337,6 +340,32 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
 
         case K_VOLUME: if constexpr (SET == 0 || SET == 3) {  // nodes/volume.rs:84-145
             float raw = s.p0;
+            if constexpr (GR) if (!gain_ride_at_rest(s)) {
+                // a ride in flight (CMD_GAIN_RIDE; never frozen): the gain of every frame is gain_ride_values of the block's snapshot, the
+                // smoother rests at the target and is not run, the mute test is not applied; a silent input still clears and flags, and
+                // the ride moves on behind the block either way
+                const GainRide rd = gain_ride_of(s);
+                gain_ride_behind_block(s, (uint32_t)frames);
+                if (mask_all(in_mask, nd.n_in)) {
+                    out_mask = clear_all_outputs(io, 0, nd.n_out);
+                    break;
+                }
+                out_mask = in_mask;
+                const bool stereo = nd.n_in == 2 && nd.n_out == 2;
+                const int nch = nd.n_in < nd.n_out ? nd.n_in : nd.n_out;
+                for (int f0 = lane * 4; f0 < frames; f0 += 256) {
+                    float gv[4];
+                    gain_ride_values<4>(rd, 0, (uint32_t)f0, gv);
+                    const v4f g = (v4f){gv[0], gv[1], gv[2], gv[3]};
+                    for (int c = 0; c < nch; ++c) {
+                        v4f y;
+                        if (!stereo && mask_bit(in_mask, c)) y = splat(0.f);
+                        else y = *(const v4f*)(io.in(c) + f0) * g;
+                        *(v4f*)(io.out(c) + f0) = y;
+                    }
+                }
+                break;
+            }
             if (mask_all(in_mask, nd.n_in)) {  // :94-100
                 smoother_reset(s.s0, raw);
                 out_mask = clear_all_outputs(io, 0, nd.n_out);
@@ -368,6 +397,23 @@ __device__ __forceinline__ void node_process_wave(const DevView& v, int node_idx
 
         case K_PAN: if constexpr (SET == 0 || SET == 3) {  // SPEC node: volume.rs stereo path with one smoother per channel
             float tl = s.p0, tr = s.p1;
+            if constexpr (GR) if (!gain_ride_at_rest(s)) {  // a ride in flight: as the volume's, one gain per ear
+                const GainRide rd = gain_ride_of(s);
+                gain_ride_behind_block(s, (uint32_t)frames);
+                if (mask_all(in_mask, nd.n_in)) {
+                    out_mask = clear_all_outputs(io, 0, nd.n_out);
+                    break;
+                }
+                out_mask = in_mask;
+                for (int f0 = lane * 4; f0 < frames; f0 += 256) {
+                    float gl[4], gr[4];
+                    gain_ride_values<4>(rd, 0, (uint32_t)f0, gl);
+                    gain_ride_values<4>(rd, 1, (uint32_t)f0, gr);
+                    *(v4f*)(io.out(0) + f0) = *(const v4f*)(io.in(0) + f0) * (v4f){gl[0], gl[1], gl[2], gl[3]};
+                    *(v4f*)(io.out(1) + f0) = *(const v4f*)(io.in(1) + f0) * (v4f){gr[0], gr[1], gr[2], gr[3]};
+                }
+                break;
+            }
             if (mask_all(in_mask, nd.n_in)) {
                 smoother_reset(s.s0, tl);
                 smoother_reset(s.s1, tr);
@@ -1047,9 +1093,10 @@ __global__ void k_frozen_scan(DevView v, int n_nodes, uint32_t cmd_block0, uint3
                 case K_SPATIAL: spat = fz = v.frames >= SP_HIST && smoother_at_rest(s.s0, s.p0) && smoother_at_rest(s.s1, s.p1) && sp_move_at_rest(s); break;  // (a move in flight moves every block: the serial path)
                 // volume.rs:104: a gain below 1e-5 is a mute only while the smoother is Inactive — keep such a node
                 // on the serial path while it is Deactivating (the status matters there)
-                case K_VOLUME: fz = smoother_at_rest(s.s0, s.p0) && (s.s0.status == SM_INACTIVE || !(s.s0.input < 0.00001f)); break;
+                // (a gain ride in flight moves every block: the serial path — for the pan below too)
+                case K_VOLUME: fz = smoother_at_rest(s.s0, s.p0) && (s.s0.status == SM_INACTIVE || !(s.s0.input < 0.00001f)) && gain_ride_at_rest(s); break;
                 case K_WIDTH: fz = smoother_at_rest(s.s0, s.p0); break;
-                default: fz = smoother_at_rest(s.s0, s.p0) && smoother_at_rest(s.s1, s.p1); break;  // K_PAN
+                default: fz = smoother_at_rest(s.s0, s.p0) && smoother_at_rest(s.s1, s.p1) && gain_ride_at_rest(s); break;  // K_PAN
             }
         }
     }
@@ -1531,7 +1578,7 @@ __device__ __forceinline__ uint32_t frozen_fast(const DevView& v, const int node
 #ifndef LEVEL_MINW
 #define LEVEL_MINW 3
 #endif
-template <int SET, bool SPM = false>
+template <int SET, bool SPM = false, bool GR = false>
 __global__ __launch_bounds__(WAVE* WPB, LEVEL_MINW) void k_level(DevView v, const int* __restrict__ level_nodes, int n_nodes,
                                                       uint32_t cmd_block0, uint32_t K, uint32_t bpw, uint32_t walkers) {
     int w = blockIdx.x * WPB + (threadIdx.x >> 6);
@@ -1557,7 +1604,7 @@ __global__ __launch_bounds__(WAVE* WPB, LEVEL_MINW) void k_level(DevView v, cons
             uint32_t todo = bpw > 1 ? frozen_fast<SET>(v, node, fz, b0, b1, K, skip) : ~0u;  // (what is left goes block by block)
             todo &= ~skip;
             for (uint32_t b = b0; b < b1; ++b)
-                if ((todo >> ((b - b0) & 31u)) & 1u) node_process_wave<SET, SPM>(v, node, b, cmd_block0 + b, adv && b + 1 == K, adv ? b : 0u, adv || spat);
+                if ((todo >> ((b - b0) & 31u)) & 1u) node_process_wave<SET, SPM, GR>(v, node, b, cmd_block0 + b, adv && b + 1 == K, adv ? b : 0u, adv || spat);
             if (spat) {
                 if (b0 == 0) spatial_finish(v, node, K);
             } else if (!adv && b0 == 0) {
@@ -1569,9 +1616,9 @@ __global__ __launch_bounds__(WAVE* WPB, LEVEL_MINW) void k_level(DevView v, cons
         if constexpr (SET == 1) {  // (a bus filter / delay the batch walkers take: k_bus_iir, launched next to this kernel)
             if (walkers && (biquad_walk_ok(v, v.nodes[node], cmd_block0, K) || delay_walk_ok(v, v.nodes[node], cmd_block0, K))) return;
         }
-        for (uint32_t b = 0; b < K; ++b) node_process_wave<SET, SPM>(v, node, b, cmd_block0 + b);
+        for (uint32_t b = 0; b < K; ++b) node_process_wave<SET, SPM, GR>(v, node, b, cmd_block0 + b);
     } else {
-        for (uint32_t b = b0; b < b1; ++b) node_process_wave<SET, SPM>(v, node, b, cmd_block0 + b);
+        for (uint32_t b = b0; b < b1; ++b) node_process_wave<SET, SPM, GR>(v, node, b, cmd_block0 + b);
     }
 }
 

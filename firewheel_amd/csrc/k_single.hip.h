@@ -4,7 +4,8 @@
 // node never needs both kinds' LDS, and the delay needs none
 // SPM: the build for a spatialiser (launch_single_node: DevView::sp_moves) — it takes CMD_SP_MOVE and renders a move; every other kind
 // runs the build without it
-template <bool SPM>
+// GR: the build for a volume or a pan (DevView::gain_rides) — it takes CMD_GAIN_RIDE and renders a ride
+template <bool SPM, bool GR = false>
 __global__ __launch_bounds__(WAVE) void k_single_node(DevView v, int node_idx) {
     __shared__ union {
         LimLds lim;
@@ -32,5 +33,5 @@ __global__ __launch_bounds__(WAVE) void k_single_node(DevView v, int node_idx) {
         dcomp_history(v, p, 1);
         return;
     }
-    node_process_wave<3, SPM>(v, node_idx, 0, 0);
+    node_process_wave<3, SPM, GR>(v, node_idx, 0, 0);
 }

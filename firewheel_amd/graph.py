@@ -88,6 +88,12 @@ class BeepTestNode(_Node):  # nodes/beep_test.rs:14-33
         self._set(0, 1.0 if enabled else 0.0, at_block)
 
 
+def _gain_ride(node, value, frames, curve, at_block):
+    """fwgpu_gain_ride for a VolumeNode / StereoPanNode: `curve` as CrossfadeNode.crossfade_to takes it"""
+    shape, (x1, y1, x2, y2) = (0, (0.0, 0.0, 1.0, 1.0)) if curve is None else (1, curve)
+    node.cx._check(node.cx.L.fwgpu_gain_ride(node.cx.c, node.id, value, frames, shape, x1, y1, x2, y2, at_block))
+
+
 class VolumeNode(_Node):  # nodes/volume.rs:14-39
     KIND = 2
 
@@ -100,6 +106,21 @@ class VolumeNode(_Node):  # nodes/volume.rs:14-39
     def set_percent_volume(self, percent_volume, at_block=0):
         self.percent_volume = max(percent_volume, 0.0)
         self._set(0, percent_volume, at_block)
+
+    RIDE_FRAMES_MAX = 1 << 24
+
+    def ride_to(self, percent_volume, frames, curve=None, at_block=0):
+        """from block `at_block` of the next process call on, ride the gain from where it stands to what `percent_volume` sets, over
+        `frames` frames (0: a hard set with no 10 ms glide) along `curve` — None: linear; (x1, y1, x2, y2): the cubic Bezier
+        CrossfadeNode.crossfade_to takes.  ONE message instead of a set_percent_volume per block (fwgpu_gain_ride): the music bus down
+        to 30 % over two seconds with an ease is `music.ride_to_secs(30.0, 2.0, (0.42, 0.0, 0.58, 1.0))`.  A second ride starts where
+        the first stands; set_percent_volume during a ride ends it and glides on from its current value"""
+        _gain_ride(self, percent_volume, frames, curve, at_block)
+        self.percent_volume = max(percent_volume, 0.0)
+
+    def ride_to_secs(self, percent_volume, secs, curve=None, at_block=0):
+        """ride_to with the length in seconds of the context's sample rate"""
+        self.ride_to(percent_volume, max(0, int(round(secs * self.cx.sample_rate))), curve, at_block)
 
 
 class SumNode(_Node):  # nodes/sum.rs
@@ -256,6 +277,19 @@ class StereoPanNode(_Node):  # SPEC node: constant-power pan, pan in
     def set_pan(self, pan, at_block=0):
         self.pan = pan
         self._set(0, pan, at_block)
+
+    RIDE_FRAMES_MAX = 1 << 24
+
+    def ride_to(self, pan, frames, curve=None, at_block=0):
+        """from block `at_block` of the next process call on, ride both ear gains from where they stand to what `pan` sets, over
+        `frames` frames (0: a hard set) along `curve` (as VolumeNode.ride_to).  The ride travels in the gains, each ear on its own: a
+        ride from hard left to hard right dips in power at the middle — one that must hold power is two rides through the centre"""
+        _gain_ride(self, pan, frames, curve, at_block)
+        self.pan = pan
+
+    def ride_to_secs(self, pan, secs, curve=None, at_block=0):
+        """ride_to with the length in seconds of the context's sample rate"""
+        self.ride_to(pan, max(0, int(round(secs * self.cx.sample_rate))), curve, at_block)
 
 
 class StereoWidthNode(_Node):  # SPEC node: mid/side width, w >= 0 (1 = unchanged, 0 = mono), smoothed

@@ -681,6 +681,33 @@ int fwgpu_crossfade_to(fwgpu_ctx* ctx, int64_t node, float position, uint32_t fr
 #define FWGPU_RESAMPLER_GLIDE_FRAMES_MAX 16777216
 int fwgpu_resampler_glide(fwgpu_ctx* ctx, int64_t node, float ratio, uint32_t frames, uint32_t at_block);
 
+/* ---- volume and pan: a gain ride, param 0 moved along a curve in one message (SPEC).
+ * fwgpu_gain_ride: `node` is a FWGPU_VOLUME or a FWGPU_STEREO_PAN node and `value` what its param 0 takes (percent_volume, or pan in
+ * -1..1).  From the first frame of block `at_block` of the next process call the node's gain — a volume's one gain, a pan's left and
+ * right gain, each on its own — travels from where it stands to the f32 gain(s) param 0 would set for `value` (G1_c), over `frames`
+ * frames, along the crossfader's curve (`shape`, x1 .. y2: as fwgpu_crossfade_to takes and validates them).  Per gain c, with G0_c the
+ * gain in force at that block's first frame (a ride in flight: its value there; else what the smoother last gave), N = frames and k the
+ * frames of the ride rendered so far, the gain of the frame j frames ahead is
+ *   ride_c(j) = N == 0 || k + j >= N ? G1_c
+ *             : clamp(G0_c + (d_c * y((float)(k + j) / (float)N)), min(G0_c, G1_c), max(G0_c, G1_c)),   d_c = G1_c - G0_c, computed once
+ * y(u) = u for shape 0; for shape 1 the crossfader's curve bit for bit (above: y = 0 at u == 0, else 24 bisection steps on
+ * B(t; x1, x2) < u, then B(t; y1, y2)).  Every operation is a separately rounded f32 operation, the division IEEE, no FMA.  The clamp
+ * replaces the crossfader's clamp to 0..1: an overshooting curve flattens at the ends, the gain never leaves the interval and never
+ * goes negative.  The ride happens in the GAINS, per ear for a pan, as a spatialiser move travels: a ride from hard left to hard right
+ * therefore dips in power at the middle (each ear passes 0.5 where equal power wants 0.707) — a ride that must hold power is two
+ * segments through the centre.  The message puts the smoother(s) at rest at the target(s); in a ride the smoother is not run and the
+ * volume's mute test (gain < 1e-5) is not applied; an input flagged silent still gives cleared, flagged outputs.  Behind every block
+ * the node is processed in, silent input or not, k += the block's frames; once k >= N the node is at rest, bit for bit a node set to
+ * the target whose smoother has settled (a volume that rode to 0 mutes from the next block on).  frames == 0 is a step: the hard set
+ * with no 10 ms glide.  A second ride starts where the first stands.  Param 0 during a ride ends it: the smoother(s) are reset to the
+ * ride's current value(s), then the parameter is set, so the one-pole glides on from there.  Several messages for one block apply in
+ * send order.  A voice with a stage in a ride is not steady: its calls run the control kernel, and lazy calls resume with the first
+ * call behind the ride; one-block calls take the launch sequence while a ride may be in flight.  FWGPU_ERR_INVALID for a node of
+ * another kind, a NaN or infinite value, frames > FWGPU_GAIN_RIDE_FRAMES_MAX, or a shape or control value fwgpu_crossfade_to refuses. */
+#define FWGPU_GAIN_RIDE_FRAMES_MAX 16777216
+int fwgpu_gain_ride(fwgpu_ctx* ctx, int64_t node, float value, uint32_t frames, int shape, float x1, float y1, float x2, float y2,
+                    uint32_t at_block);
+
 /* ---- spatialiser: a move of the source in one message (SPEC).
  * fwgpu_spatial_move: from the first frame of block `at_block` of the next process call, move the node from where it stands to what
  * params 0..2 would set for (x, y, z) — the ear gains G1l, G1r and the whole per-ear delays d1l, d1r (0..63 frames) — over `frames`

@@ -30,6 +30,8 @@ pub const FWGPU_CROSSFADE_FRAMES_MAX: u32 = 16777216;
 pub const FWGPU_CROSSFADE_CH_MAX: u32 = 8;
 /// the longest glide of fwgpu_resampler_glide, in frames
 pub const FWGPU_RESAMPLER_GLIDE_FRAMES_MAX: u32 = 16777216;
+/// the longest ride of fwgpu_gain_ride, in frames
+pub const FWGPU_GAIN_RIDE_FRAMES_MAX: u32 = 16777216;
 /// the longest move of fwgpu_spatial_move, in frames
 pub const FWGPU_SPATIAL_MOVE_FRAMES_MAX: u32 = 16777216;
 /// the longest sweep of fwgpu_biquad_sweep, in frames
@@ -218,6 +220,7 @@ extern "C" {
     pub fn fwgpu_graph_output_latency(ctx: *mut fwgpu_ctx, frames: *mut u32) -> c_int;
     pub fn fwgpu_crossfade_to(ctx: *mut fwgpu_ctx, node: i64, position: f32, frames: u32, shape: c_int, x1: f32, y1: f32, x2: f32, y2: f32, at_block: u32) -> c_int;
     pub fn fwgpu_resampler_glide(ctx: *mut fwgpu_ctx, node: i64, ratio: f32, frames: u32, at_block: u32) -> c_int;
+    pub fn fwgpu_gain_ride(ctx: *mut fwgpu_ctx, node: i64, value: f32, frames: u32, shape: c_int, x1: f32, y1: f32, x2: f32, y2: f32, at_block: u32) -> c_int;
     pub fn fwgpu_spatial_move(ctx: *mut fwgpu_ctx, node: i64, x: f32, y: f32, z: f32, frames: u32, at_block: u32) -> c_int;
     pub fn fwgpu_biquad_sweep(ctx: *mut fwgpu_ctx, node: i64, cutoff_hz: f32, q: f32, frames: u32, at_block: u32) -> c_int;
     pub fn fwgpu_proc_info(ctx: *mut fwgpu_ctx, stream_time_secs: *mut f64, stream_status: *mut u32, output_underflows: *mut u64, input_overflows: *mut u64) -> c_int;

@@ -124,6 +124,34 @@ impl GpuVolumeNode {
         self.percent_volume = percent_volume.max(0.0);
         let _ = self.b.set_param(0, percent_volume);
     }
+    /// the longest ride one message takes, in frames
+    pub const RIDE_FRAMES_MAX: u32 = ffi::FWGPU_GAIN_RIDE_FRAMES_MAX;
+    /// From the next block on, ride the gain from where it stands to what `percent_volume` sets, over `frames` frames (0: a hard set
+    /// with no 10 ms glide) along `curve` — one message instead of a `set_percent_volume` per block.  A second ride starts where the
+    /// first stands; `set_percent_volume` during a ride ends it and glides on from its current value.  Before activation only the
+    /// target is kept: the node then starts there.
+    pub fn ride_to(&mut self, percent_volume: f32, frames: u32, curve: CrossfadeCurve) -> Result<(), GpuError> {
+        gain_ride(&self.b, percent_volume, frames, curve)?;
+        self.percent_volume = percent_volume.max(0.0);
+        Ok(())
+    }
+    /// ... over `secs` seconds, rounded to whole frames of `sample_rate`
+    pub fn ride_to_secs(&mut self, percent_volume: f32, secs: f64, sample_rate: u32, curve: CrossfadeCurve) -> Result<(), GpuError> {
+        self.ride_to(percent_volume, (secs * sample_rate as f64).round().max(0.0) as u32, curve)
+    }
+}
+/// fwgpu_gain_ride for a volume or a pan node that is active (before activation there is nothing to send)
+fn gain_ride(b: &Binding, value: f32, frames: u32, curve: CrossfadeCurve) -> Result<(), GpuError> {
+    let (shape, x1, y1, x2, y2) = match curve {
+        CrossfadeCurve::Linear => (0, 0.0, 0.0, 1.0, 1.0),
+        CrossfadeCurve::Bezier(x1, y1, x2, y2) => (1, x1, y1, x2, y2),
+    };
+    if let Some(node) = b.node {
+        let _g = b.cx.control();
+        let rc = unsafe { ffi::fwgpu_gain_ride(b.cx.as_ptr(), node, value, frames, shape, x1, y1, x2, y2, 0) };
+        b.cx.check(rc as i64)?;
+    }
+    Ok(())
 }
 impl AudioNode for GpuVolumeNode {
     fn debug_name(&self) -> &'static str {
@@ -471,6 +499,22 @@ macro_rules! param_node {
 }
 param_node!(GpuStereoPanNode, "stereo_pan", ffi::FWGPU_STEREO_PAN, io(2, 2, 2, 2, false),
             "equal-power stereo pan, pan in [-1, 1], one ParamSmoother per channel", [pan], {set_pan => (0, pan)});
+impl GpuStereoPanNode {
+    /// the longest ride one message takes, in frames
+    pub const RIDE_FRAMES_MAX: u32 = ffi::FWGPU_GAIN_RIDE_FRAMES_MAX;
+    /// From the next block on, ride both ear gains from where they stand to what `pan` sets, over `frames` frames (0: a hard set) along
+    /// `curve`.  The ride travels in the gains, each ear on its own: a ride from hard left to hard right dips in power at the middle —
+    /// one that must hold power is two rides through the centre.  A setter during a ride ends it.
+    pub fn ride_to(&mut self, pan: f32, frames: u32, curve: CrossfadeCurve) -> Result<(), GpuError> {
+        gain_ride(&self.b, pan, frames, curve)?;
+        self.pan = pan;
+        Ok(())
+    }
+    /// ... over `secs` seconds, rounded to whole frames of `sample_rate`
+    pub fn ride_to_secs(&mut self, pan: f32, secs: f64, sample_rate: u32, curve: CrossfadeCurve) -> Result<(), GpuError> {
+        self.ride_to(pan, (secs * sample_rate as f64).round().max(0.0) as u32, curve)
+    }
+}
 param_node!(GpuStereoWidthNode, "stereo_width", ffi::FWGPU_STEREO_WIDTH, io(2, 2, 2, 2, false),
             "mid/side width, one smoothed parameter (0 = mono, 1 = unchanged)", [width], {set_width => (0, width)});
 param_node!(GpuBiquadNode, "biquad", ffi::FWGPU_BIQUAD, io(1, 64, 1, 64, false),

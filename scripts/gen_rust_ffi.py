@@ -93,6 +93,8 @@ def generate():
     o.append("pub const FWGPU_CROSSFADE_CH_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_CROSSFADE_CH_MAX (\d+)", open(HDR).read()).group(1)))
     o.append("/// the longest glide of fwgpu_resampler_glide, in frames")
     o.append("pub const FWGPU_RESAMPLER_GLIDE_FRAMES_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_RESAMPLER_GLIDE_FRAMES_MAX (\d+)", open(HDR).read()).group(1)))
+    o.append("/// the longest ride of fwgpu_gain_ride, in frames")
+    o.append("pub const FWGPU_GAIN_RIDE_FRAMES_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_GAIN_RIDE_FRAMES_MAX (\d+)", open(HDR).read()).group(1)))
     o.append("/// the longest move of fwgpu_spatial_move, in frames")
     o.append("pub const FWGPU_SPATIAL_MOVE_FRAMES_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_SPATIAL_MOVE_FRAMES_MAX (\d+)", open(HDR).read()).group(1)))
     o.append("/// the longest sweep of fwgpu_biquad_sweep, in frames")
