@@ -12,6 +12,7 @@ from .graph import (  # noqa: F401
     BeepTestNode,
     BiquadNode,
     CompileGraphError,
+    CompressorNode,
     DelayNode,
     DummyAudioNode,
     FirReverbNode,
@@ -39,6 +40,6 @@ from .graph import (  # noqa: F401
 
 __all__ = [
     "FirewheelGpuCtx", "HostNode", "VolumeNode", "SumNode", "SamplerNode", "BeepTestNode", "HardClipNode", "MonoToStereoNode",
-    "StereoToMonoNode", "DummyAudioNode", "StereoPanNode", "StereoWidthNode", "BiquadNode", "DelayNode", "FirReverbNode", "ResamplerNode", "SpatialNode", "MeterNode", "LimiterNode", "DuckerNode", "CrossfadeNode", "DelayCompNode", "doppler_ratio", "LoopRange", "SampleFormat", "AddEdgeError",
+    "StereoToMonoNode", "DummyAudioNode", "StereoPanNode", "StereoWidthNode", "BiquadNode", "DelayNode", "FirReverbNode", "ResamplerNode", "SpatialNode", "MeterNode", "LimiterNode", "DuckerNode", "CompressorNode", "CrossfadeNode", "DelayCompNode", "doppler_ratio", "LoopRange", "SampleFormat", "AddEdgeError",
     "CompileGraphError", "FwgpuError", "load_library", "build_library", "LIB_PATH",
 ]

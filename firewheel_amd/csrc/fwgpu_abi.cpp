@@ -476,7 +476,7 @@ int64_t fwgpu_graph_out_node(fwgpu_ctx* c) { return c ? c->graph.id_of(c->graph.
 
 int64_t fwgpu_add_node(fwgpu_ctx* c, int kind, uint32_t n_in, uint32_t n_out, const float* params, int n_params) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
-    if (kind < 0 || kind > K_LAST) return fail(c, FWGPU_ERR_INVALID, "unsupported node kind");
+    if (kind < 0 || kind > K_KIND_MAX) return fail(c, FWGPU_ERR_INVALID, "unsupported node kind");
     if (n_params < 0 || (n_params > 0 && !params)) return fail(c, FWGPU_ERR_INVALID, "params is null but n_params > 0");
     if (kind == K_FIR || kind == K_RESAMPLER) {
         int ir = n_params > 0 ? (int)params[0] : -1;
@@ -1126,6 +1126,11 @@ int fwgpu_node_set_param(fwgpu_ctx* c, int64_t node, int param, float value, uin
             return fail(c, FWGPU_ERR_INVALID, "LimiterNode has no runtime params: ceiling and hold_frames are set at add_node");
         case K_DUCKER:  // threshold, depth and the three times are fixed at construction (moving ones: out of scope)
             return fail(c, FWGPU_ERR_INVALID, "DuckerNode has no runtime params: threshold, depth, attack, release and hold are set at add_node");
+        case K_COMPRESSOR:  // the curve, the times and the makeup are fixed at construction (moving ones: out of scope)
+            static_assert(FWGPU_COMPRESSOR == K_COMPRESSOR && FWGPU_COMPRESSOR_WIN_MAX == COMP_WIN_MAX && FWGPU_COMPRESSOR_HOLD_MAX == COMP_HOLD_MAX &&
+                              FWGPU_COMPRESSOR_CH_MAX == COMP_CH_MAX, "the header's compressor kind and caps");
+            return fail(c, FWGPU_ERR_INVALID,
+                        "CompressorNode has no runtime params: threshold, ratio, knee, attack, release, hold and makeup are set at add_node");
         case K_DELAY_COMP:  // the delay is fixed at construction (a moving one would be an effect: FWGPU_DELAY)
             return fail(c, FWGPU_ERR_INVALID, "DelayCompNode has no runtime params: frames is set at add_node");
         default:

@@ -116,6 +116,26 @@ void spatial_params(float x, float y, float z, uint32_t sample_rate, float* gl, 
     *dl = (int)round(fmax(0.0, s) * itd_max);
     *dr = (int)round(fmax(0.0, -s) * itd_max);
 }
+// SPEC compressor: the static curve in decibels, computed in f64 on the control side and rounded to f32.  T0 is the level
+// at which the knee begins; knot i of the table sits at u_i = 2^(i / 16) * (1 + (i % 16) / 16) times T0 — where the top four mantissa
+// bits of an f32 change — and holds the linear gain there.  G[0] is exactly 1 (gr = 0 at u = 1) and G never rises.
+float compressor_knee_start(float threshold, float knee_db) { return (float)((double)threshold * pow(10.0, -(double)knee_db / 40.0)); }
+void compressor_table(float ratio, float knee_db, float G[COMP_TAB_PAD]) {
+    const double knee = (double)knee_db, slope = 1.0 / (double)ratio - 1.0;
+    for (int i = 0; i < COMP_TAB_PAD; ++i) G[i] = 0.0f;
+    for (int i = 0; i < COMP_TAB_N; ++i) {
+        const double u = ldexp(1.0 + (double)(i % 16) / 16.0, i / 16);
+        const double over = 20.0 * log10(u) - knee / 2.0;  // decibels above the threshold
+        double gr = 0.0;
+        if (knee > 0.0 && 2.0 * fabs(over) <= knee) {
+            const double t = over + knee / 2.0;
+            gr = slope * (t * t) / (2.0 * knee);
+        } else if (over > 0.0) {
+            gr = slope * over;
+        }
+        G[i] = (float)pow(10.0, gr / 20.0);
+    }
+}
 uint32_t delay_frames(float secs, uint32_t sample_rate) {
     double d = round((double)secs * (double)sample_rate);
     if (!(d >= 1.0)) d = 1.0;
@@ -223,6 +243,26 @@ NodeState make_state(int kind, const float* params, int n_params, uint32_t sampl
                             r >= 1.0f && r <= (float)DUCK_WIN_MAX && r == floorf(r) && h >= 0.0f && h <= (float)DUCK_HOLD_MAX && h == floorf(h);
             s.p0 = ok ? t : DUCK_THRESHOLD_DEFAULT;
             s.p1 = ok ? d : 1.0f;
+            s.playhead = ok ? (uint64_t)a : 1;
+            s.loop_start = ok ? (uint64_t)r : 1;
+            s.full_range = ok ? (int)h : 0;
+            s.loop_end = ok ? (uint64_t)(a > r ? a : r) + (uint64_t)h : 0;
+            break;
+        }
+        case K_COMPRESSOR: {  // params: threshold (linear, 1e-6..1000), ratio (1..1000), knee_db (0..24), attack_frames, release_frames
+                              // (1..32768), hold_frames (0..2048), makeup (linear, 0.001..1000)
+            const float t = p(0, COMP_THRESHOLD_DEFAULT), ratio = p(1, COMP_RATIO_DEFAULT), knee = p(2, COMP_KNEE_DEFAULT),
+                        a = p(3, (float)COMP_ATTACK_DEFAULT), r = p(4, (float)COMP_RELEASE_DEFAULT), h = p(5, (float)COMP_HOLD_DEFAULT),
+                        m = p(6, COMP_MAKEUP_DEFAULT);
+            // anything else — NaN, inf, a fraction, out of range — leaves loop_end 0, and the node fails activation at the next update
+            const bool ok = t >= 1e-6f && t <= 1000.0f && ratio >= 1.0f && ratio <= 1000.0f && knee >= 0.0f && knee <= 24.0f && a >= 1.0f &&
+                            a <= (float)COMP_WIN_MAX && a == floorf(a) && r >= 1.0f && r <= (float)COMP_WIN_MAX && r == floorf(r) && h >= 0.0f &&
+                            h <= (float)COMP_HOLD_MAX && h == floorf(h) && m >= 0.001f && m <= 1000.0f;
+            s.phasor_inc = ok ? t : COMP_THRESHOLD_DEFAULT;
+            s.gain = ok ? ratio : 1.0f;
+            s.phasor = ok ? knee : 0.0f;
+            s.p0 = compressor_knee_start(s.phasor_inc, s.phasor);
+            s.p1 = ok ? m : 1.0f;
             s.playhead = ok ? (uint64_t)a : 1;
             s.loop_start = ok ? (uint64_t)r : 1;
             s.full_range = ok ? (int)h : 0;

@@ -631,6 +631,8 @@ float db_to_gain_clamped_neg_100_db(float db);
 void pan_to_gains(float pan, float* gl, float* gr);
 Smoother make_smoother(float val, uint32_t sample_rate);
 void biquad_coefs(int type, float cutoff_hz, float q, uint32_t sample_rate, float co[5]);
+float compressor_knee_start(float threshold, float knee_db);               // T0 (SPEC compressor)
+void compressor_table(float ratio, float knee_db, float G[COMP_TAB_PAD]);  // G[0..COMP_TAB_N), zeros behind it
 void resampler_table(float* h);
 uint64_t resampler_step(float ratio);
 void spatial_params(float x, float y, float z, uint32_t sample_rate, float* gl, float* gr, int* dl, int* dr);

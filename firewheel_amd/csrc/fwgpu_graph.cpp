@@ -317,6 +317,13 @@ bool check_activation(int kind, uint32_t n_in, uint32_t n_out, std::string& err)
                 return false;
             }
             return true;
+        case K_COMPRESSOR:  // SPEC: self-keyed, linked channels, as many outputs as inputs, 1..8 (a keyed bus: the ducker)
+            if (n_in != n_out || n_in < 1 || n_in > COMP_CH_MAX) {
+                err = "CompressorNode needs 1..8 inputs and as many outputs. Got num_inputs: " + std::to_string(n_in) +
+                      ", num_outputs: " + std::to_string(n_out);
+                return false;
+            }
+            return true;
         case K_DELAY_COMP:  // SPEC: a pure delay, as many outputs as inputs, 1..8
             if (n_in != n_out || n_in < 1 || n_in > DCOMP_CH_MAX) {
                 err = "DelayCompNode needs 1..8 inputs and as many outputs. Got num_inputs: " + std::to_string(n_in) +

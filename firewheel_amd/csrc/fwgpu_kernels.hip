@@ -6,7 +6,8 @@
 //   k_limiter.hip.h  SPEC look-ahead limiter: k_limiter — sliding minimum and moving average of a bus, its K blocks in parallel
 //   k_delay_comp.hip.h SPEC latency compensation: k_delay_comp — a pure delay of whole frames, a copy; every block of a batch in parallel
 //   k_ducker.hip.h   SPEC sidechain ducker: k_ducker — window counts over the key bus's gate bits, runs of blocks in parallel
-//   k_single.hip.h   k_single_node — one node of any kind on scratch buffers (behind the three above: it calls into each)
+//   k_compressor.hip.h SPEC bus compressor: k_compressor — a table curve and window sums of the gain target, runs of blocks in parallel
+//   k_single.hip.h   k_single_node — one node of any kind on scratch buffers (behind the four above: it calls into each)
 //   k_control.hip.h  fused plans, control half: k_voice_control (per-voice per-block state machines, K blocks per launch)
 //   k_leaf.hip.h     fused voice-bank plan: k_leaf_sum (HBM-streaming source fetch + gain stages + ordered radix-P sum
 //                    in registers), k_bus_sum (upper sum tree), k_root_out (root sum + interleave)
@@ -40,6 +41,7 @@ __device__ __forceinline__ v4f splat(float x) { return (v4f){x, x, x, x}; }
 #include "k_limiter.hip.h"
 #include "k_delay_comp.hip.h"
 #include "k_ducker.hip.h"
+#include "k_compressor.hip.h"
 #include "k_single.hip.h"
 #include "k_control.hip.h"
 #include "k_leaf.hip.h"
@@ -92,6 +94,14 @@ int launch_level(hipStream_t s, const DevView& v, const int* d_level_nodes, int 
         const int own_hist = K == 1 ? 1 : 0;
         hipLaunchKernelGGL(k_delay_comp, dim3(n_nodes, K), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K, own_hist);
         if (!own_hist) hipLaunchKernelGGL(k_delay_comp_hist, dim3(n_nodes), dim3(WAVE), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K);
+    }
+    // a bus compressor — a workgroup per (node, run of blocks); behind it, unless one workgroup is the whole launch, the workgroup per
+    // node that writes the history of gain targets back (stream order)
+    if (kinds & LB_COMPRESSOR) {
+        const int pieces = v.frames > COMP_RUN_MAX ? (v.frames + COMP_RUN_MAX - 1) / COMP_RUN_MAX : 1;
+        const int own_hist = K == 1 && pieces == 1 ? 1 : 0;
+        hipLaunchKernelGGL(k_compressor, dim3(n_nodes, K * pieces), dim3(COMP_THREADS), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K, own_hist);
+        if (!own_hist) hipLaunchKernelGGL(k_compressor_hist, dim3(n_nodes), dim3(COMP_THREADS), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K);
     }
     if (walkers)
         hipLaunchKernelGGL(k_bus_iir, dim3((n_nodes + WPB - 1) / WPB), dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K);

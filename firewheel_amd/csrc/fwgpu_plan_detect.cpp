@@ -188,7 +188,7 @@ bool detect_fused(const Plan& plan, const HostGraph& graph, uint32_t mbf, FusedB
         const PlanNode& n = plan.nodes[root];
         const bool master_kind = n.kind == K_VOLUME || n.kind == K_HARD_CLIP || n.kind == K_PAN || n.kind == K_WIDTH ||
                                  n.kind == K_BIQUAD || n.kind == K_DELAY || n.kind == K_METER ||  // (a meter: one more launch, the plan stays)
-                                 n.kind == K_LIMITER;                                             // (and so is a limiter)
+                                 n.kind == K_LIMITER || n.kind == K_COMPRESSOR;                    // (and so are a limiter and a compressor)
         if (!master_kind || n.n_in != 2 || n.n_out != 2 || covered[root] || tail.size() >= 16) return false;
         covered[root] = 1;
         tail.push_back(root);

@@ -593,6 +593,7 @@ static int activate_nodes(ImageBuild& b) {
         uint32_t nch = n.n_in < n.n_out ? n.n_in : n.n_out;
         size_t len = 0;
         std::vector<float> head;
+        uint32_t head_pad = 0;  // floats at the slice's start that `head` fills whole, eight to a job: the zeroing job starts behind them
         if (n.kind == K_BIQUAD) {
             len = 5 + 4 * (size_t)nch + BQ_SNAP_LEN;  // (behind the channels' state: a sweep as the chain plan's call found it)
             head.resize(5);
@@ -619,6 +620,15 @@ static int activate_nodes(ImageBuild& b) {
                             "DuckerNode: threshold must be finite and in 1e-6..1000, depth in 0..1, attack_frames and release_frames whole "
                             "numbers in 1..32768, hold_frames a whole number in 0..32768");
             len = duck_ext_len(n.init);
+        } else if (n.kind == K_COMPRESSOR) {  // the table, then the last W values of 65535 - q, zeroed like every slice: zeros are unity
+            if (!comp_state_ok(n.init, (int)n.n_in, (int)n.n_out))
+                return fail(c, FWGPU_ERR_INVALID,
+                            "CompressorNode: threshold must be finite and in 1e-6..1000, ratio in 1..1000, knee_db in 0..24, attack_frames and "
+                            "release_frames whole numbers in 1..32768, hold_frames a whole number in 0..2048, makeup in 0.001..1000");
+            len = comp_ext_len(n.init);
+            head.resize(COMP_TAB_PAD);
+            compressor_table(n.init.gain, n.init.phasor, head.data());
+            head_pad = COMP_TAB_PAD;
         } else if (n.kind == K_DELAY_COMP) {  // hist[n_in][D] and a counter per channel, zeroed like every slice: the SPEC's x[n < 0] and loud = 0
             if (!dcomp_state_ok(n.init, (int)n.n_in, (int)n.n_out))
                 return fail(c, FWGPU_ERR_INVALID, "DelayCompNode: frames must be a whole number in 0..8192");
@@ -649,11 +659,19 @@ static int activate_nodes(ImageBuild& b) {
             si.st.ext_off = off;
             si.st.ext_len = (uint32_t)len;
             AdoptExtJobHost j{};
-            j.off = off;
-            j.zero_len = b.ext_need == before ? (uint32_t)((len + 63) / 64 * 64) : 0u;  // (a bumped slice is zero already)
-            j.n_head = (uint32_t)std::min<size_t>(head.size(), 8);
+            j.off = off + head_pad;
+            j.zero_len = b.ext_need == before ? (uint32_t)((len + 63) / 64 * 64) - head_pad : 0u;  // (a bumped slice is zero already)
+            j.n_head = head_pad ? 0u : (uint32_t)std::min<size_t>(head.size(), 8);
             for (uint32_t k = 0; k < j.n_head; ++k) j.head[k] = head[k];
             if (j.zero_len || j.n_head) b.ext_jobs.push_back(j);
+            // a head longer than one job's eight floats (the compressor's table): jobs of their own, so that no two jobs write one float
+            for (uint32_t h0 = 0; h0 < head_pad; h0 += 8) {
+                AdoptExtJobHost t{};
+                t.off = off + h0;
+                t.n_head = 8;
+                for (uint32_t k = 0; k < 8; ++k) t.head[k] = head[h0 + k];
+                b.ext_jobs.push_back(t);
+            }
         }
         b.inits.push_back(si);
     }

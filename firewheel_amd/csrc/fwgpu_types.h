@@ -14,7 +14,9 @@ enum : int {
     K_DUCKER = 18,  // SPEC sidechain ducker: n main + k key inputs, n outputs; window counts of the key's gate bits, no latency
     K_DELAY_COMP = 19,  // SPEC latency compensation: n -> n, a pure delay of a whole number of frames, a copy with no arithmetic
     K_CROSSFADE = 20,  // SPEC crossfader: 2n -> n, two buses blended along an automated curve of the node's frame count; k_level<0> renders it
-    K_LAST = K_CROSSFADE,  // the last node kind
+    K_LAST = K_CROSSFADE,  // the last node kind that k_level renders and a message may reach (the kinds behind it bring a kernel of their own)
+    K_COMPRESSOR = 21,  // SPEC bus compressor: n -> n, self-keyed, linked channels; a table curve and window sums of the gain target, no latency
+    K_KIND_MAX = K_COMPRESSOR,  // the last node kind fwgpu_add_node accepts
 };
 #if defined(__HIPCC__)
 #define FW_TYPES_HD __host__ __device__
@@ -34,20 +36,21 @@ FW_TYPES_HD constexpr float fw_hi_float_of(double d) { return fw_float_of((uint3
 // needed 248 VGPRs (2 waves per SIMD — nothing to hide HBM latency behind, 0.9 TB/s on a level of volume nodes).  Set 0: the streaming
 // kinds (volume, pan, sum, hard clip, mono<->stereo, width: 127 VGPRs), set 1: serial recurrences / filter banks / libm (beep, biquad,
 // delay, resampler, spatialiser: 147), set 2: the sampler (every sample format, wraps, tails, ramps).  Sets 4 and above are no
-// instantiation of k_level: a kernel of its own, launched next to them (k_limiter, k_ducker, k_delay_comp).
+// instantiation of k_level: a kernel of its own, launched next to them (k_limiter, k_ducker, k_delay_comp, k_compressor).
 FW_TYPES_HD inline int kind_set(int kind) {
     if (kind == K_SAMPLER) return 2;
     if (kind == K_LIMITER) return 4;
     if (kind == K_DUCKER) return 5;
     if (kind == K_DELAY_COMP) return 6;
+    if (kind == K_COMPRESSOR) return 7;
     return (kind == K_BEEP || kind == K_BIQUAD || kind == K_DELAY || kind == K_RESAMPLER || kind == K_SPATIAL) ? 1 : 0;
 }
 FW_TYPES_HD inline bool kind_has_own_kernel(int kind) { return kind_set(kind) >= 4; }
 // a level's launch bits (launch_level's `kinds`): bit s = the level holds a kind of set s, plus LB_WALKERS for a biquad / delay (in a
 // batch, the ones that are bus effects go to the walkers' kernel k_bus_iir)
-enum : int { LB_SET0 = 1, LB_SET1 = 2, LB_SET2 = 4, LB_WALKERS = 8, LB_LIMITER = 16, LB_DUCKER = 32, LB_DELAY_COMP = 64 };
+enum : int { LB_SET0 = 1, LB_SET1 = 2, LB_SET2 = 4, LB_WALKERS = 8, LB_LIMITER = 16, LB_DUCKER = 32, LB_DELAY_COMP = 64, LB_COMPRESSOR = 128 };
 FW_TYPES_HD inline int kind_launch_bits(int kind) { return (1 << kind_set(kind)) | ((kind == K_BIQUAD || kind == K_DELAY) ? LB_WALKERS : 0); }
-static_assert(LB_LIMITER == 1 << 4 && LB_DUCKER == 1 << 5 && LB_DELAY_COMP == 1 << 6, "a launch bit is 1 << kind_set");
+static_assert(LB_LIMITER == 1 << 4 && LB_DUCKER == 1 << 5 && LB_DELAY_COMP == 1 << 6 && LB_COMPRESSOR == 1 << 7, "a launch bit is 1 << kind_set");
 // K_CROSSFADE: n output channels (bus A on inputs 0..n-1, bus B on n..2n-1), the longest segment in frames (2^24: k and dur convert to
 // f32 exactly), the bisection steps of the Bezier solver, and the two laws / shapes
 #define XF_CH_MAX 8
@@ -74,6 +77,24 @@ static_assert(LB_LIMITER == 1 << 4 && LB_DUCKER == 1 << 5 && LB_DELAY_COMP == 1 
 #define DUCK_ATTACK_DEFAULT 480u
 #define DUCK_RELEASE_DEFAULT 12000u
 #define DUCK_HOLD_DEFAULT 4800u
+// K_COMPRESSOR: the caps of attack / release and of hold (frames) and of the channel count.  The node's ext slice holds the gain table
+// G[0..COMP_TAB_N) (16 knots per octave over 20 octaves above T0, and the knot that ends them) padded to COMP_TAB_PAD floats and, behind
+// it, the last W = max(A, R) + H values of 65535 - q as 16-bit words, oldest first, two to a 32-bit slot.  A workgroup stages W + run
+// of them in LDS: COMP_RUN_MAX is sized so that two workgroups share a CU's 160 KiB (k_compressor.hip.h CompLds).
+#define COMP_WIN_MAX 32768u
+#define COMP_HOLD_MAX 2048u
+#define COMP_RUN_MAX 4096
+#define COMP_CH_MAX 8
+#define COMP_TAB_N 321
+#define COMP_TAB_PAD 328
+#define COMP_OCTAVES 20
+#define COMP_THRESHOLD_DEFAULT 0.25f
+#define COMP_RATIO_DEFAULT 4.0f
+#define COMP_KNEE_DEFAULT 6.0f
+#define COMP_ATTACK_DEFAULT 240u
+#define COMP_RELEASE_DEFAULT 12000u
+#define COMP_HOLD_DEFAULT 0u
+#define COMP_MAKEUP_DEFAULT 1.0f
 // K_LIMITER: LIM_LOOK terms in the moving average (one per lane of a wave; 1/64 is an exact scale), latency LIM_LOOK - 1 frames.  The
 // node's ext slice keeps the last H + LIM_HIST_PAD input frames per channel (H = hold_frames); a block reads back H + 2 * (LIM_LOOK - 1).
 #define LIM_LOOK 64
@@ -171,12 +192,16 @@ struct NodeState {
     //        them): the ride's end only clears these seven fields, back to make_state's zeros.  No other message reaches them; a
     //        node's state keeps its slot over a plan install.  The arithmetic is gain_ride_* below the struct
     //   METER: ext = ring[R][n_in] of MeterRec (4 floats each), loop_end = R (0: the creation parameter was refused)
-    //   LIMITER, DUCKER, DELAY_COMP: loop_end = 0 marks a creation parameter that was refused; the valid states and the slice lengths
-    //        are lim_/duck_/dcomp_state_ok and _ext_len below the struct
+    //   LIMITER, DUCKER, DELAY_COMP, COMPRESSOR: loop_end = 0 marks a creation parameter that was refused; the valid states and the
+    //        slice lengths are lim_/duck_/dcomp_/comp_state_ok and _ext_len below the struct
     //   LIMITER: p0 = ceiling C, loop_start = hold_frames H, loop_end = HK; ext = hist[n_in][HK]: the last HK input frames per channel,
     //        oldest first
     //   DUCKER: p0 = threshold T, p1 = depth D, playhead = A, loop_start = R, full_range = H, loop_end = W; ext = the last W gate bits
     //        on[], oldest first, bit i in bit i % 32 of word i / 32 (the float slots hold 32-bit words), the bits from W on zero
+    //   COMPRESSOR: p0 = T0 (where the knee begins), p1 = makeup M, playhead = A, loop_start = R, full_range = H, loop_end = W; phasor_inc,
+    //        gain, phasor = the creation parameters threshold, ratio, knee_db (the host builds the table from them at activation; no
+    //        kernel reads them); ext = G[COMP_TAB_PAD], then the last W values of 65535 - q as 16-bit words, oldest first, value i in
+    //        bits 16 * (i % 2) of slot COMP_TAB_PAD + i / 2 — zeros, as every slice starts, are the SPEC's unity history
     //   DELAY_COMP: loop_start = D, loop_end = D + 1; ext = hist[n_in][D]: the last D input frames per channel, oldest first (a block
     //        flagged silent enters as zeros), then loud[n_in]: 32-bit counters in the float slots — how many of the frames in front of
     //        the next block may still be heard
@@ -209,6 +234,14 @@ FW_TYPES_HD inline bool dcomp_state_ok(const NodeState& s, int n_in, int n_out) 
     return D <= DCOMP_MAX && s.loop_end == D + 1 && n_in == n_out && n_in >= 1 && n_in <= DCOMP_CH_MAX;
 }
 FW_TYPES_HD inline uint32_t dcomp_ext_len(const NodeState& s, int n_in) { return (uint32_t)n_in * (uint32_t)s.loop_start + (uint32_t)n_in; }
+// (n -> n; the table, then W = max(A, R) + H 16-bit words in 32-bit slots)
+FW_TYPES_HD inline bool comp_state_ok(const NodeState& s, int n_in, int n_out) {
+    const uint64_t A = s.playhead, R = s.loop_start, W = s.loop_end;
+    const int H = s.full_range;
+    return A >= 1 && A <= COMP_WIN_MAX && R >= 1 && R <= COMP_WIN_MAX && H >= 0 && H <= (int)COMP_HOLD_MAX &&
+           W == (A > R ? A : R) + (uint64_t)H && n_in == n_out && n_in >= 1 && n_in <= COMP_CH_MAX && s.p0 > 0.0f && s.p1 > 0.0f;
+}
+FW_TYPES_HD inline uint32_t comp_ext_len(const NodeState& s) { return (uint32_t)COMP_TAB_PAD + (uint32_t)((s.loop_end + 1) / 2); }
 
 // K_RESAMPLER ratio glide (SPEC): ONE statement for the node kernels, the control kernel and the leaf kernel.  All in
 // wrapping u64 arithmetic; a signed inc travels as its two's-complement bits.

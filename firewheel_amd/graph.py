@@ -8,6 +8,7 @@ Names, argument meaning and error behaviour follow the reference (BillyDM/firewh
 All arithmetic happens in libfwgpu's HIP kernels; this file only marshals arguments.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -564,6 +565,86 @@ class DuckerNode(_Node):
 
     def params(self):
         return [float(self.threshold), float(self.depth), float(self.attack_frames), float(self.release_frames), float(self.hold_frames)]
+
+
+class CompressorNode(_Node):
+    """SPEC node: bus compressor — self-keyed, linked channels.  Above `threshold` (linear, 1e-6..1000) the level
+    rises `ratio` (1..1000) times slower, through a soft knee `knee_db` wide (0..24); the gain comes down over `attack_frames`, stays for
+    `hold_frames` after the level has fallen and comes back over `release_frames` (1..32768, 0..2048, 1..32768); `makeup` (linear,
+    0.001..1000) scales the result.  The curve is a table of 16 knots per octave built on the host, the gain a function of integer sums
+    over windows of the quantised target, no recurrence in time: the blocks of a batch render in parallel, bit-exact against the numpy
+    model of tests/compressor_model.py; no latency.  add_node(channels, channels, CompressorNode(...)), channels in 1..8.
+    `threshold_db=` / `makeup_db=` give the two in decibels instead, converted by MeterNode.db_to_gain.  No parameters after creation."""
+    KIND = 21
+    WIN_MAX, HOLD_MAX, CH_MAX = 32768, 2048, 8
+    KNOTS_PER_OCTAVE, OCTAVES = 16, 20
+
+    def __init__(self, threshold=0.25, ratio=4.0, knee_db=6.0, attack_frames=240, release_frames=12000, hold_frames=0, makeup=1.0, channels=2,
+                 threshold_db=None, makeup_db=None):
+        self.threshold = float(MeterNode.db_to_gain(threshold_db)) if threshold_db is not None else threshold
+        self.ratio = ratio
+        self.knee_db = knee_db
+        self.attack_frames = attack_frames
+        self.release_frames = release_frames
+        self.hold_frames = hold_frames
+        self.makeup = float(MeterNode.db_to_gain(makeup_db)) if makeup_db is not None else makeup
+        self.channels = channels
+
+    def attack_secs(self, sample_rate):
+        return self.attack_frames / float(sample_rate)
+
+    def release_secs(self, sample_rate):
+        return self.release_frames / float(sample_rate)
+
+    def hold_secs(self, sample_rate):
+        return self.hold_frames / float(sample_rate)
+
+    @classmethod
+    def from_secs(cls, sample_rate, attack_secs=0.005, release_secs=0.25, hold_secs=0.0, **kw):
+        """the three times in seconds, rounded to whole frames of `sample_rate`"""
+        return cls(attack_frames=max(1, int(round(attack_secs * sample_rate))), release_frames=max(1, int(round(release_secs * sample_rate))),
+                   hold_frames=max(0, int(round(hold_secs * sample_rate))), **kw)
+
+    def params(self):
+        return [float(self.threshold), float(self.ratio), float(self.knee_db), float(self.attack_frames), float(self.release_frames),
+                float(self.hold_frames), float(self.makeup)]
+
+    def knee_start(self):
+        """T0: the level at which the knee begins, as the node computes it (f64, rounded to f32)"""
+        t, knee = float(np.float32(self.threshold)), float(np.float32(self.knee_db))
+        return np.float32(t * math.pow(10.0, -knee / 40.0))
+
+    def table(self):
+        """G[0..320]: the gain at the knots u_i = 2^(i // 16) * (1 + (i % 16) / 16) times T0, as the node computes it"""
+        knee, slope = float(np.float32(self.knee_db)), 1.0 / float(np.float32(self.ratio)) - 1.0
+        G = np.empty(self.KNOTS_PER_OCTAVE * self.OCTAVES + 1, dtype=np.float32)
+        for i in range(G.size):
+            u = math.ldexp(1.0 + (i % 16) / 16.0, i // 16)
+            over = 20.0 * math.log10(u) - knee / 2.0
+            gr = 0.0
+            if knee > 0.0 and 2.0 * abs(over) <= knee:
+                t = over + knee / 2.0
+                gr = slope * (t * t) / (2.0 * knee)
+            elif over > 0.0:
+                gr = slope * over
+            G[i] = np.float32(math.pow(10.0, gr / 20.0))
+        return G
+
+    def static_gain(self, level):
+        """the gain (makeup not included) a steady input of linear `level` settles at, before its quantisation to 16 bits: the table
+        curve on the host, for a UI's transfer plot.  level: a number or an array, NaN-free"""
+        G, f32 = self.table(), np.float32
+        key = np.abs(np.asarray(level, dtype=f32))
+        with np.errstate(over="ignore"):
+            u = (key / self.knee_start()).astype(f32)
+        over = u > f32(1)
+        d = np.where(over, u.view(np.uint32).astype(np.int64) - 0x3F800000, 0)
+        i = d >> 19
+        fr = (d & 0x7FFFF).astype(f32) * f32(2.0 ** -19)
+        sat = i >= G.size - 1
+        i = np.minimum(i, G.size - 2)
+        t = (G[i] + ((G[i + 1] - G[i]).astype(f32) * fr).astype(f32)).astype(f32)
+        return np.where(over, np.where(sat, G[-1], t), f32(1)).astype(f32)
 
 
 class DelayCompNode(_Node):

@@ -65,8 +65,12 @@ enum fwgpu_node_kind {
                                  default 12000), hold_frames (0..32768, default 4800); see "sidechain ducker" below */
     FWGPU_DELAY_COMP = 19,    /* SPEC latency compensation (n in, n out, n in 1..8)  params: frames (a whole number in
                                  0..FWGPU_DELAY_COMP_MAX, default 63); see "latency compensation" below */
-    FWGPU_CROSSFADE = 20      /* SPEC crossfader (2n in, n out, n in 1..8)  params: position (0..1, default 0 = all of bus A), law
+    FWGPU_CROSSFADE = 20,     /* SPEC crossfader (2n in, n out, n in 1..8)  params: position (0..1, default 0 = all of bus A), law
                                  (0 linear, 1 equal power; default 1); see "crossfader" below and fwgpu_crossfade_to */
+    FWGPU_COMPRESSOR = 21     /* SPEC bus compressor (n in, n out, n in 1..8)  params: threshold (linear, 1e-6..1000, default 0.25), ratio
+                                 (1..1000, default 4), knee_db (full width, 0..24, default 6), attack_frames (1..32768, default 240),
+                                 release_frames (1..32768, default 12000), hold_frames (0..2048, default 0), makeup (linear,
+                                 0.001..1000, default 1.0); see "bus compressor" below */
 };
 
 /* sample formats — core/sample_resource.rs:28-335 */
@@ -582,6 +586,50 @@ int64_t fwgpu_meter_read(fwgpu_ctx* ctx, int64_t node, uint64_t first_block, uin
  * zeroed at activation (the gate was closed) and kept across plan changes.  A ducker is never part of a fused plan's master chain
  * (it is not 2 -> 2): the level executor renders it.  fwgpu_node_process renders it block by block with the history kept between
  * calls. */
+
+/* ---- bus compressor (FWGPU_COMPRESSOR; SPEC).  The third dynamics tool of a bus, beside the limiter and the
+ * ducker: it holds an SFX or dialogue bus together, and on the master in front of the limiter it leaves the limiter little to do.
+ * Self-keyed with linked channels: n_in == n_out = n in 1..FWGPU_COMPRESSOR_CH_MAX, any other shape is refused at fwgpu_add_node (a
+ * keyed bus is the ducker's job).  A threshold T that is NaN, infinite or outside 1e-6..1000, a ratio outside 1..1000, a knee_db outside
+ * 0..24, an attack_frames A or release_frames R that is NaN, a fraction or outside 1..FWGPU_COMPRESSOR_WIN_MAX, a hold_frames H that is
+ * NaN, a fraction or outside 0..FWGPU_COMPRESSOR_HOLD_MAX and a makeup M outside 0.001..1000 fail activation at fwgpu_update
+ * (FWGPU_ERR_INVALID).  No parameters after creation (fwgpu_node_set_param is refused), no smoother, no messages, no latency.
+ * At activation, in f64 with the host's libm:
+ *   T0   = (float)(T * 10^(-knee_db / 40))                      (the level at which the knee begins)
+ *   G[i] for i in 0..320, 16 knots per octave over 20 octaves: knot i sits at u_i = 2^(i / 16) * (1 + (i % 16) / 16) (i / 16 the integer
+ *          quotient); with over = 20 * log10(u_i) - knee_db / 2 and slope = 1 / ratio - 1:
+ *          gr = slope * (over + knee_db / 2)^2 / (2 * knee_db)   if knee_db > 0 and 2 * |over| <= knee_db
+ *          gr = slope * over                                     otherwise, if over > 0;      gr = 0 otherwise
+ *          G[i] = (float)10^(gr / 20)                            (G[0] is exactly 1.0f and G never rises)
+ * With x_c[n] channel c at frame n since the node's activation (every frame of every block, full or short; a channel flagged silent
+ * for a block counts as +0.0 and is not read):
+ *   key[n] = max over c of |x_c[n]|         (fmaxf from +0.0: a NaN sample is ignored; never negative)
+ *   u[n]   = key[n] / T0                    (IEEE f32 division)
+ *   t[n]   = 1.0f                           if !(u[n] > 1.0f); else with d = bits(u[n]) - 0x3F800000, i = d >> 19,
+ *                                           fr = (float)(d & 0x7FFFF) * 2^-19 (exact):
+ *            G[320]                         if i >= 320 (an infinite key included)
+ *            G[i] + ((G[i+1] - G[i]) * fr)  otherwise (every operation a separately rounded f32 operation, no FMA)
+ *   q[n]   = (uint32)((t[n] * 65535.0f) + 0.5f)            (0..65535; q[n < 0] = 65535: unity)
+ *   m[n]   = min of q[k], k in [n-H, n]                     (the hold: a peak detector over H frames)
+ *   ca[n]  = sum of m[k], k in (n-A, n]     cr[n] = sum of m[k], k in (n-R, n]              (exact integers, below 2^32)
+ *   a[n]   = (float)ca[n] / (float)(A * 65535)              r[n] = (float)cr[n] / (float)(R * 65535)
+ *   g[n]   = fminf(a[n], r[n])
+ *   y_c[n] = x_c[n] * (g[n] * M)            (g * M one product, then one product per channel)
+ * No recurrence in time: the gain is a function of integer sums over windows of q, so the K blocks of a batch render in parallel and
+ * the output is bit-exact against a few lines of numpy (tests/compressor_model.py) in any order of evaluation.  While the level has
+ * stayed at or below T0 for max(A, R) + H frames g is exactly 1.0f, and with M = 1 the output is the input bit for bit.  g never
+ * exceeds 1 and never falls below G[320] minus the 1/65535 quantum.  With A <= R a step up in level takes the gain down linearly over A
+ * frames; a step down lets it back linearly over R, which begins H frames later.  A burst shorter than R reaches full reduction in A
+ * frames, returns over A to the plateau 1 - (1 - t) * len / R and leaves over the rest of R: the price of having no recurrence, as
+ * for the ducker.  A steady level settles at q / 65535, within 2^-16 of the curve; the table's interpolation stays within 0.01 dB of
+ * the exact curve.  ratio == 1 is the identity times M.  A channel flagged silent gives an output that is zero-filled and flagged and
+ * still lets the others drive the gain; nothing else is flagged.  The node's state is the table and the last max(A, R) + H values of
+ * q as 16-bit words, unity at activation and kept across plan changes.  A 2 -> 2 compressor may sit in a fused plan's master chain, as
+ * a limiter may: one more launch per batch, the plan stays.  fwgpu_node_process renders it block by block with the history kept
+ * between calls. */
+#define FWGPU_COMPRESSOR_WIN_MAX 32768
+#define FWGPU_COMPRESSOR_HOLD_MAX 2048
+#define FWGPU_COMPRESSOR_CH_MAX 8
 
 /* ---- latency compensation (FWGPU_DELAY_COMP and the latency queries; SPEC).  A limiter makes its bus
  * FWGPU_LIMITER_LATENCY frames late; summed with a bus that is not, the two are misaligned, and a dry signal mixed with its limited

@@ -28,6 +28,10 @@ pub const FWGPU_DELAY_COMP_MAX: u32 = 8192;
 /// the longest segment of fwgpu_crossfade_to, in frames, and the most channels per bus of a FWGPU_CROSSFADE node
 pub const FWGPU_CROSSFADE_FRAMES_MAX: u32 = 16777216;
 pub const FWGPU_CROSSFADE_CH_MAX: u32 = 8;
+/// the longest attack / release window and hold of a FWGPU_COMPRESSOR node, in frames, and its most channels
+pub const FWGPU_COMPRESSOR_WIN_MAX: u32 = 32768;
+pub const FWGPU_COMPRESSOR_HOLD_MAX: u32 = 2048;
+pub const FWGPU_COMPRESSOR_CH_MAX: u32 = 8;
 /// the longest glide of fwgpu_resampler_glide, in frames
 pub const FWGPU_RESAMPLER_GLIDE_FRAMES_MAX: u32 = 16777216;
 /// the longest ride of fwgpu_gain_ride, in frames
@@ -103,6 +107,7 @@ pub const FWGPU_LIMITER: c_int = 17;
 pub const FWGPU_DUCKER: c_int = 18;
 pub const FWGPU_DELAY_COMP: c_int = 19;
 pub const FWGPU_CROSSFADE: c_int = 20;
+pub const FWGPU_COMPRESSOR: c_int = 21;
 
 // enum fwgpu_sample_format
 pub const FWGPU_INTERLEAVED_I16: c_int = 0;

@@ -785,6 +785,65 @@ impl AudioNode for GpuDuckerNode {
     }
 }
 
+/// Bus compressor (SPEC, DESIGN.md §6 of the fwgpu repository): self-keyed with linked channels.  Above `threshold` the level rises
+/// `ratio` times slower, through a soft knee `knee_db` wide; the gain comes down over `attack_frames`, stays for `hold_frames` and comes
+/// back over `release_frames`; `makeup` scales the result.  The curve is a table built on the host, the gain a function of integer sums
+/// over windows of the quantised target: no recurrence in time, so the blocks of a batch render in parallel on the device; no
+/// latency.  As many outputs as inputs, 1..=8.
+pub struct GpuCompressorNode {
+    b: Binding,
+    threshold: f32,
+    ratio: f32,
+    knee_db: f32,
+    attack_frames: u32,
+    release_frames: u32,
+    hold_frames: u32,
+    makeup: f32,
+}
+impl GpuCompressorNode {
+    /// the longest attack / release window and the longest hold, in frames
+    pub const WIN_MAX: u32 = ffi::FWGPU_COMPRESSOR_WIN_MAX;
+    pub const HOLD_MAX: u32 = ffi::FWGPU_COMPRESSOR_HOLD_MAX;
+    /// `threshold`: linear, finite, 1e-6..=1000; `ratio`: 1..=1000; `knee_db`: 0..=24; `attack_frames`, `release_frames`:
+    /// 1..=[`GpuCompressorNode::WIN_MAX`]; `hold_frames`: 0..=[`GpuCompressorNode::HOLD_MAX`]; `makeup`: linear, 0.001..=1000.
+    /// Anything else fails activation.
+    #[allow(clippy::too_many_arguments)]
+    pub fn new(cx: &Arc<GpuContext>, threshold: f32, ratio: f32, knee_db: f32, attack_frames: u32, release_frames: u32, hold_frames: u32,
+               makeup: f32) -> Self {
+        Self { b: Binding::new(cx), threshold, ratio, knee_db, attack_frames, release_frames, hold_frames, makeup }
+    }
+    /// threshold and makeup in decibels, through core/util.rs db_to_gain
+    #[allow(clippy::too_many_arguments)]
+    pub fn with_db(cx: &Arc<GpuContext>, threshold_db: f32, ratio: f32, knee_db: f32, attack_frames: u32, release_frames: u32, hold_frames: u32,
+                   makeup_db: f32) -> Self {
+        Self::new(cx, firewheel_core::util::db_to_gain(threshold_db), ratio, knee_db, attack_frames, release_frames, hold_frames,
+                  firewheel_core::util::db_to_gain(makeup_db))
+    }
+    /// a time in seconds as whole frames of `sample_rate` (what the three `_frames` arguments take)
+    pub fn secs_to_frames(secs: f64, sample_rate: u32) -> u32 {
+        (secs * sample_rate as f64).round().max(0.0) as u32
+    }
+}
+impl AudioNode for GpuCompressorNode {
+    fn debug_name(&self) -> &'static str {
+        "compressor"
+    }
+    fn info(&self) -> AudioNodeInfo {
+        io(1, 8, 1, 8, false)
+    }
+    fn activate(&mut self, _sr: u32, _mbf: usize, num_inputs: usize, num_outputs: usize) -> Result<Box<dyn AudioNodeProcessor>, Box<dyn Error>> {
+        self.b.activate(
+            ffi::FWGPU_COMPRESSOR,
+            num_inputs,
+            num_outputs,
+            &[self.threshold, self.ratio, self.knee_db, self.attack_frames as f32, self.release_frames as f32, self.hold_frames as f32, self.makeup],
+        )
+    }
+    fn deactivate(&mut self, _p: Option<Box<dyn AudioNodeProcessor>>) {
+        self.b.deactivate()
+    }
+}
+
 /// Latency compensation (SPEC, DESIGN.md §6 of the fwgpu repository): a pure delay of `frames` whole frames, a copy with no arithmetic —
 /// what a bus needs that is summed with a bus a [`GpuLimiterNode`] has made [`GpuLimiterNode::LATENCY_FRAMES`] frames late.  No
 /// recurrence in time, so every block of a batch renders in parallel on the device.  An output block is flagged silent exactly when

@@ -91,6 +91,10 @@ def generate():
     o.append("/// the longest segment of fwgpu_crossfade_to, in frames, and the most channels per bus of a FWGPU_CROSSFADE node")
     o.append("pub const FWGPU_CROSSFADE_FRAMES_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_CROSSFADE_FRAMES_MAX (\d+)", open(HDR).read()).group(1)))
     o.append("pub const FWGPU_CROSSFADE_CH_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_CROSSFADE_CH_MAX (\d+)", open(HDR).read()).group(1)))
+    o.append("/// the longest attack / release window and hold of a FWGPU_COMPRESSOR node, in frames, and its most channels")
+    o.append("pub const FWGPU_COMPRESSOR_WIN_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_COMPRESSOR_WIN_MAX (\d+)", open(HDR).read()).group(1)))
+    o.append("pub const FWGPU_COMPRESSOR_HOLD_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_COMPRESSOR_HOLD_MAX (\d+)", open(HDR).read()).group(1)))
+    o.append("pub const FWGPU_COMPRESSOR_CH_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_COMPRESSOR_CH_MAX (\d+)", open(HDR).read()).group(1)))
     o.append("/// the longest glide of fwgpu_resampler_glide, in frames")
     o.append("pub const FWGPU_RESAMPLER_GLIDE_FRAMES_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_RESAMPLER_GLIDE_FRAMES_MAX (\d+)", open(HDR).read()).group(1)))
     o.append("/// the longest ride of fwgpu_gain_ride, in frames")
