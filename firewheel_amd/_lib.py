@@ -152,6 +152,9 @@ SIGNATURES = {
     "fwgpu_graph_latency_report": (i64, [vp, C.POINTER(LatencySkew), u32]),
     "fwgpu_graph_output_latency": (ci, [vp, C.POINTER(u32)]),
     "fwgpu_crossfade_to": (ci, [vp, i64, f32, u32, ci, f32, f32, f32, f32, u32]),
+    "fwgpu_fir_morph": (ci, [vp, i64, f32, u32, ci, f32, f32, f32, f32, u32]),
+    "fwgpu_fir_set_ir": (ci, [vp, i64, ci, ci]),
+    "fwgpu_fir_morph_stats": (ci, [vp, C.POINTER(u64), C.POINTER(u64)]),
     "fwgpu_resampler_glide": (ci, [vp, i64, f32, u32, u32]),
     "fwgpu_gain_ride": (ci, [vp, i64, f32, u32, ci, f32, f32, f32, f32, u32]),
     "fwgpu_spatial_move": (ci, [vp, i64, f32, f32, f32, u32, u32]),

@@ -448,7 +448,7 @@ void fwgpu_ctx_destroy(fwgpu_ctx* c) {
     for (hipEvent_t e : c->ev_stream_pub)
         if (e) (void)hipEventDestroy(e);
     DevBuf* bufs[] = {&c->d_states, &c->d_ext, &c->d_samples, &c->d_rt_sync, &c->d_lazy_horizon, &c->d_cmds, &c->d_in_stage, &c->d_out_stage, &c->d_scratch_pool,
-                      &c->d_scratch_flags, &c->d_scratch_tab, &c->d_mask, &c->d_trace, &c->d_rs_table};
+                      &c->d_scratch_flags, &c->d_scratch_tab, &c->d_mask, &c->d_trace, &c->d_rs_table, &c->d_fir_stats};
     for (DevBuf* b : bufs) b->release();
     for (TimerCat& t : c->timers)
         for (auto& p : t.ev) {
@@ -496,7 +496,35 @@ int64_t fwgpu_add_node(fwgpu_ctx* c, int kind, uint32_t n_in, uint32_t n_out, co
         if (!check_activation(kind, n_in, n_out, err)) return fail(c, FWGPU_ERR_INVALID, err);
     }
     NodeState st = make_state(kind, params, n_params, c->sample_rate);
-    return c->graph.add_node(kind, n_in, n_out, st);
+    const int64_t id = c->graph.add_node(kind, n_in, n_out, st);
+    if (kind == K_FIR && n_params >= 2 && id >= 0)  // SPEC FIR morph: two or more parameters make the node morph-capable
+        if (HostNode* hn = c->graph.get(id)) {
+            hn->fir_morph = true;
+            hn->fir_ir[0] = st.sample;
+            hn->fir_ir[1] = st.s1.status;
+            hn->fir_max_taps = fw_bits_of(st.s1.a);
+            hn->fir_target = st.p1;
+            hn->fir_target_end = 0;
+        }
+    return id;
+}
+// control side: `sample` has lost a FIR user (a node removed, a slot exchanged) — each of its converted copies (one per channel and
+// padded length T) that no FIR node of that T, and none that waits for its activation, uses any more goes to limbo until the first image built without it is the
+// active one
+static void fir_ir_release(fwgpu_ctx* c, int sample) {
+    if (sample < 0) return;
+    for (auto it = c->ir_cache.begin(); it != c->ir_cache.end();) {
+        bool used = false;
+        if (std::get<0>(it->first) == sample)
+            for (const HostNode& n : c->graph.nodes)  // (a node that waits for its activation may need any length: it keeps the copies)
+                if (fir_uses_sample(n, sample) && (!n.activated || n.init.loop_start == std::get<2>(it->first))) used = true;
+        if (std::get<0>(it->first) == sample && !used) {
+            c->limbo.push_back({c->build_gen + 1, 1, it->second, (uint32_t)(((size_t)std::get<2>(it->first) + 63) / 64 * 64)});
+            it = c->ir_cache.erase(it);
+        } else {
+            ++it;
+        }
+    }
 }
 int fwgpu_remove_node(fwgpu_ctx* c, int64_t node) {
     NEED_CTX(c, FWGPU_ERR_INVALID);
@@ -506,7 +534,7 @@ int fwgpu_remove_node(fwgpu_ctx* c, int64_t node) {
     struct Freed {
         bool any = false, activated = false;
         uint32_t off = 0, len = 0;
-        int kind = 0, ir = -1;
+        int kind = 0, ir = -1, ir_b = -1;
     } fr;
     if (HostNode* hn = c->graph.get(node))
         if (hn->activated) {
@@ -514,7 +542,8 @@ int fwgpu_remove_node(fwgpu_ctx* c, int64_t node) {
             fr.any = hn->init.ext_len != 0;
             fr.off = hn->init.ext_off;
             fr.len = hn->init.ext_len;
-            fr.ir = hn->kind == K_FIR ? hn->init.sample : -1;
+            fr.ir = hn->kind == K_FIR ? (hn->fir_morph ? hn->fir_ir[0] : hn->init.sample) : -1;
+            fr.ir_b = hn->kind == K_FIR && hn->fir_morph ? hn->fir_ir[1] : -1;
         }
     if (HostNode* hn = c->graph.get(node)) fr.kind = hn->kind;
     int held_stream = -1;  // (SPEC streaming source: removing the sampler leaves its stream finished)
@@ -523,21 +552,8 @@ int fwgpu_remove_node(fwgpu_ctx* c, int64_t node) {
     if (rc == 0 && held_stream >= 0 && held_stream < (int)c->streams.size()) stream_detach(c, c->streams[held_stream]);
     if (rc) return fail(c, rc, "remove_node: unknown node or graph in/out node");
     if (fr.any) c->limbo.push_back({c->build_gen + 1, 1, fr.off, (uint32_t)(((size_t)fr.len + 63) / 64 * 64)});
-    if (fr.ir >= 0) {  // the f32 copy of an impulse response goes with its last FIR user
-        bool used = false;
-        for (const HostNode& n : c->graph.nodes)
-            if (n.alive && n.kind == K_FIR && n.init.sample == fr.ir) used = true;
-        if (!used)
-            for (auto it = c->ir_cache.begin(); it != c->ir_cache.end();) {
-                if (it->first.first == fr.ir) {
-                    c->limbo.push_back({c->build_gen + 1, 1, it->second, (uint32_t)(((size_t)c->ir_len[it->first] + 63) / 64 * 64)});
-                    c->ir_len.erase(it->first);
-                    it = c->ir_cache.erase(it);
-                } else {
-                    ++it;
-                }
-            }
-    }
+    fir_ir_release(c, fr.ir);  // the f32 copies of an impulse response go with its last FIR user (either slot)
+    if (fr.ir_b != fr.ir) fir_ir_release(c, fr.ir_b);
     // The node is gone from the GRAPH; the running plan may hold it until the next plan is adopted.  What it still owns —
     // its slot (the message key), its ext slice, messages queued for it, a sampler's sample — is released AT that adoption
     // (adopt_image) or after it (release_limbo), never from this thread while a process call may be using it.
@@ -974,7 +990,7 @@ int fwgpu_sample_destroy(fwgpu_ctx* c, int sample) {
     // FIR / resampler nodes name their sample at construction and keep it for life: refuse while one exists.  Samplers
     // pick samples by message, which the host does not track: see the contract in fwgpu.h.
     for (const HostNode& n : c->graph.nodes)
-        if (n.alive && (n.kind == K_FIR || n.kind == K_RESAMPLER) && n.init.sample == sample)
+        if ((n.alive && n.kind == K_RESAMPLER && n.init.sample == sample) || fir_uses_sample(n, sample))
             return fail(c, FWGPU_ERR_INVALID, "sample is in use by a FIR / resampler node");
     use_device(c);
     RtHold hold(c);       // the resident realtime kernel ends now, and none is launched until the data is gone
@@ -1024,7 +1040,7 @@ int fwgpu_sample_retired(fwgpu_ctx* c, int sample) {
     use_device(c);
     collect_returns(c);
     for (const HostNode& n : c->graph.nodes)
-        if (n.alive && (n.kind == K_FIR || n.kind == K_RESAMPLER) && n.init.sample == sample) return 0;
+        if ((n.alive && n.kind == K_RESAMPLER && n.init.sample == sample) || fir_uses_sample(n, sample)) return 0;
     return c->sample_refs[sample] == 0 ? 1 : 0;
 }
 int fwgpu_ext_pool_floats(fwgpu_ctx* c, uint64_t* in_use, uint64_t* capacity) {
@@ -1050,6 +1066,80 @@ int fwgpu_crossfade_to(fwgpu_ctx* c, int64_t node, float position, uint32_t fram
     if (!(y1 >= -1.0f && y1 <= 2.0f && y2 >= -1.0f && y2 <= 2.0f))
         return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: y1 and y2 must be in -1..2");
     return push_cmd(c, node, K_CROSSFADE, make_xf_to(at_block, position, frames, shape, x1, y1, x2, y2), false);
+}
+// SPEC FIR morph: one CMD_XF_TO for a morph-capable FirReverbNode, with fwgpu_crossfade_to's refusals.  The host keeps
+// the last morph's target and end (HostNode::fir_target, fir_target_end) — what fwgpu_fir_set_ir asks before it exchanges a slot
+int fwgpu_fir_morph(fwgpu_ctx* c, int64_t node, float position, uint32_t frames, int shape, float x1, float y1, float x2, float y2,
+                    uint32_t at_block) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    HostNode* n = c->graph.get(node);
+    if (!n) return fail(c, FWGPU_ERR_INVALID, "unknown node id");
+    if (n->kind != K_FIR || !n->fir_morph) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: the node is not a morph-capable FirReverbNode");
+    if (!(position >= 0.0f && position <= 1.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: position must be in 0..1");
+    if (frames > XF_FRAMES_MAX) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: at most 2^24 frames");
+    if (shape != XF_SHAPE_LINEAR && shape != XF_SHAPE_BEZIER) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: shape must be 0 (linear) or 1 (Bezier)");
+    if (!(x1 >= 0.0f && x1 <= 1.0f && x2 >= 0.0f && x2 <= 1.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: x1 and x2 must be in 0..1");
+    if (!(y1 >= -1.0f && y1 <= 2.0f && y2 >= -1.0f && y2 <= 2.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: y1 and y2 must be in -1..2");
+    Cmd m = make_xf_to(at_block, position, frames, shape, x1, y1, x2, y2);
+    int rc;
+    // held: the message waits in early_msgs — for the plan that activates the node, or for the one that holds a fwgpu_fir_set_ir — and
+    // starts only behind the update that releases it; process calls on the old plan may render any number of frames before that, so
+    // the book is written at the release (fwgpu_plan_install.cpp publish), and until then both slots count as audible
+    const bool held = !n->activated || n->fir_hold;
+    if (n->activated && n->fir_hold) {  // a fwgpu_fir_set_ir waits for its plan: held like a message for a node that is not activated yet
+        m.state = (int)(node & 0xffffffff);
+        if (c->early_msgs.size() >= fwgpu_ctx::RING_CAP) return fail(c, FWGPU_ERR_QUEUE_FULL, "too many held messages");
+        c->early_msgs.push_back(m);
+        rc = 0;
+    } else {
+        rc = push_cmd(c, node, K_FIR, m, false);
+    }
+    if (rc == 0) {
+        if (held) n->fir_held++;
+        else fir_note_morph(*n, position, c->frames_ctl.load(std::memory_order_acquire) + (uint64_t)at_block * c->mbf, frames);
+    }
+    return rc;
+}
+// SPEC FIR morph: exchange the impulse response of a slot nobody hears — a graph edit, adopted with the plan the next update builds
+int fwgpu_fir_set_ir(fwgpu_ctx* c, int64_t node, int slot, int sample) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    HostNode* n = c->graph.get(node);
+    if (!n) return fail(c, FWGPU_ERR_INVALID, "unknown node id");
+    if (n->kind != K_FIR || !n->fir_morph) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_set_ir: the node is not a morph-capable FirReverbNode");
+    if (slot != 0 && slot != 1) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_set_ir: slot must be 0 (A) or 1 (B)");
+    if (sample == -1 && slot == 0) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_set_ir: slot A cannot be emptied (its rows append the history)");
+    if (sample != -1) {
+        if (sample < 0 || sample >= (int)c->samples.size() || !c->samples[sample].alive || c->samples[sample].desc.frames == 0)
+            return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_set_ir: sample must be -1 or the id of a non-empty impulse-response sample");
+        if (c->samples[sample].stream >= 0) return fail(c, FWGPU_ERR_INVALID, "a stream cannot be an impulse response or a resampler's source");
+        const uint64_t cap = n->activated ? n->init.loop_start : (n->fir_max_taps ? n->fir_max_taps : (1u << 24));
+        if (c->samples[sample].desc.frames > cap) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_set_ir: the sample is longer than the node's tap capacity");
+    }
+    // inaudible: no morph waits to be released, the last morph queued (or the creation position) targets exactly the other slot's end,
+    // and its last frame lies behind the frames of every process call started so far (the edit is adopted by a later call's plan)
+    const float other_end = slot == 0 ? 1.0f : 0.0f;
+    if (n->fir_held || n->fir_target != other_end || n->fir_target_end > c->frames_ctl.load(std::memory_order_acquire))
+        return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_set_ir: the slot is audible (morph to the other slot's end and render the fade first)");
+    const int old = n->fir_ir[slot];
+    if (old == sample) return 0;
+    n->fir_ir[slot] = sample;
+    if (!n->activated && slot == 0) n->init.sample = sample;
+    if (n->activated) n->fir_hold = true;
+    c->graph.needs_compile = true;
+    if (old != n->fir_ir[slot ^ 1]) fir_ir_release(c, old);
+    return 0;
+}
+int fwgpu_fir_morph_stats(fwgpu_ctx* c, uint64_t* tiles_run, uint64_t* tiles_skipped) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    unsigned long long h[2] = {0ull, 0ull};
+    if (c->d_fir_stats.p) {
+        use_device(c);
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(h, c->d_fir_stats.p, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, FWGPU_ERR_DEVICE, "fwgpu_fir_morph_stats: reading the counters failed");
+    }
+    if (tiles_run) *tiles_run = (uint64_t)h[0];
+    if (tiles_skipped) *tiles_skipped = (uint64_t)h[1];
+    return 0;
 }
 // SPEC resampler ratio glide: one CMD_RS_GLIDE to param 1's resampler_step of the ratio; frames == 0 is param 1's
 // message, a step.  Any ratio but a NaN, at most 2^24 frames

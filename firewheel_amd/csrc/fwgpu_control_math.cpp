@@ -191,6 +191,21 @@ NodeState make_state(int kind, const float* params, int n_params, uint32_t sampl
             break;
         case K_FIR:
             s.sample = (int)p(0, -1.0f);  // impulse-response sample id; T and the ring are set at activation
+            if (n_params >= 2) {  // SPEC FIR morph (fwgpu_types.h fir_morph_*): ir_a, ir_b, max_taps, position, law
+                const float irb = p(1, -1.0f), taps = p(2, 0.0f), pos = p(3, 0.0f), law = p(4, (float)XF_LAW_EQUAL_POWER);
+                // anything else — NaN, out of range, a fraction, another law — sets s0.status, and the node fails activation at the next update
+                const bool ok = irb >= -1.0f && irb <= 16777216.0f && irb == floorf(irb) && taps >= 0.0f && taps <= 16777216.0f && taps == floorf(taps) &&
+                                pos >= 0.0f && pos <= 1.0f && (law == (float)XF_LAW_LINEAR || law == (float)XF_LAW_EQUAL_POWER);
+                memset(&s.s0, 0, sizeof(s.s0));  // node time 0, t0 0
+                memset(&s.s1, 0, sizeof(s.s1));
+                s.enabled = 1;
+                s.s0.status = ok ? 0 : 1;
+                s.s1.status = ok ? (int)irb : -1;                   // (the host's bookkeeping takes these two over: HostNode::fir_ir, fir_max_taps)
+                s.s1.a = fw_float_of(ok ? (uint32_t)taps : 0u);
+                s.p0 = s.p1 = ok ? pos : 0.0f;  // at rest at `position`: dur (full_range) 0
+                s.playing = ok ? (int)law : XF_LAW_EQUAL_POWER;
+                s.has_loop = XF_SHAPE_LINEAR;
+            }
             break;
         case K_RESAMPLER:  // params: sample id, ratio, loop, playing
             s.sample = (int)p(0, -1.0f);

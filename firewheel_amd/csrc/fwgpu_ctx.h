@@ -232,6 +232,7 @@ struct PlanImage {
     struct FirGroup {  // one GEMM launch: every FIR row of a level with the same tap count
         int level, row_off, n_rows, tile_off;
         uint32_t T;
+        int morph = 0;  // a group of morph-capable nodes (A and B rows; n_rows partner indices behind its n_rows / 32 tile offsets)
     };
     std::vector<FirGroup> fir_groups;
     DevBuf d_fir_rows, d_fir_tiles, d_fir_partials;
@@ -421,6 +422,9 @@ struct fwgpu_ctx : fwgpu::PlanImage {
     // flight (an upper bound: a message for block b starts no later than b whole blocks into its call); bq_sweep_live: the call being
     // rendered may meet a sweep — no lazy call, no batch walkers (k_level<1> renders the sweep's blocks), k_chain's sweep instantiation
     uint64_t frames_done = 0, bq_sweep_until = 0;
+    // frames_ctl: the control side's view of frames_done — stored by a process call BEFORE it drains the ring, as the count behind that
+    // call: a message pushed after the store is applied no earlier than that frame (fwgpu_fir_morph keeps a morph's end by it)
+    std::atomic<uint64_t> frames_ctl{0};
     bool bq_sweep_live = false;
     // the same for spatialiser moves (CMD_SP_MOVE): sp_move_live — the call being rendered may meet a move: no lazy call, no captured
     // graph, and the node / control kernels' move instantiations (k_level<1, true>, k_voice_control_spm); a call that cannot meet one
@@ -453,8 +457,9 @@ struct fwgpu_ctx : fwgpu::PlanImage {
     bool ahead_this_call = false;    // the process call in progress runs in ahead mode
     bool cmds_on_ctl = false;        // ... and its message upload goes to the control stream
 
-    std::map<std::pair<int, int>, uint32_t> ir_cache;  // (sample id, channel) -> ext offset of h[T] as f32
-    std::map<std::pair<int, int>, uint32_t> ir_len;    // ... and its length in floats (freed with the last FIR user)
+    typedef std::tuple<int, int, uint32_t> IrKey;  // (sample id, channel, length T the copy is zero-padded to)
+    std::map<IrKey, uint32_t> ir_cache;            // -> ext offset of h[T] as f32 (freed with the sample's last FIR user, either slot)
+    DevBuf d_fir_stats;                            // two 64-bit counters: fwgpu_fir_morph_stats
     std::map<size_t, std::vector<uint32_t>> ext_free;  // ext slices of removed nodes, by 64-rounded size (floats)
 
     // host nodes: the control side's registry of process functions (by node slot); an image gets copies

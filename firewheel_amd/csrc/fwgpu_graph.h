@@ -38,7 +38,31 @@ struct HostNode {
     int pending_msgs = 0;
     uint64_t pending_epoch = 0;
     int stream = -1;  // a sampler whose sample, as last sent, is a stream (SPEC streaming source): its index in fwgpu_ctx::streams
+    // a morph-capable FirReverbNode (SPEC FIR morph), control side: the slots' samples as the GRAPH has them (-1: an
+    // empty slot B; the next plan build reads them), the max_taps parameter, the morph book (fir_note_morph below) and whether a
+    // fwgpu_fir_set_ir waits for a plan build (morph messages are held until then)
+    bool fir_morph = false;
+    int fir_ir[2] = {-1, -1};
+    uint32_t fir_max_taps = 0;
+    float fir_target = 0.0f;      // the target of the morph that is applied LAST among those sent (the greatest start; ties: the later one)
+    uint64_t fir_last_start = 0;  // ... that morph's first frame, in the ctx's count of frames (an upper bound)
+    uint64_t fir_target_end = 0;  // the first frame behind every morph sent so far (an upper bound)
+    uint32_t fir_held = 0;        // morphs that wait in early_msgs: when they start is not known before they are released — both slots count as audible
+    bool fir_hold = false;
 };
+// The morph book of a morph-capable FirReverbNode: a morph that starts no later than `start` (frames of the ctx's count) and lasts
+// `frames`.  Messages apply in (block, send) order, so the target that stands in the end is that of the greatest start
+inline void fir_note_morph(HostNode& n, float position, uint64_t start, uint32_t frames) {
+    if (start >= n.fir_last_start) {
+        n.fir_last_start = start;
+        n.fir_target = position;
+    }
+    if (start + frames > n.fir_target_end) n.fir_target_end = start + frames;
+}
+// does a FIR node use this sample, in either slot?
+inline bool fir_uses_sample(const HostNode& n, int sample) {
+    return n.alive && n.kind == K_FIR && (n.fir_morph ? n.fir_ir[0] == sample || n.fir_ir[1] == sample : n.init.sample == sample);
+}
 
 inline int64_t make_id(uint32_t slot, uint32_t gen) { return (int64_t(gen) << 32) | int64_t(slot); }
 

@@ -138,6 +138,17 @@ int launch_fir(hipStream_t s, const DevView& v, const FirRow* d_rows, int n_rows
     const int row_tiles = (n_rows + 31) / 32, n_rows_pad = row_tiles * 32;
     const int col_groups = (v.frames + 255) / 256, n_pad = col_groups * 256;
     if ((size_t)n_segs * n_rows_pad * n_pad * K > partial_cap_floats) return (int)hipErrorInvalidValue;
+    if (v.fir_morph) {  // a morph group (DevView::fir_morph): the control step, then the morph instantiations; the partner indices sit behind the tile offsets
+        hipLaunchKernelGGL(k_fir_morph_control, dim3((n_rows + 63) / 64), dim3(64), 0, s, v, d_rows, n_rows, (uint32_t)K);
+        hipLaunchKernelGGL(k_fir_append_morph, dim3(n_rows, K), dim3(256), 0, s, v, d_rows, n_rows);
+        if (gemm_begin) (void)hipEventRecord(gemm_begin, s);
+        hipLaunchKernelGGL(k_fir_gemm_morph, dim3(row_tiles, n_segs, col_groups * K), dim3(256), 0, s, v, d_rows, n_rows, d_tile_h_off, T,
+                           d_partials, n_rows_pad, n_pad, col_groups);
+        if (gemm_end) (void)hipEventRecord(gemm_end, s);
+        hipLaunchKernelGGL(k_fir_reduce_morph, dim3(n_rows, K), dim3(256), 0, s, v, d_rows, n_rows, d_tile_h_off + row_tiles, d_partials, n_segs,
+                           n_rows_pad, n_pad);
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(k_fir_append, dim3(n_rows, K), dim3(256), 0, s, v, d_rows, n_rows);
     if (gemm_begin) (void)hipEventRecord(gemm_begin, s);
     hipLaunchKernelGGL(k_fir_gemm, dim3(row_tiles, n_segs, col_groups * K), dim3(256), 0, s, v, d_rows, n_rows, d_tile_h_off, T,

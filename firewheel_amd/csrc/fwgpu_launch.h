@@ -35,6 +35,11 @@ struct DevView {
     // wave that rendered a downstream node's block in registers, read by that node's own wave a level later.  nullptr: no fusion.
     uint32_t* chain_done = nullptr;  // (initialised here: the upper-tree / master-chain / realtime views are filled field by field)
     int chain_words = 0;
+    // launch_fir's view only (it sits in the padding behind chain_words: the view, a kernel argument, keeps its size).  0: a group of
+    // plain FIR nodes.  FIR_MORPH_GROUP | b: a group of morph-capable nodes (SPEC FIR morph, fwgpu_types.h fir_morph_*) — launch_fir
+    // runs the control step and the morph instantiations; b = the batch's first block in the call's message list (cmds); and in such
+    // a view chain_done, which no FIR kernel has a use for, points at the two 64-bit counters of fwgpu_fir_morph_stats (or is nullptr)
+    uint32_t fir_morph = 0;
     // level meters (K_METER): the ctx's block count at block 0 of this launch and the launch's block count — block b writes its
     // records to ring slot (meter_blk0 + b) % R, and only if meter_K - b <= R (a launch longer than the ring keeps its last R
     // blocks: two waves never meet in a slot).  meter_K = 0: nothing is recorded (fwgpu_node_process).
@@ -49,6 +54,7 @@ struct DevView {
     // k_level<0, false, true>; fwgpu_node_process sets it for these two kinds (k_single_node<false, true>)
     int gain_rides = 0;
 };
+static_assert(sizeof(DevView) == 168, "DevView: a kernel that passes its view on by reference keeps a copy in scratch — a new field goes into padding");
 
 // The compact records are tiled: 32 voices x 8 blocks per 4 KiB tile, [voice % 32][block % 8].  A voice's 8 consecutive blocks
 // are one 128-B line — what its control wave stores (full lines) and what k_chain walks — and the 32 records a leaf wave

@@ -512,7 +512,7 @@ struct ImageBuild {
     // step 2: the nodes this image activates
     std::vector<StateInitHost> inits;                // per new node: slot, init record with its ext slice / FIR ring geometry filled in
     std::vector<AdoptExtJobHost> ext_jobs;           // per new node with an ext slice: recycled slices zeroed, head floats (coefficients) set
-    std::map<std::pair<int, int>, uint32_t> new_ir;  // impulse responses to convert to f32 -> ext offset
+    std::map<fwgpu_ctx::IrKey, uint32_t> new_ir;     // impulse responses to convert to f32, zero-padded to the key's length -> ext offset
     size_t ext_need;
     // the launch plan
     FusedBuild fb, hb;
@@ -553,7 +553,7 @@ struct ImageBuild {
             if ((uint32_t)si.index == slot) return si.st;
         return c->graph.nodes[slot].init;
     }
-    uint32_t ir_off(const std::pair<int, int>& key) const {
+    uint32_t ir_off(const fwgpu_ctx::IrKey& key) const {
         auto it = new_ir.find(key);
         return it != new_ir.end() ? it->second : c->ir_cache[key];
     }
@@ -594,6 +594,7 @@ static int activate_nodes(ImageBuild& b) {
         size_t len = 0;
         std::vector<float> head;
         uint32_t head_pad = 0;  // floats at the slice's start that `head` fills whole, eight to a job: the zeroing job starts behind them
+        uint64_t fir_R = 0;     // a morph-capable FIR node: its ring length, for the place of its block records in the slice
         if (n.kind == K_BIQUAD) {
             len = 5 + 4 * (size_t)nch + BQ_SNAP_LEN;  // (behind the channels' state: a sweep as the chain plan's call found it)
             head.resize(5);
@@ -642,14 +643,36 @@ static int activate_nodes(ImageBuild& b) {
                 return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "FIR node: impulse-response sample was destroyed");
             uint64_t T = c->samples[ir].desc.frames;
             if (T == 0 || T > (1u << 24)) return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "FIR node: 1 <= taps <= 2^24");
+            if (n.fir_morph) {  // SPEC FIR morph: the creation parameters are refused here, as a crossfader's are; T is the tap capacity
+                if (n.init.s0.status != 0)
+                    return fail(c, FWGPU_ERR_INVALID, "FirReverbNode: max_taps must be a whole number in 0..2^24, position in 0..1, law 0 (linear) or 1 (equal power)");
+                for (int slot = 0; slot < 2; ++slot) {
+                    const int id = n.fir_ir[slot];
+                    if (slot == 1 && id == -1) continue;  // an empty slot B
+                    if (id < 0 || id >= (int)c->samples.size() || !c->samples[id].alive || c->samples[id].desc.frames == 0 || c->samples[id].stream >= 0 ||
+                        c->samples[id].desc.frames > (1u << 24))
+                        return fail(c, FWGPU_ERR_INVALID, "FirReverbNode: ir_b must be -1 or the id of a non-empty impulse-response sample of at most 2^24 frames");
+                    T = slot == 0 ? c->samples[id].desc.frames : std::max<uint64_t>(T, c->samples[id].desc.frames);
+                }
+                if (n.fir_max_taps) {
+                    if (n.fir_max_taps < T) return fail(c, FWGPU_ERR_INVALID, "FirReverbNode: max_taps is shorter than an impulse response");
+                    T = n.fir_max_taps;
+                }
+            }
             uint64_t R = T - 1 + (uint64_t)P.kmax * c->mbf;  // every block of a K-batch finds its whole window in the ring
             si.st.loop_start = T;
             si.st.loop_end = R;
             si.st.playhead = 0;
             len = (size_t)nch * 2 * (size_t)R;
-            for (uint32_t ch = 0; ch < nch; ++ch) {
-                auto key = std::make_pair(ir, (int)std::min<uint32_t>(ch, (uint32_t)c->samples[ir].desc.channels - 1));
-                if (!c->ir_cache.count(key)) b.new_ir.emplace(key, 0u);  // offset assigned below, once the pool layout is final
+            if (n.fir_morph) {
+                fir_R = R;
+                len = (size_t)fir_morph_ext_len(R, nch, P.kmax);
+                if (nch == 0 || len > 0xffffffffull) return fail(c, FWGPU_ERR_INVALID, "ext state pool exceeds 2^32 floats");
+            } else {
+                for (uint32_t ch = 0; ch < nch; ++ch) {
+                    fwgpu_ctx::IrKey key(ir, (int)std::min<uint32_t>(ch, (uint32_t)c->samples[ir].desc.channels - 1), (uint32_t)T);
+                    if (!c->ir_cache.count(key)) b.new_ir.emplace(key, 0u);  // offset assigned below, once the pool layout is final
+                }
             }
         }
         if (len) {
@@ -658,6 +681,12 @@ static int activate_nodes(ImageBuild& b) {
             if (!b.take_ext(len, &off)) return fail(c, FWGPU_ERR_INVALID, "ext state pool exceeds 2^32 floats");
             si.st.ext_off = off;
             si.st.ext_len = (uint32_t)len;
+            if (fir_R) {  // the block records behind the rings; the host's copies of ir_b / max_taps (s1.status, s1.a) have done their work
+                memset(&si.st.s1, 0, sizeof(si.st.s1));
+                si.st.s1.input = fw_float_of(off + fir_morph_tab_rel(fir_R, nch));
+                si.st.s1.last = fw_float_of(P.kmax);
+                if (!fir_morph_state_ok(si.st, (int)n.n_in, (int)n.n_out)) return fail(c, FWGPU_ERR_INVALID, "FirReverbNode: not a state the morph kernels render");
+            }
             AdoptExtJobHost j{};
             j.off = off + head_pad;
             j.zero_len = b.ext_need == before ? (uint32_t)((len + 63) / 64 * 64) - head_pad : 0u;  // (a bumped slice is zero already)
@@ -675,12 +704,31 @@ static int activate_nodes(ImageBuild& b) {
         }
         b.inits.push_back(si);
     }
+    // morph-capable FIR nodes: both slots' copies, padded to the node's T — for the nodes this build activates and for the ones whose
+    // slot a fwgpu_fir_set_ir has changed since the last build (the copy is cached per (sample, channel, padded length))
+    for (uint32_t slot = 0; slot < (uint32_t)c->graph.nodes.size(); ++slot) {
+        const HostNode& n = c->graph.nodes[slot];
+        if (!n.alive || n.kind != K_FIR || !n.fir_morph) continue;
+        const NodeState st = b.node_init(slot);
+        if (!fir_morph_on(st) || st.loop_end == 0) continue;  // (not activated, and not by this build either)
+        const uint32_t nch = n.n_in < n.n_out ? n.n_in : n.n_out;
+        for (int sl = 0; sl < 2; ++sl) {
+            const int id = n.fir_ir[sl];
+            if (id < 0) continue;
+            if (id >= (int)c->samples.size() || !c->samples[id].alive || c->samples[id].desc.frames == 0 || c->samples[id].desc.frames > st.loop_start)
+                return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "FIR node: impulse-response sample was destroyed");
+            for (uint32_t ch = 0; ch < nch; ++ch) {
+                fwgpu_ctx::IrKey key(id, (int)std::min<uint32_t>(ch, (uint32_t)c->samples[id].desc.channels - 1), (uint32_t)st.loop_start);
+                if (!c->ir_cache.count(key)) b.new_ir.emplace(key, 0u);
+            }
+        }
+    }
     for (auto& kv : b.new_ir) {  // one f32 copy of each impulse-response channel
-        uint64_t T = c->samples[kv.first.first].desc.frames;
+        uint64_t T = std::get<2>(kv.first);
         if (b.ext_need + (T + 63) / 64 * 64 > 0xffffffffull) return fail(c, FWGPU_ERR_INVALID, "ext state pool exceeds 2^32 floats");
         kv.second = (uint32_t)b.ext_need;
         b.ext_need += (T + 63) / 64 * 64;
-        P.ir_convs.push_back({kv.first.first, kv.first.second, kv.second, (uint32_t)T});
+        P.ir_convs.push_back({std::get<0>(kv.first), std::get<1>(kv.first), kv.second, (uint32_t)T});
     }
     int rc;
     if (b.ext_need > c->ctl_ext_cap) {
@@ -863,49 +911,81 @@ static int plan_host_nodes(ImageBuild& b) {
     P.host_out_ptrs.assign(max_out, nullptr);
     return 0;
 }
-// 3b. FIR banks: one GEMM per (level, impulse-response channel)
+// 3b. FIR banks: one GEMM per (level, T, morph) — morph-capable nodes (SPEC FIR morph) form groups of their own, so the groups of plain
+//     nodes are what they were
 static int plan_fir_banks(ImageBuild& b) {
     fwgpu_ctx* c = b.c; PlanImage& P = b.P;
-    std::map<std::tuple<int, uint32_t, uint32_t>, std::vector<FirRow>> groups;
+    struct RowTmp {
+        FirRow r;
+        uint32_t h;  // ext offset of the row's impulse-response channel
+        int pair;    // morph: which (node, channel) of the launch the row belongs to
+    };
+    std::map<std::tuple<int, uint32_t, int>, std::vector<RowTmp>> launches;
+    std::map<std::tuple<int, uint32_t, int>, int> n_pairs;
     for (const PlanNode& p : b.plan.nodes) {
         if (p.kind != K_FIR) continue;
         const NodeState hst = b.node_init(p.slot);
-        int ir = hst.sample;
+        const HostNode& hn = c->graph.nodes[p.slot];
         uint32_t T = (uint32_t)hst.loop_start;
         int nch = std::min(p.n_in, p.n_out);
+        const int morph = hn.fir_morph ? 1 : 0;
+        const auto lkey = std::make_tuple(p.level, T, morph);
         for (int ch = 0; ch < nch; ++ch) {
-            auto key = std::make_pair(ir, std::min(ch, c->samples[ir].desc.channels - 1));
-            FirRow r;
-            r.state = (int)p.slot;
-            r.ch = ch;
-            r.in_buf = p.in_buf[ch];
-            r.out_buf = p.out_buf[ch];
-            groups[std::make_tuple(p.level, b.ir_off(key), T)].push_back(r);
+            const int pair = n_pairs[lkey]++;
+            for (int slot = 0; slot <= morph; ++slot) {
+                const int ir = morph ? hn.fir_ir[slot] : hst.sample;
+                if (ir < 0) continue;  // an empty slot B has no row
+                fwgpu_ctx::IrKey key(ir, std::min(ch, c->samples[ir].desc.channels - 1), T);
+                FirRow r;
+                r.state = (int)p.slot;
+                r.ch = ch;
+                r.in_buf = slot ? -1 : p.in_buf[ch];  // (a B row: fwgpu_types.h FirRow)
+                r.out_buf = p.out_buf[ch];
+                launches[lkey].push_back({r, b.ir_off(key), pair});
+            }
         }
     }
-    // one launch per (level, T); inside it rows are sorted by impulse-response channel and padded so that
-    // every 32-row tile convolves with a single h (tile_h_off)
+    // inside a launch rows are sorted by impulse-response channel and padded so that every 32-row tile convolves with a single h
+    // (tile_h_off); a morph group's partner indices follow its tile offsets
     std::vector<FirRow> flat_rows;
     std::vector<uint32_t> flat_tiles;
     size_t partial_need = 0;
-    std::map<std::pair<int, uint32_t>, std::vector<std::pair<uint32_t, std::vector<FirRow>*>>> launches;
-    for (auto& g : groups)
-        launches[std::make_pair(std::get<0>(g.first), std::get<2>(g.first))].emplace_back(std::get<1>(g.first), &g.second);
     for (auto& l : launches) {
+        std::vector<RowTmp>& rows = l.second;
+        std::stable_sort(rows.begin(), rows.end(), [](const RowTmp& x, const RowTmp& y) { return x.h < y.h; });
         PlanImage::FirGroup fg;
-        fg.level = l.first.first;
-        fg.T = l.first.second;
+        fg.level = std::get<0>(l.first);
+        fg.T = std::get<1>(l.first);
+        fg.morph = std::get<2>(l.first);
         fg.row_off = (int)flat_rows.size();
         fg.tile_off = (int)flat_tiles.size();
-        for (auto& part : l.second) {
-            for (const FirRow& r : *part.second) flat_rows.push_back(r);
+        std::vector<uint32_t> where_a((size_t)n_pairs[l.first], FIR_NO_PARTNER), where_b((size_t)n_pairs[l.first], FIR_NO_PARTNER);
+        for (size_t i = 0; i < rows.size();) {
+            const uint32_t h = rows[i].h;
+            for (; i < rows.size() && rows[i].h == h; ++i) {
+                (rows[i].r.in_buf < 0 ? where_b : where_a)[(size_t)rows[i].pair] = (uint32_t)(flat_rows.size() - fg.row_off);
+                flat_rows.push_back(rows[i].r);
+            }
             while ((flat_rows.size() - fg.row_off) % 32) {
                 flat_rows.push_back(FirRow{-1, 0, 0, 0});
             }
-            while (flat_tiles.size() - fg.tile_off < (flat_rows.size() - fg.row_off) / 32) flat_tiles.push_back(part.first);
+            while (flat_tiles.size() - fg.tile_off < (flat_rows.size() - fg.row_off) / 32) flat_tiles.push_back(h);
         }
         fg.n_rows = (int)flat_rows.size() - fg.row_off;
+        if (fg.morph) {
+            std::vector<uint32_t> partner((size_t)fg.n_rows, FIR_NO_PARTNER);
+            for (size_t q = 0; q < where_a.size(); ++q) {
+                if (where_a[q] != FIR_NO_PARTNER) partner[where_a[q]] = where_b[q];
+                if (where_b[q] != FIR_NO_PARTNER) partner[where_b[q]] = where_a[q];
+            }
+            flat_tiles.insert(flat_tiles.end(), partner.begin(), partner.end());
+        }
         P.fir_groups.push_back(fg);
+        if (fg.morph && !c->d_fir_stats.p) {  // fwgpu_fir_morph_stats' two counters: allocated with the first morph group, zero from then on
+            HIPC(c, c->d_fir_stats.ensure_n("d_fir_stats", 2 * sizeof(unsigned long long)));
+            int zrc = zero(c, c->d_fir_stats.p, 2 * sizeof(unsigned long long));
+            if (zrc) return zrc;
+        }
         size_t W = (size_t)fg.T - 1 + c->mbf;
         size_t segs = (W + FIR_SEG - 1) / FIR_SEG;
         partial_need = std::max(partial_need, segs * (size_t)fg.n_rows * (size_t)((c->mbf + 255) / 256 * 256) * P.kmax);
@@ -1179,8 +1259,8 @@ static void commit_bookkeeping(ImageBuild& b) {
     }
     for (auto& kv : b.new_ir) {
         c->ir_cache[kv.first] = kv.second;
-        c->ir_len[kv.first] = (uint32_t)c->samples[kv.first.first].desc.frames;
     }
+    for (HostNode& n : c->graph.nodes) n.fir_hold = false;  // every fwgpu_fir_set_ir so far is in this image: publish releases the held messages
     c->ext_used = b.ext_need;
     if (P.grow_states.p) c->ctl_states_cap = P.grow_states_cap;
     if (P.grow_ext.p) c->ctl_ext_cap = P.grow_ext_cap;
@@ -1421,6 +1501,17 @@ static void publish(fwgpu_ctx* c, PlanImage* img) {
         }
         std::this_thread::yield();  // a process call is running: it (or the next one) takes the pending image at its start
     }
+    // held morphs of morph-capable FIR nodes (fwgpu_fir_morph): they start no earlier than the frames of the calls started so far — the
+    // book fwgpu_fir_set_ir asks is written now, not when they were sent
+    const uint64_t frames_now = c->frames_ctl.load(std::memory_order_acquire);
+    for (const Cmd& m : c->early_msgs)
+        if (m.type == CMD_XF_TO && m.state >= 0 && (size_t)m.state < c->graph.nodes.size()) {
+            HostNode& hn = c->graph.nodes[(size_t)m.state];
+            if (hn.alive && hn.kind == K_FIR && hn.fir_morph && hn.fir_held) {
+                fir_note_morph(hn, m.f0, frames_now + (uint64_t)m.block * c->mbf, (uint32_t)m.i0);
+                hn.fir_held--;
+            }
+        }
     for (const Cmd& m : c->early_msgs) (void)c->ring.push(m);  // messages sent to nodes before the update that activates them
     c->early_msgs.clear();
     if (!try_adopt_from_control(c, img)) c->pending.store(img, std::memory_order_release);

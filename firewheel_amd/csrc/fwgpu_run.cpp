@@ -531,7 +531,12 @@ int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const
                         t.launches++;
                     }
                 }
-                LCHK(c, launch_fir(c->stream, v, c->d_fir_rows.as<FirRow>() + g.row_off, g.n_rows,
+                DevView vf = v;  // (what launch_fir needs to know about a morph group travels in the view)
+                if (g.morph) {
+                    vf.fir_morph = FIR_MORPH_GROUP | cmd_block;
+                    vf.chain_done = c->d_fir_stats.as<uint32_t>();
+                }
+                LCHK(c, launch_fir(c->stream, vf, c->d_fir_rows.as<FirRow>() + g.row_off, g.n_rows,
                                    c->d_fir_tiles.as<uint32_t>() + g.tile_off, g.T, c->d_fir_partials.as<float>(),
                                    c->d_fir_partials.cap / sizeof(float), K, g0, g1));
             }
@@ -881,6 +886,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     // FWGPU_CTL_AHEAD=2, the default) only a call that has something to hide: a message on the list, or voices the call before
     // sent messages to (their glides continue).  A message-free call's control kernel is ~8 us of steady tails; beside the render
     // kernel of the call before it cost that kernel 7-15 us of co-residency and the step a ~10 us cross-stream event.
+    c->frames_ctl.store(c->frames_done + frames, std::memory_order_release);
     drain_ring(c);
     note_bq_sweeps(c);
     note_sp_moves(c);

@@ -1,5 +1,6 @@
 // fwgpu_types.h — POD structs shared by the host planner and the HIP kernels (HBM-resident layout).
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 namespace fwgpu {
@@ -163,7 +164,8 @@ struct NodeState {
     //        it stood at the START of the chain plan's current call (k_voice_control writes it, k_chain's sweep instantiation reads it)
     //   DELAY also uses p0 = feedback, p1 = mix, gain = dry (1-mix), playhead = ring position, loop_end = D
     //   FIR: ext = mirrored history ring[channels][2R]; playhead = ring position, loop_end = R, loop_start = T,
-    //        sample = impulse-response sample id
+    //        sample = impulse-response sample id (a morph-capable node: of slot A at activation; enabled = 1 and the fields listed
+    //        at fir_morph_* below hold its segment, node time and block records)
     //   SAMPLER also keeps its gain envelope (CMD_SMP_FADE) in fields it has no other use for: phasor = E0, gain = E1,
     //        enabled = N in bits 0..24 and `then` (SMP_FADE_*) in bits 28..29, s1.status = k (frames of the fade rendered, k < N).
     //        At rest: enabled == 0 and s1.status == 0, the value is E1 = gain.  make_state leaves a new sampler at rest at 1.0f; no
@@ -839,6 +841,42 @@ FW_TYPES_HD inline bool xf_state_ok(const NodeState& s, int n_in, int n_out) {
            (s.playing == XF_LAW_LINEAR || s.playing == XF_LAW_EQUAL_POWER) && unit(s.phasor) && unit(s.gain) && ctl_y(s.phasor_inc) &&
            ctl_y(s.aux) && s.playhead >= s.loop_start;
 }
+// The crossfader's position rule (SPEC): ONE statement for the crossfader's message and render case (k_common.hip.h,
+// k_generic.hip.h), the FIR morph (fir_morph_* below) and a host build.  The segment as the rule reads it:
+struct XfSeg {
+    float P0, P1, x1, y1, x2, y2;
+    uint64_t t0;
+    uint32_t dur;
+    int shape;
+};
+FW_TYPES_HD_INLINE XfSeg xf_seg(const NodeState& s) {
+    return XfSeg{s.p0, s.p1, s.phasor, s.phasor_inc, s.gain, s.aux, s.loop_start, (uint32_t)s.full_range, s.has_loop};
+}
+// the positions of frames n .. n + W - 1 (node time) under the segment.  The solver — XF_ITERS bisection steps on x(t) = u, then
+// y(t) — runs on the W frames at once, its loop rolled: the same trip count for every frame, nothing indexed by a variable
+template <int W>
+FW_TYPES_HD_INLINE void xf_positions(const XfSeg& g, uint64_t n, float (&p)[W]) {
+    const uint32_t dur = g.dur;
+    const uint64_t k0 = n - g.t0;
+    FW_TYPES_UNROLL
+    for (int e = 0; e < W; ++e) p[e] = g.P1;
+    if (dur == 0u || k0 >= (uint64_t)dur) return;
+    const float fdur = (float)dur;  // (exact: dur <= 2^24; so is every k < dur)
+    float u[W], y[W];
+    FW_TYPES_UNROLL
+    for (int e = 0; e < W; ++e) u[e] = (float)((uint32_t)k0 + (uint32_t)e) / fdur;
+    fw_curve_y<W>(g.shape, g.x1, g.y1, g.x2, g.y2, u, y);
+    const float span = g.P1 - g.P0;
+    FW_TYPES_UNROLL
+    for (int e = 0; e < W; ++e)
+        if (k0 + (uint64_t)e < (uint64_t)dur)  // (the segment may end among the W frames)
+            p[e] = fminf(fmaxf(g.P0 + (span * y[e]), 0.0f), 1.0f);  // an overshooting curve is allowed; the position is clamped
+}
+FW_TYPES_HD_INLINE void xf_gains(int law, float p, float& a, float& b) {
+    const float q = 1.0f - p;
+    a = law == XF_LAW_LINEAR ? q : sqrtf(q);
+    b = law == XF_LAW_LINEAR ? p : sqrtf(p);
+}
 
 struct SampleDesc {  // core/sample_resource.rs:4-26; data is HBM-resident
     const void* data;
@@ -1305,6 +1343,112 @@ struct FirRow {  // one GEMM row = one channel of one FIR node
     int in_buf;
     int out_buf;
 };
+// K_FIR, morph-capable (SPEC FIR morph): a FIR node created with two or more parameters has two impulse-response slots
+// A and B of T taps each (a shorter impulse response is zero-padded to T) over ONE history ring per channel.  The slot sums s_A[n],
+// s_B[n] are the plain FIR definition above (segments of FIR_SEG, fma chains from +0.0, partials added in order, + (+0.0f)); an empty
+// slot's sum is +0.0.  The position p of frame n follows the crossfader's rule (XfSeg, xf_positions: node time = frames rendered since
+// activation, a message retargets from where the old segment stands), the gains its laws (xf_gains), and
+//     y[n] = s_A[n] if p == 0,  s_B[n] if p == 1,  else (s_A[n] * a) + (s_B[n] * b)      (three separately rounded operations)
+// A block is at rest when dur == 0 or the segment has ended at its first frame; at rest at p == 0 slot B is idle for the block (no
+// matrix work), at rest at p == 1 slot A is, in every other block both slots run.
+// State, in NodeState fields a plain FIR node leaves at make_state's values (playhead, loop_start, loop_end, sample, ext_off, ext_len
+// mean what they mean for every FIR node; the ext slice is the rings, then — 16-float aligned — one FirMorphBlk per block of a batch):
+//     enabled = 1 (0: a plain node), s0.status = 0 (1: a creation parameter was refused), p0 / p1 = P0 / P1, full_range = dur,
+//     has_loop = shape, phasor, phasor_inc, gain, aux = x1, y1, x2, y2, playing = law, s0.input | s0.last << 32 = node time (raw bits),
+//     s0.a | s0.b << 32 = t0, s1.input = ext offset of the block records, s1.last = how many there are (raw bits);
+//     s1.status / s1.a carry the creation parameters ir_b / max_taps to the host's bookkeeping (no kernel reads them)
+// Rows (FirRow) of a morph group: an A row is a plain row; a B row names the same state and ch, in_buf = -1 (that is what marks it)
+// and its node's out_buf.  Behind the group's n_rows / 32 tile offsets sit n_rows partner indices: row r's other slot's row in the
+// group, FIR_NO_PARTNER for none.
+#define FIR_MORPH_BLK_FLOATS 16
+#define FIR_NO_PARTNER 0xffffffffu
+#define FIR_MORPH_GROUP 0x80000000u  // DevView::fir_morph: the flag; the bits below it are the batch's first block
+enum : int { FIR_MODE_NONE = 0, FIR_MODE_A = 1, FIR_MODE_B = 2, FIR_MODE_BOTH = 3 };  // bit 0: slot A runs, bit 1: slot B runs
+struct FirMorphBlk {  // what k_fir_morph_control leaves per block of the batch: the segment in force at the block's first frame
+    float P0, P1, x1, y1, x2, y2;
+    uint32_t t0_lo, t0_hi, dur;
+    int shape;
+    uint32_t T_lo, T_hi;  // node time of the block's first frame
+    int mode, law;
+    uint32_t pad[2];
+};
+static_assert(sizeof(FirMorphBlk) == FIR_MORPH_BLK_FLOATS * sizeof(float), "FirMorphBlk layout");
+FW_TYPES_HD inline bool fir_morph_on(const NodeState& s) { return s.enabled == 1; }
+FW_TYPES_HD inline uint64_t fir_morph_time(const NodeState& s) { return (uint64_t)fw_bits_of(s.s0.input) | ((uint64_t)fw_bits_of(s.s0.last) << 32); }
+FW_TYPES_HD inline void fir_morph_set_time(NodeState& s, uint64_t t) {
+    s.s0.input = fw_float_of((uint32_t)t);
+    s.s0.last = fw_float_of((uint32_t)(t >> 32));
+}
+FW_TYPES_HD inline uint64_t fir_morph_t0(const NodeState& s) { return (uint64_t)fw_bits_of(s.s0.a) | ((uint64_t)fw_bits_of(s.s0.b) << 32); }
+FW_TYPES_HD inline uint32_t fir_morph_tab(const NodeState& s) { return fw_bits_of(s.s1.input); }
+FW_TYPES_HD inline uint32_t fir_morph_tab_n(const NodeState& s) { return fw_bits_of(s.s1.last); }
+FW_TYPES_HD inline XfSeg fir_morph_seg(const NodeState& s) {
+    return XfSeg{s.p0, s.p1, s.phasor, s.phasor_inc, s.gain, s.aux, fir_morph_t0(s), (uint32_t)s.full_range, s.has_loop};
+}
+FW_TYPES_HD inline XfSeg fir_morph_seg(const FirMorphBlk& b) {
+    return XfSeg{b.P0, b.P1, b.x1, b.y1, b.x2, b.y2, (uint64_t)b.t0_lo | ((uint64_t)b.t0_hi << 32), b.dur, b.shape};
+}
+// where the rings end and the block records begin, and the whole slice, in floats (nch rings of 2R, `n_blk` records)
+FW_TYPES_HD inline uint32_t fir_morph_tab_rel(uint64_t R, uint32_t nch) { return (uint32_t)(((uint64_t)nch * 2u * R + 15u) / 16u * 16u); }
+FW_TYPES_HD inline uint64_t fir_morph_ext_len(uint64_t R, uint32_t nch, uint32_t n_blk) {
+    return (uint64_t)fir_morph_tab_rel(R, nch) + (uint64_t)n_blk * FIR_MORPH_BLK_FLOATS;
+}
+// the states the morph kernels render (anything else would index the ext pool out of bounds): ONE statement for the plan build, the
+// device guard of k_fir_morph_control and a host build
+FW_TYPES_HD inline bool fir_morph_state_ok(const NodeState& s, int n_in, int n_out) {
+    const auto unit = [](float x) { return x >= 0.0f && x <= 1.0f; };  // (false for a NaN)
+    const auto ctl_y = [](float y) { return y >= -1.0f && y <= 2.0f; };
+    const int nch = n_in < n_out ? n_in : n_out;
+    const uint64_t T = s.loop_start, R = s.loop_end;
+    if (!(s.enabled == 1 && s.s0.status == 0 && nch >= 1 && T >= 1 && T <= (1u << 24) && R >= T && s.playhead < R)) return false;
+    if (!(unit(s.p0) && unit(s.p1) && s.full_range >= 0 && (uint32_t)s.full_range <= XF_FRAMES_MAX &&
+          (s.has_loop == XF_SHAPE_LINEAR || s.has_loop == XF_SHAPE_BEZIER) && (s.playing == XF_LAW_LINEAR || s.playing == XF_LAW_EQUAL_POWER) &&
+          unit(s.phasor) && unit(s.gain) && ctl_y(s.phasor_inc) && ctl_y(s.aux) && fir_morph_time(s) >= fir_morph_t0(s)))
+        return false;
+    const uint64_t tab = fir_morph_tab(s), n_blk = fir_morph_tab_n(s);
+    return n_blk >= 1 && tab % 16u == 0 && tab >= (uint64_t)s.ext_off + (uint64_t)nch * 2u * R &&
+           tab + n_blk * FIR_MORPH_BLK_FLOATS <= (uint64_t)s.ext_off + (uint64_t)s.ext_len;
+}
+// CMD_XF_TO at a block's first frame: a new segment from where the old one stands (the crossfader's retarget rule)
+FW_TYPES_HD inline void fir_morph_msg(NodeState& s, float P1, uint32_t frames, int shape, float x1, float y1, float x2, float y2) {
+    float from[1];
+    const uint64_t T = fir_morph_time(s);
+    xf_positions<1>(fir_morph_seg(s), T, from);
+    s.p0 = from[0];
+    s.p1 = P1;
+    s.s0.a = fw_float_of((uint32_t)T);
+    s.s0.b = fw_float_of((uint32_t)(T >> 32));
+    s.full_range = (int)frames;
+    s.has_loop = shape;
+    s.phasor = x1;
+    s.phasor_inc = y1;
+    s.gain = x2;
+    s.aux = y2;
+}
+FW_TYPES_HD inline int fir_morph_mode(const XfSeg& g, uint64_t T) {
+    const bool rest = g.dur == 0u || T - g.t0 >= (uint64_t)g.dur;
+    return rest && g.P1 == 0.0f ? FIR_MODE_A : (rest && g.P1 == 1.0f ? FIR_MODE_B : FIR_MODE_BOTH);
+}
+// one block of `frames` frames, its messages applied: the record, then the advanced time
+FW_TYPES_HD inline FirMorphBlk fir_morph_block(NodeState& s, uint32_t frames) {
+    const XfSeg g = fir_morph_seg(s);
+    const uint64_t T = fir_morph_time(s);
+    FirMorphBlk b = {g.P0, g.P1, g.x1, g.y1, g.x2, g.y2, (uint32_t)g.t0, (uint32_t)(g.t0 >> 32), g.dur, g.shape, (uint32_t)T, (uint32_t)(T >> 32),
+                     fir_morph_mode(g, T), s.playing, {0u, 0u}};
+    fir_morph_set_time(s, T + (uint64_t)frames);
+    return b;
+}
+// frame n (node time) of a block whose record is b, from the two slot sums (an idle or empty slot's: +0.0f, never read at its end)
+FW_TYPES_HD_INLINE float fir_morph_out(const FirMorphBlk& b, const XfSeg& g, uint64_t n, float sA, float sB) {
+    if (b.mode == FIR_MODE_A) return sA;
+    if (b.mode == FIR_MODE_B) return sB;
+    float p[1], ga, gb;
+    xf_positions<1>(g, n, p);
+    if (p[0] == 0.0f) return sA;
+    if (p[0] == 1.0f) return sB;
+    xf_gains(b.law, p[0], ga, gb);
+    return (sA * ga) + (sB * gb);
+}
 
 #define CH_FAST_KMAX 64  // blocks per k_chain launch its steady-call loop keeps per-block source addresses for (LDS);
                          // the host never batches more blocks than this into one chain-plan launch

@@ -100,41 +100,7 @@ __device__ __forceinline__ uint64_t sat_round_u64(double x) {  // `(x).round() a
 // the four consecutive frames a lane renders).  Every operation is a separately rounded f32 operation (-ffp-contract=off), the
 // division and the square roots are IEEE.  B(t; a, d) = ((q*t + b)*t + c)*t, the cubic Bezier coordinate through 0, a, d, 1
 // (XfCubic, xf_cubic, xf_bezier and the solver fw_curve_y: fwgpu_types.h — the gain ride reads the same curve)
-// the segment as the position rule reads it
-struct XfSeg {
-    float P0, P1, x1, y1, x2, y2;
-    uint64_t t0;
-    uint32_t dur;
-    int shape;
-};
-__device__ __forceinline__ XfSeg xf_seg(const NodeState& s) {
-    return XfSeg{s.p0, s.p1, s.phasor, s.phasor_inc, s.gain, s.aux, s.loop_start, (uint32_t)s.full_range, s.has_loop};
-}
-// the positions of frames n .. n + W - 1 (node time) under the segment.  The solver — XF_ITERS bisection steps on x(t) = u, then
-// y(t) — runs on the W frames at once, its loop rolled: the same trip count for every frame, nothing indexed by a variable
-template <int W>
-__device__ __forceinline__ void xf_positions(const XfSeg& g, uint64_t n, float (&p)[W]) {
-    const uint32_t dur = g.dur;
-    const uint64_t k0 = n - g.t0;
-#pragma unroll
-    for (int e = 0; e < W; ++e) p[e] = g.P1;
-    if (dur == 0u || k0 >= (uint64_t)dur) return;
-    const float fdur = (float)dur;  // (exact: dur <= 2^24; so is every k < dur)
-    float u[W], y[W];
-#pragma unroll
-    for (int e = 0; e < W; ++e) u[e] = (float)((uint32_t)k0 + (uint32_t)e) / fdur;
-    fw_curve_y<W>(g.shape, g.x1, g.y1, g.x2, g.y2, u, y);
-    const float span = g.P1 - g.P0;
-#pragma unroll
-    for (int e = 0; e < W; ++e)
-        if (k0 + (uint64_t)e < (uint64_t)dur)  // (the segment may end among the W frames)
-            p[e] = fminf(fmaxf(g.P0 + (span * y[e]), 0.0f), 1.0f);  // an overshooting curve is allowed; the position is clamped
-}
-__device__ __forceinline__ void xf_gains(int law, float p, float& a, float& b) {
-    const float q = 1.0f - p;
-    a = law == XF_LAW_LINEAR ? q : sqrtf(q);
-    b = law == XF_LAW_LINEAR ? p : sqrtf(p);
-}
+// (XfSeg, xf_seg, xf_positions and xf_gains: fwgpu_types.h — the FIR morph reads the same rule, and so does a host build)
 
 // first command of (state, block) in the (state, block, seq)-sorted list
 __device__ inline int chain_cmd_lower_bound(const Cmd* cmds, int n_cmds, int state_idx, uint32_t block) {

@@ -23,11 +23,15 @@ __global__ void k_ir_convert(const SampleDesc* __restrict__ samples, int sample,
 
 // append the blocks' input to each row's mirrored history ring (positions q and q+R hold the same sample);
 // blockIdx.y = block of the K-batch (the ring holds T-1 + K*max_block_frames samples: every block's window is there)
-__global__ void k_fir_append(DevView v, const FirRow* __restrict__ rows, int n_rows) {
+// MORPH (here and below): the instantiation for a morph group (SPEC FIR morph, fwgpu_types.h fir_morph_*) — a B row reads its node's
+// ring and never appends to it
+template <bool MORPH>
+__device__ __forceinline__ void fir_append_body(const DevView& v, const FirRow* __restrict__ rows, int n_rows) {
     int r = blockIdx.x;
     if (r >= n_rows) return;
     const FirRow row = rows[r];
     if (row.state < 0) return;  // padding row (tiles are impulse-response-homogeneous)
+    if (MORPH && row.in_buf < 0) return;
     const uint32_t kb = blockIdx.y;
     const NodeState* s = &v.states[row.state];
     const uint32_t R = (uint32_t)s->loop_end, p = (uint32_t)s->playhead;
@@ -40,30 +44,94 @@ __global__ void k_fir_append(DevView v, const FirRow* __restrict__ rows, int n_r
         ring[q + R] = x;
     }
 }
+__global__ void k_fir_append(DevView v, const FirRow* __restrict__ rows, int n_rows) { fir_append_body<false>(v, rows, n_rows); }
+__global__ void k_fir_append_morph(DevView v, const FirRow* __restrict__ rows, int n_rows) { fir_append_body<true>(v, rows, n_rows); }
+
+// a morph node's record of block kb of this batch; nullptr: a state the plan build would not let through (nothing may be touched)
+__device__ __forceinline__ const FirMorphBlk* fir_morph_blk(const DevView& v, int state, uint32_t kb) {
+    const NodeState* s = &v.states[state];
+    const uint64_t tab = fir_morph_tab(*s), end = (uint64_t)s->ext_off + (uint64_t)s->ext_len;
+    if (!fir_morph_on(*s) || kb >= fir_morph_tab_n(*s) || tab < (uint64_t)s->ext_off || tab + ((uint64_t)kb + 1u) * FIR_MORPH_BLK_FLOATS > end) return nullptr;
+    return (const FirMorphBlk*)(v.ext + tab) + kb;
+}
+// does this row's slot run in block kb?  (a padding row, an idle slot: no)
+__device__ __forceinline__ bool fir_morph_row_runs(const DevView& v, const FirRow& row, uint32_t kb) {
+    if (row.state < 0) return false;
+    const FirMorphBlk* b = fir_morph_blk(v, row.state, kb);
+    return b && (b->mode & (row.in_buf < 0 ? FIR_MODE_B : FIR_MODE_A)) != 0;
+}
+// The control step of a morph group, in front of its GEMM: a thread per node (its A row of channel 0) walks the call's messages for
+// the node in block order, leaves per block of the batch the segment in force at that block's first frame and the block's mode, and
+// stores the advanced segment and node time.  The ring position is k_fir_reduce_morph's, as a plain node's is k_fir_reduce's
+__global__ void k_fir_morph_control(DevView v, const FirRow* __restrict__ rows, int n_rows, uint32_t K) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const FirRow row = rows[r];
+    if (row.state < 0 || row.in_buf < 0 || row.ch != 0) return;
+    NodeState* sp = &v.states[row.state];
+    NodeState s = *sp;
+    if (!fir_morph_state_ok(s, 1, 1) || K > fir_morph_tab_n(s)) return;  // (the bounds of one channel: the weakest any node has)
+    FirMorphBlk* tab = (FirMorphBlk*)(v.ext + fir_morph_tab(s));
+    const uint32_t cmd_block0 = v.fir_morph & ~FIR_MORPH_GROUP;
+    int i = chain_cmd_lower_bound(v.cmds, v.n_cmds, row.state, cmd_block0);
+    for (uint32_t kb = 0; kb < K; ++kb) {
+        const uint32_t block = cmd_block0 + kb;
+        for (; i < v.n_cmds; ++i) {
+            const Cmd c = v.cmds[i];
+            if (c.state != row.state || c.block != block) break;
+            if (c.type == CMD_XF_TO) fir_morph_msg(s, c.f0, (uint32_t)c.i0, c.i1, xf_cmd_x1(c), xf_cmd_y1(c), xf_cmd_x2(c), xf_cmd_y2(c));
+        }
+        tab[kb] = fir_morph_block(s, (uint32_t)v.frames);
+    }
+    sp->p0 = s.p0;
+    sp->p1 = s.p1;
+    sp->s0 = s.s0;
+    sp->full_range = s.full_range;
+    sp->has_loop = s.has_loop;
+    sp->phasor = s.phasor;
+    sp->phasor_inc = s.phasor_inc;
+    sp->gain = s.gain;
+    sp->aux = s.aux;
+}
 
 #define FIR_PITCH (FIR_KC + 1)  // LDS row pitch in floats: 65 -> the 32 rows of a column hit 32 different banks
-__global__ __launch_bounds__(256) void k_fir_gemm(DevView v, const FirRow* __restrict__ rows, int n_rows,
-                                                  const uint32_t* __restrict__ tile_h_off, uint32_t T,
-                                                  float* __restrict__ partials, int n_rows_pad, int n_pad, int col_groups) {
+template <bool MORPH>
+__device__ __forceinline__ void fir_gemm_body(const DevView& v, const FirRow* __restrict__ rows, int n_rows,
+                                              const uint32_t* __restrict__ tile_h_off, uint32_t T,
+                                              float* __restrict__ partials, int n_rows_pad, int n_pad, int col_groups) {
     __shared__ float lds[2 * 32 * FIR_PITCH + 2 * (256 + FIR_KC)];
     float* As = lds;                          // [2][32][FIR_PITCH]
     float* Hw = lds + 2 * 32 * FIR_PITCH;     // [2][256 + FIR_KC]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int row0 = blockIdx.x * 32;
+    // MORPH: the tile a workgroup takes is rotated by its (segment, block): with blockIdx.x the tile, the idle tiles of a group at
+    // rest — one whole slot, a fixed half of every run of blockIdx.x — fell on the same places of the dispatcher's round and the
+    // running half rendered at half the chip's rate (scripts/fir_morph_cost.py: "rest" took 1.92 x "plain" before)
+    int tile_ = (int)blockIdx.x;
+    if constexpr (MORPH) tile_ = (int)((blockIdx.x + blockIdx.y * 5u + blockIdx.z * 11u) % gridDim.x);
+    const int tile = tile_;
+    const int row0 = tile * 32;
     const uint32_t seg = blockIdx.y;
     const uint32_t kb = blockIdx.z / (uint32_t)col_groups;               // block of the K-batch
     const int ib = (int)(blockIdx.z % (uint32_t)col_groups) * 256;       // first output frame of this column group
+    if constexpr (MORPH) {  // a tile whose every row is idle in this block returns before its first load (fwgpu_fir_morph_stats counts both)
+        const int runs = tid < 32 && row0 + tid < n_rows && fir_morph_row_runs(v, rows[row0 + tid], kb) ? 1 : 0;
+        if (!__syncthreads_or(runs)) {
+            if (tid == 0 && v.chain_done) atomicAdd((unsigned long long*)v.chain_done + 1, 1ull);  // (a morph view's chain_done: the two counters)
+            return;
+        }
+        if (tid == 0 && v.chain_done) atomicAdd((unsigned long long*)v.chain_done, 1ull);
+    }
     const int frames = v.frames;
     const uint32_t W = T - 1u + (uint32_t)frames;
     const uint32_t m_begin = seg * FIR_SEG;
     const uint32_t m_end = m_begin + FIR_SEG < W ? m_begin + FIR_SEG : W;
-    const float* h = v.ext + tile_h_off[blockIdx.x];  // every row of a tile convolves with the same h
+    const float* h = v.ext + tile_h_off[tile];  // every row of a tile convolves with the same h
 
     // loader role: thread t stages 8 consecutive window positions of row (t >> 3)
     constexpr int NA = FIR_KC / 8;  // floats per loader thread: 8 threads cover one row of the chunk
     const int lrow = tid >> 3, lcol = (tid & 7) * NA;
     const float* wptr = nullptr;
-    if (row0 + lrow < n_rows && rows[row0 + lrow].state >= 0) {
+    if (row0 + lrow < n_rows && rows[row0 + lrow].state >= 0 && (!MORPH || fir_morph_row_runs(v, rows[row0 + lrow], kb))) {  // (an idle row is staged as zeros)
         const FirRow row = rows[row0 + lrow];
         const NodeState* s = &v.states[row.state];
         const uint32_t R = (uint32_t)s->loop_end, p = (uint32_t)s->playhead;
@@ -150,6 +218,16 @@ __global__ __launch_bounds__(256) void k_fir_gemm(DevView v, const FirRow* __res
         P[(size_t)rr * row_pitch + ct1 * 32 + (lane & 31)] = acc1[r];
     }
 }
+__global__ __launch_bounds__(256) void k_fir_gemm(DevView v, const FirRow* __restrict__ rows, int n_rows,
+                                                  const uint32_t* __restrict__ tile_h_off, uint32_t T,
+                                                  float* __restrict__ partials, int n_rows_pad, int n_pad, int col_groups) {
+    fir_gemm_body<false>(v, rows, n_rows, tile_h_off, T, partials, n_rows_pad, n_pad, col_groups);
+}
+__global__ __launch_bounds__(256) void k_fir_gemm_morph(DevView v, const FirRow* __restrict__ rows, int n_rows,
+                                                        const uint32_t* __restrict__ tile_h_off, uint32_t T,
+                                                        float* __restrict__ partials, int n_rows_pad, int n_pad, int col_groups) {
+    fir_gemm_body<true>(v, rows, n_rows, tile_h_off, T, partials, n_rows_pad, n_pad, col_groups);
+}
 
 // segment partials added in segment order; writes the node outputs, clears their silence flags, advances the ring
 __global__ void k_fir_reduce(DevView v, const FirRow* __restrict__ rows, int n_rows, const float* __restrict__ partials,
@@ -179,3 +257,46 @@ __global__ void k_fir_reduce(DevView v, const FirRow* __restrict__ rows, int n_r
     }
 }
 
+
+// ... of a morph group: a workgroup per (A row, block).  The slot sums are the plain node's — segment partials in segment order, then
+// + (+0.0f) — taken only from a slot that ran; the frame is the copy or the blend of fir_morph_out.  `partner`: per row of the group
+// the row of its node's other slot (FIR_NO_PARTNER: an empty slot B, whose sum is +0.0)
+__global__ void k_fir_reduce_morph(DevView v, const FirRow* __restrict__ rows, int n_rows, const uint32_t* __restrict__ partner,
+                                   const float* __restrict__ partials, int n_segs, int n_rows_pad, int n_pad) {
+    int r = blockIdx.x;
+    if (r >= n_rows) return;
+    const FirRow row = rows[r];
+    if (row.state < 0 || row.in_buf < 0) return;
+    const uint32_t kb = blockIdx.y, K = gridDim.y;
+    const FirMorphBlk* bp = fir_morph_blk(v, row.state, kb);
+    if (!bp) return;
+    const FirMorphBlk b = *bp;
+    if (b.mode == FIR_MODE_NONE) return;
+    const uint32_t rb = partner[r];
+    const bool run_a = (b.mode & FIR_MODE_A) != 0, run_b = (b.mode & FIR_MODE_B) != 0 && rb != FIR_NO_PARTNER && rb < (uint32_t)n_rows;
+    const XfSeg g = fir_morph_seg(b);
+    const uint64_t T0 = (uint64_t)b.T_lo | ((uint64_t)b.T_hi << 32);
+    const size_t row_pitch = (size_t)K * n_pad;
+    float* out = v.pool + (size_t)kb * v.pool_blk_stride + (size_t)row.out_buf * v.stride;
+    for (int i = threadIdx.x; i < v.frames; i += blockDim.x) {
+        float sa = 0.0f, sb = 0.0f;
+        if (run_a) {
+            float t = partials[(size_t)r * row_pitch + (size_t)kb * n_pad + i];
+            for (int sgm = 1; sgm < n_segs; ++sgm) t = t + partials[((size_t)sgm * n_rows_pad + r) * row_pitch + (size_t)kb * n_pad + i];
+            sa = t + 0.0f;
+        }
+        if (run_b) {
+            float t = partials[(size_t)rb * row_pitch + (size_t)kb * n_pad + i];
+            for (int sgm = 1; sgm < n_segs; ++sgm) t = t + partials[((size_t)sgm * n_rows_pad + rb) * row_pitch + (size_t)kb * n_pad + i];
+            sb = t + 0.0f;
+        }
+        out[i] = fir_morph_out(b, g, T0 + (uint64_t)i, sa, sb);
+    }
+    if (threadIdx.x == 0) {
+        v.flags[(size_t)kb * v.flags_blk_stride + row.out_buf] = 0;
+        if (row.ch == 0 && kb == 0) {
+            NodeState* s = &v.states[row.state];
+            s->playhead = (s->playhead + (uint64_t)K * (uint64_t)v.frames) % s->loop_end;
+        }
+    }
+}

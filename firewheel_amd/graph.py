@@ -362,11 +362,40 @@ class DelayNode(_Node):  # SPEC node: integer-sample delay line (fixed length) w
 class FirReverbNode(_Node):  # SPEC node: convolution with an impulse-response sample (f32 MFMA Toeplitz GEMM)
     KIND = 12
 
-    def __init__(self, impulse_response_sample):
-        self.ir = impulse_response_sample
+    def __init__(self, ir, ir_b=None, max_taps=0, position=0.0, law=1, morph=None):
+        """ir alone: the plain node.  Anything else given: a morph-capable node (SPEC FIR morph, include/fwgpu.h) — slot A = ir, slot
+        B = ir_b (None: empty), both zero-padded to max_taps (0: the longer of the two), blended at `position` (0 = A, 1 = B) under
+        `law` (0 linear, 1 equal power).  morph=True asks for a morph-capable node whatever the other arguments are — with ir_b=None
+        and the defaults that is the wet fader, a node with an empty slot B; morph=None (default) decides as above"""
+        self.ir, self.ir_b, self.max_taps, self.position, self.law = ir, ir_b, max_taps, position, law
+        self.morph = bool(morph) if morph is not None else not (ir_b is None and max_taps == 0 and position == 0.0 and law == 1)
+        if not self.morph and not (ir_b is None and max_taps == 0 and position == 0.0 and law == 1):
+            raise ValueError("FirReverbNode: morph=False with ir_b, max_taps, position or law given")
 
     def params(self):
-        return [float(self.ir)]
+        if not self.morph:
+            return [float(self.ir)]
+        return [float(self.ir), float(-1 if self.ir_b is None else self.ir_b), float(self.max_taps), float(self.position), float(self.law)]
+
+    def morph_to(self, position, frames, curve=None, at_block=0):
+        """from block `at_block` of the next process call on, move to `position` over `frames` frames (0: a jump) along `curve`
+        (None: linear; else the Bezier's (x1, y1, x2, y2)) — fwgpu_fir_morph"""
+        shape, (x1, y1, x2, y2) = (0, (0.0, 0.0, 1.0, 1.0)) if curve is None else (1, curve)
+        self.cx._check(self.cx.L.fwgpu_fir_morph(self.cx.c, self.id, position, frames, shape, x1, y1, x2, y2, at_block))
+        self.position = position
+
+    def morph_to_secs(self, position, secs, curve=None, at_block=0):
+        """... over `secs` seconds, rounded to whole frames of the context's sample rate"""
+        self.morph_to(position, max(0, int(round(secs * self.cx.sample_rate))), curve, at_block)
+
+    def set_ir(self, slot, sample):
+        """exchange the impulse response of a slot nobody hears (0 = A, 1 = B; sample None: empty slot B); takes effect with the next
+        update — fwgpu_fir_set_ir"""
+        self.cx._check(self.cx.L.fwgpu_fir_set_ir(self.cx.c, self.id, slot, -1 if sample is None else sample))
+        if slot == 0:
+            self.ir = sample
+        else:
+            self.ir_b = sample
 
 
 class ResamplerNode(_Node):  # SPEC node: resampling source — polyphase windowed sinc, 32.32 fixed-point position
@@ -956,6 +985,12 @@ class FirewheelGpuCtx(object):
     def hip_stream(self):
         """the hipStream_t (int) the ctx's process calls launch on — include/fwgpu.h fwgpu_hip_stream"""
         return int(self.L.fwgpu_hip_stream(self.c) or 0)
+
+    def fir_morph_stats(self):
+        """(GEMM workgroups of FIR morph groups that ran, that returned idle) — include/fwgpu.h fwgpu_fir_morph_stats"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.fwgpu_fir_morph_stats(self.c, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def lazy_stats(self):
         """(launch batches rendered without a control kernel, with one) — include/fwgpu.h fwgpu_lazy_stats"""

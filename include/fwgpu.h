@@ -53,7 +53,9 @@ enum fwgpu_node_kind {
     FWGPU_STEREO_WIDTH = 9,   /* SPEC                 params: width */
     FWGPU_BIQUAD = 10,        /* SPEC                 params: type, cutoff_hz, q */
     FWGPU_DELAY = 11,         /* SPEC                 params: delay_secs, feedback, mix */
-    FWGPU_FIR = 12,           /* SPEC convolution     params: impulse-response sample id (fwgpu_sample_create) */
+    FWGPU_FIR = 12,           /* SPEC convolution     params: impulse-response sample id (fwgpu_sample_create).  With two or more
+                                 parameters the node is morph-capable: ir_a, ir_b (-1: empty), max_taps (0: the longer of the two),
+                                 position (0..1, default 0), law (0 linear, 1 equal power; default 1); see "FIR morph" below */
     FWGPU_RESAMPLER = 13,     /* SPEC polyphase resampling source (0 inputs)  params: sample id, ratio, loop, playing */
     FWGPU_SPATIAL = 14,       /* SPEC 3D spatialiser (1|2 in, 2 out)          params: x, y, z of the source */
     FWGPU_HOST_NODE = 15,     /* any other `dyn AudioNodeProcessor` (graph/processor.rs:243): runs on the HOST, see below */
@@ -710,6 +712,37 @@ int fwgpu_graph_output_latency(fwgpu_ctx* ctx, uint32_t* frames);
 #define FWGPU_CROSSFADE_CH_MAX 8
 int fwgpu_crossfade_to(fwgpu_ctx* ctx, int64_t node, float position, uint32_t frames, int shape, float x1, float y1, float x2, float y2,
                        uint32_t at_block);
+
+/* ---- FIR reverb morph: two impulse responses over one history, blended along the crossfader's curve (SPEC).
+ * A FWGPU_FIR node created with ONE parameter is the plain node.  Created with two or more it is morph-capable: slot A and slot B each
+ * hold an impulse response, zero-padded to the node's tap capacity T (max_taps, or the longer of the two), and both convolve the SAME
+ * input history — one ring per channel, appended every block whatever the position.  The slot sum s_X[n] is bit for bit the output of
+ * a plain FIR node whose sample is slot X's impulse response padded to T (window T-1+frames, segments of 4096 positions, one fma
+ * chain per segment from +0.0, partials added in order, + (+0.0f)); channel c convolves with channel min(c, C_h - 1); an empty slot's
+ * sum is +0.0.  Position p of frame n, node time, the segment, the retarget rule and the gains a, b are the crossfader's above, and
+ *   p == 0:  y = s_A, a copy        p == 1:  y = s_B, a copy        otherwise  y = (s_A * a) + (s_B * b)   (no FMA)
+ * A block at rest (dur == 0, or the segment over at its first frame) at p == 0 leaves slot B idle — no matrix work —, at p == 1 slot
+ * A; in every other block both slots run.  The out flag is cleared as a plain node's; latency is unchanged.  A bad ir_b, max_taps
+ * (not 0 and shorter than an impulse response, or above 2^24), position or law is refused by the next fwgpu_update, as a crossfader's.
+ *
+ * fwgpu_fir_morph: fwgpu_crossfade_to for such a node — same message, same refusals (and FWGPU_ERR_INVALID for a plain FIR node).
+ *
+ * fwgpu_fir_set_ir: exchange the impulse response of `slot` (0 = A, 1 = B) for `sample` (slot 1: or -1, an empty slot) — a graph
+ * edit: it takes effect with the plan the next fwgpu_update builds.  The new impulse response convolves the history the node has: when
+ * it fades in, its tail is complete from the first frame.  FWGPU_ERR_INVALID when the node is not morph-capable, the sample is a
+ * stream, empty or longer than T, -1 is given for slot 0 (slot A's rows append the history), or the slot is not inaudible: the last
+ * morph sent (none: the creation position) must target exactly the OTHER slot's end, and its last frame must lie within the frames of
+ * the process calls started so far (a call counts from its start: the edit is adopted by a later call's plan, never by the one in
+ * flight).  A morph sent after the edit and before that update — or before the node's first update — is held and released by the
+ * update; it starts only then, and while one is held both slots count as audible.  A sample
+ * in either slot cannot be destroyed; its converted copy is cached per (sample, channel, T) and freed with its last user.
+ *
+ * fwgpu_fir_morph_stats: GEMM workgroups of morph groups since the context was created — that ran / that returned because every row of
+ * their tile was idle in their block. */
+int fwgpu_fir_morph(fwgpu_ctx* ctx, int64_t node, float position, uint32_t frames, int shape, float x1, float y1, float x2, float y2,
+                    uint32_t at_block);
+int fwgpu_fir_set_ir(fwgpu_ctx* ctx, int64_t node, int slot, int sample);
+int fwgpu_fir_morph_stats(fwgpu_ctx* ctx, uint64_t* tiles_run, uint64_t* tiles_skipped);
 
 /* ---- resampling source: a ratio glide (Doppler) in one message (SPEC).
  * fwgpu_resampler_glide: from the first frame of block `at_block` of the next process call, move the node's ratio to `ratio` over

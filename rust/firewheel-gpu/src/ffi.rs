@@ -224,6 +224,9 @@ extern "C" {
     pub fn fwgpu_graph_latency_report(ctx: *mut fwgpu_ctx, out: *mut fwgpu_latency_skew, cap: u32) -> i64;
     pub fn fwgpu_graph_output_latency(ctx: *mut fwgpu_ctx, frames: *mut u32) -> c_int;
     pub fn fwgpu_crossfade_to(ctx: *mut fwgpu_ctx, node: i64, position: f32, frames: u32, shape: c_int, x1: f32, y1: f32, x2: f32, y2: f32, at_block: u32) -> c_int;
+    pub fn fwgpu_fir_morph(ctx: *mut fwgpu_ctx, node: i64, position: f32, frames: u32, shape: c_int, x1: f32, y1: f32, x2: f32, y2: f32, at_block: u32) -> c_int;
+    pub fn fwgpu_fir_set_ir(ctx: *mut fwgpu_ctx, node: i64, slot: c_int, sample: c_int) -> c_int;
+    pub fn fwgpu_fir_morph_stats(ctx: *mut fwgpu_ctx, tiles_run: *mut u64, tiles_skipped: *mut u64) -> c_int;
     pub fn fwgpu_resampler_glide(ctx: *mut fwgpu_ctx, node: i64, ratio: f32, frames: u32, at_block: u32) -> c_int;
     pub fn fwgpu_gain_ride(ctx: *mut fwgpu_ctx, node: i64, value: f32, frames: u32, shape: c_int, x1: f32, y1: f32, x2: f32, y2: f32, at_block: u32) -> c_int;
     pub fn fwgpu_spatial_move(ctx: *mut fwgpu_ctx, node: i64, x: f32, y: f32, z: f32, frames: u32, at_block: u32) -> c_int;

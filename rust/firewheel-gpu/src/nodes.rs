@@ -568,10 +568,56 @@ impl GpuSpatialNode {
 pub struct GpuFirReverbNode {
     b: Binding,
     ir: GpuSample,
+    /// Some: a morph-capable node (two impulse-response slots over one history, include/fwgpu.h "FIR morph")
+    morph: Option<FirMorph>,
+}
+struct FirMorph {
+    ir_b: Option<GpuSample>,
+    max_taps: u32,
+    position: f32,
+    law: CrossfadeLaw,
 }
 impl GpuFirReverbNode {
     pub fn new(cx: &Arc<GpuContext>, impulse_response: GpuSample) -> Self {
-        Self { b: Binding::new(cx), ir: impulse_response }
+        Self { b: Binding::new(cx), ir: impulse_response, morph: None }
+    }
+    /// Slot A = `ir_a`, slot B = `ir_b` (None: empty), both zero-padded to `max_taps` (0: the longer of the two), blended at
+    /// `position` (0 = all A, 1 = all B) under `law`.  A bad value fails activation.
+    pub fn new_morph(cx: &Arc<GpuContext>, ir_a: GpuSample, ir_b: Option<GpuSample>, max_taps: u32, position: f32, law: CrossfadeLaw) -> Self {
+        Self { b: Binding::new(cx), ir: ir_a, morph: Some(FirMorph { ir_b, max_taps, position, law }) }
+    }
+    /// From the next block on, move to `position` over `frames` frames (0: a jump) along `curve` (fwgpu_fir_morph); a retarget in
+    /// mid-fade starts where the old fade stands.  Before activation only the target is kept: the node then starts at rest there.
+    pub fn morph_to(&mut self, position: f32, frames: u32, curve: CrossfadeCurve) -> Result<(), GpuError> {
+        let (shape, x1, y1, x2, y2) = match curve {
+            CrossfadeCurve::Linear => (0, 0.0, 0.0, 1.0, 1.0),
+            CrossfadeCurve::Bezier(x1, y1, x2, y2) => (1, x1, y1, x2, y2),
+        };
+        if let Some(node) = self.b.node {
+            let _g = self.b.cx.control();
+            let rc = unsafe { ffi::fwgpu_fir_morph(self.b.cx.as_ptr(), node, position, frames, shape, x1, y1, x2, y2, 0) };
+            self.b.cx.check(rc as i64)?;
+        }
+        if let Some(m) = self.morph.as_mut() {
+            m.position = position;
+        }
+        Ok(())
+    }
+    /// Exchange the impulse response of a slot nobody hears (0 = A, 1 = B; None: an empty slot B) — fwgpu_fir_set_ir; it takes effect
+    /// with the next update.  Before activation the constructor's value is replaced.
+    pub fn set_ir(&mut self, slot: u32, sample: Option<GpuSample>) -> Result<(), GpuError> {
+        if let Some(node) = self.b.node {
+            let _g = self.b.cx.control();
+            let id = sample.as_ref().map_or(-1, |s| s.id() as std::os::raw::c_int);
+            let rc = unsafe { ffi::fwgpu_fir_set_ir(self.b.cx.as_ptr(), node, slot as std::os::raw::c_int, id) };
+            self.b.cx.check(rc as i64)?;
+        }
+        match (slot, sample, self.morph.as_mut()) {
+            (0, Some(s), _) => self.ir = s,
+            (1, s, Some(m)) => m.ir_b = s,
+            _ => {}
+        }
+        Ok(())
     }
 }
 impl AudioNode for GpuFirReverbNode {
@@ -584,7 +630,13 @@ impl AudioNode for GpuFirReverbNode {
     fn activate(&mut self, _sr: u32, _mbf: usize, num_inputs: usize, num_outputs: usize) -> Result<Box<dyn AudioNodeProcessor>, Box<dyn Error>> {
         // FIR banks run at graph level (one MFMA GEMM per schedule level): use this node under GpuProcessor (B2);
         // fwgpu_node_process refuses it
-        self.b.activate(ffi::FWGPU_FIR, num_inputs, num_outputs, &[self.ir.id() as f32])
+        match &self.morph {
+            None => self.b.activate(ffi::FWGPU_FIR, num_inputs, num_outputs, &[self.ir.id() as f32]),
+            Some(m) => {
+                let ir_b = m.ir_b.as_ref().map_or(-1.0, |s| s.id() as f32);
+                self.b.activate(ffi::FWGPU_FIR, num_inputs, num_outputs, &[self.ir.id() as f32, ir_b, m.max_taps as f32, m.position, m.law as i32 as f32])
+            }
+        }
     }
     fn deactivate(&mut self, _p: Option<Box<dyn AudioNodeProcessor>>) {
         self.b.deactivate()
