@@ -1050,6 +1050,14 @@ int fwgpu_ext_pool_floats(fwgpu_ctx* c, uint64_t* in_use, uint64_t* capacity) {
     return 0;
 }
 
+// The automation curve of fwgpu_crossfade_to, fwgpu_fir_morph and fwgpu_gain_ride (`who`): the shape, x in 0..1, y in -1..2.  0: the
+// curve is good; else the refusal, reported in the caller's name
+static int refuse_bad_curve(fwgpu_ctx* c, const char* who, int shape, float x1, float y1, float x2, float y2) {
+    if (shape != XF_SHAPE_LINEAR && shape != XF_SHAPE_BEZIER) return fail(c, FWGPU_ERR_INVALID, who, "shape must be 0 (linear) or 1 (Bezier)");
+    if (!(x1 >= 0.0f && x1 <= 1.0f && x2 >= 0.0f && x2 <= 1.0f)) return fail(c, FWGPU_ERR_INVALID, who, "x1 and x2 must be in 0..1");
+    if (!(y1 >= -1.0f && y1 <= 2.0f && y2 >= -1.0f && y2 <= 2.0f)) return fail(c, FWGPU_ERR_INVALID, who, "y1 and y2 must be in -1..2");
+    return 0;
+}
 // SPEC crossfader: one CMD_XF_TO; position and x in 0..1, y in -1..2, at most 2^24 frames
 int fwgpu_crossfade_to(fwgpu_ctx* c, int64_t node, float position, uint32_t frames, int shape, float x1, float y1, float x2, float y2,
                        uint32_t at_block) {
@@ -1060,11 +1068,7 @@ int fwgpu_crossfade_to(fwgpu_ctx* c, int64_t node, float position, uint32_t fram
     if (n->kind != K_CROSSFADE) return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: the node is not a CrossfadeNode");
     if (!(position >= 0.0f && position <= 1.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: position must be in 0..1");
     if (frames > FWGPU_CROSSFADE_FRAMES_MAX) return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: at most 2^24 frames");
-    if (shape != XF_SHAPE_LINEAR && shape != XF_SHAPE_BEZIER) return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: shape must be 0 (linear) or 1 (Bezier)");
-    if (!(x1 >= 0.0f && x1 <= 1.0f && x2 >= 0.0f && x2 <= 1.0f))
-        return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: x1 and x2 must be in 0..1");
-    if (!(y1 >= -1.0f && y1 <= 2.0f && y2 >= -1.0f && y2 <= 2.0f))
-        return fail(c, FWGPU_ERR_INVALID, "fwgpu_crossfade_to: y1 and y2 must be in -1..2");
+    if (int rc = refuse_bad_curve(c, "fwgpu_crossfade_to", shape, x1, y1, x2, y2)) return rc;
     return push_cmd(c, node, K_CROSSFADE, make_xf_to(at_block, position, frames, shape, x1, y1, x2, y2), false);
 }
 // SPEC FIR morph: one CMD_XF_TO for a morph-capable FirReverbNode, with fwgpu_crossfade_to's refusals.  The host keeps
@@ -1077,9 +1081,7 @@ int fwgpu_fir_morph(fwgpu_ctx* c, int64_t node, float position, uint32_t frames,
     if (n->kind != K_FIR || !n->fir_morph) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: the node is not a morph-capable FirReverbNode");
     if (!(position >= 0.0f && position <= 1.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: position must be in 0..1");
     if (frames > XF_FRAMES_MAX) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: at most 2^24 frames");
-    if (shape != XF_SHAPE_LINEAR && shape != XF_SHAPE_BEZIER) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: shape must be 0 (linear) or 1 (Bezier)");
-    if (!(x1 >= 0.0f && x1 <= 1.0f && x2 >= 0.0f && x2 <= 1.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: x1 and x2 must be in 0..1");
-    if (!(y1 >= -1.0f && y1 <= 2.0f && y2 >= -1.0f && y2 <= 2.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_fir_morph: y1 and y2 must be in -1..2");
+    if (int bad = refuse_bad_curve(c, "fwgpu_fir_morph", shape, x1, y1, x2, y2)) return bad;
     Cmd m = make_xf_to(at_block, position, frames, shape, x1, y1, x2, y2);
     int rc;
     // held: the message waits in early_msgs — for the plan that activates the node, or for the one that holds a fwgpu_fir_set_ir — and
@@ -1283,9 +1285,7 @@ int fwgpu_gain_ride(fwgpu_ctx* c, int64_t node, float value, uint32_t frames, in
     if (n->kind != K_VOLUME && n->kind != K_PAN) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: the node is not a VolumeNode or a StereoPanNode");
     if (!(value - value == 0.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: value is NaN or infinite");
     if (frames > FWGPU_GAIN_RIDE_FRAMES_MAX) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: at most 2^24 frames");
-    if (shape != XF_SHAPE_LINEAR && shape != XF_SHAPE_BEZIER) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: shape must be 0 (linear) or 1 (Bezier)");
-    if (!(x1 >= 0.0f && x1 <= 1.0f && x2 >= 0.0f && x2 <= 1.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: x1 and x2 must be in 0..1");
-    if (!(y1 >= -1.0f && y1 <= 2.0f && y2 >= -1.0f && y2 <= 2.0f)) return fail(c, FWGPU_ERR_INVALID, "fwgpu_gain_ride: y1 and y2 must be in -1..2");
+    if (int rc = refuse_bad_curve(c, "fwgpu_gain_ride", shape, x1, y1, x2, y2)) return rc;
     float g0, g1 = 0.0f;  // (a volume has one gain: its second target stays where make_state leaves p1)
     if (n->kind == K_VOLUME) g0 = percent_volume_to_raw_gain(value);
     else pan_to_gains(value, &g0, &g1);

@@ -150,6 +150,38 @@ struct StatCounter {
     operator uint64_t() const { return v.load(std::memory_order_relaxed); }
 };
 
+// The host's book of one kind of ramp (a sweep, a move, a ride: a value moved from A to B over N frames by one message).  `until`: the
+// frame count behind which no ramp of the kind sent so far is in flight — an upper bound: a message for block b starts no later than b
+// whole blocks into its call, and a ramp that a later message cuts short leaves the bound standing, which costs kernels, not bits.
+// `live`: the call being rendered may meet one.
+// The bound assumes the node renders every block from its message on.  A node that leaves the plan in mid-ramp keeps N != 0 in its
+// state slot and may come back with a later plan: max_n = the longest ramp noted while one may be in flight, parked_n = the longest
+// one that a plan install may have parked (never cleared: the node may return with any later plan).
+struct RampBook {
+    uint64_t until = 0;
+    bool live = false;
+    uint32_t max_n = 0, parked_n = 0;
+    // a message on the list: its ramp of n frames is over by frame `end`
+    void note(uint64_t end, uint32_t n) {
+        if (end > until) until = end;
+        if (n > max_n) max_n = n;
+    }
+    // a ramp started by ONE node's process call moves only with that node's calls: the frame count of the process calls says nothing
+    // about it, so from here on every process call of this ctx counts as one that may meet it
+    void pin() { until = ~0ull; }
+    // at the head of a process call, behind note(): may this call meet a ramp?  (forced: it holds a message that only the ramp builds apply)
+    void settle(uint64_t frames_done, bool forced) {
+        live = forced || frames_done < until;
+        if (!live) max_n = 0;
+    }
+    // a plan install: a node may leave the plan here with its ramp in flight, and one that left earlier may come back here with its ramp
+    // where it stood — at most its N frames from now: the call a parked node returns in runs the ramp builds until its ramp is over
+    void park(uint64_t frames_done) {
+        if (frames_done < until && max_n > parked_n) parked_n = max_n;
+        if (parked_n && until != ~0ull && frames_done + parked_n > until) until = frames_done + parked_n;
+    }
+};
+
 struct TimerCat {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
     size_t used = 0;
@@ -417,31 +449,21 @@ struct fwgpu_ctx : fwgpu::PlanImage {
     uint32_t lazy_epoch = 0;                     // epoch the LazyRecs were made under
     bool lazy_valid = false;                     // nothing but lazy calls has moved the voices since they were made
     bool lazy_this_call = false;
-    // biquad coefficient sweeps (CMD_BQ_SWEEP): the host knows every sweep's length and counts the frames it renders —
-    // frames_done: frames rendered by process calls so far; bq_sweep_until: the frame count behind which no sweep sent so far is in
-    // flight (an upper bound: a message for block b starts no later than b whole blocks into its call); bq_sweep_live: the call being
-    // rendered may meet a sweep — no lazy call, no batch walkers (k_level<1> renders the sweep's blocks), k_chain's sweep instantiation
-    uint64_t frames_done = 0, bq_sweep_until = 0;
+    // Ramps in flight: the host knows every ramp's length and counts the frames it renders — frames_done: frames
+    // rendered by process calls so far.  One RampBook per kind of ramp whose calls take other kernels; a call that no book says may meet
+    // a ramp launches exactly the kernels it launched before that ramp existed.
+    uint64_t frames_done = 0;
     // frames_ctl: the control side's view of frames_done — stored by a process call BEFORE it drains the ring, as the count behind that
     // call: a message pushed after the store is applied no earlier than that frame (fwgpu_fir_morph keeps a morph's end by it)
     std::atomic<uint64_t> frames_ctl{0};
-    bool bq_sweep_live = false;
-    // the same for spatialiser moves (CMD_SP_MOVE): sp_move_live — the call being rendered may meet a move: no lazy call, no captured
-    // graph, and the node / control kernels' move instantiations (k_level<1, true>, k_voice_control_spm); a call that cannot meet one
-    // launches exactly the kernels it launched before the move existed
-    uint64_t sp_move_until = 0;
-    bool sp_move_live = false;
-    // The bound assumes the node renders every block from its message on.  A node that leaves the plan in mid-move keeps N != 0 in its
-    // state slot and may come back with a later plan: sp_move_max_n = the longest move noted while one may be in flight,
-    // sp_move_parked_n = the longest one that a plan install may have parked (never cleared: the node may return with any later
-    // plan) — adopt_image extends the bound by it, so the call a parked node returns in runs the move builds until its move is over
-    uint32_t sp_move_max_n = 0, sp_move_parked_n = 0;
-    // the same for gain rides of volume / pan nodes (CMD_GAIN_RIDE): gain_ride_live — the call being rendered may meet a ride: no lazy
-    // call, no captured graph, no resident realtime kernel, and the ride instantiations (k_level<0, false, true>, k_voice_control_ride);
-    // a call that cannot meet one launches exactly the kernels it launched before the ride existed.  _max_n / _parked_n as the move's
-    uint64_t gain_ride_until = 0;
-    bool gain_ride_live = false;
-    uint32_t gain_ride_max_n = 0, gain_ride_parked_n = 0;
+    // sweeps (CMD_BQ_SWEEP): a live call starts no batch walkers (k_level<1> renders the sweep's blocks) and takes k_chain's sweep
+    // instantiation — launch_chain's sweep bit comes from this book alone.  moves (CMD_SP_MOVE): the node / control kernels' move
+    // instantiations (k_level<1, true>, k_voice_control_spm).  gain_rides (CMD_GAIN_RIDE, volume / pan nodes): the ride instantiations
+    // (k_level<0, false, true>, k_voice_control_ride), and — on this book alone — no resident realtime kernel and no one-launch callback
+    // (run_fused_batch: k_rt_block and k_rt_persist keep the control code they had)
+    RampBook sweeps, moves, gain_rides;
+    // this call may meet a ramp of some kind: no lazy call and no captured graph (their control kernel has to run)
+    bool ramp_live() const { return sweeps.live || moves.live || gain_rides.live; }
     StatCounter lazy_calls, ctl_calls;           // fused batches rendered without / with a control kernel (fwgpu_lazy_stats)
     // Grouped calls: a lazy batch of a voice-bank plan whose tree is leaves -> root -> stereo out is rendered by ONE
     // kernel, k_leaf_group_lazy — leaf sums stay on chip, k_root_out does not run.  FWGPU_LEAF_GROUP=0|1 (read at creation) switches
@@ -612,6 +634,7 @@ inline void phase_mark(fwgpu_ctx* c, int p) {
 }
 
 int fail(fwgpu_ctx* c, int code, const char* msg);  // no allocation: the message is copied into a fixed buffer
+int fail(fwgpu_ctx* c, int code, const char* who, const char* what);  // the message is "who: what"
 inline int fail(fwgpu_ctx* c, int code, const std::string& msg) { return fail(c, code, msg.c_str()); }
 // process entry points bracket themselves with this: fail() then writes the audio thread's buffer
 struct AudioCallScope {

@@ -71,10 +71,10 @@ int launch_level(hipStream_t s, const DevView& v, const int* d_level_nodes, int 
     dim3 grid((n_nodes + WPB - 1) / WPB, (K + bpw - 1) / bpw);
     // the level holds a biquad / delay node — in a batch, the ones that are bus effects go to the walkers' kernel
     const uint32_t walkers = (kinds & LB_WALKERS) && K > 1 && !v.no_walkers ? 1u : 0u;
-    // (a call that may meet a gain ride — fwgpu_run.cpp note_gain_rides — takes the instantiation that renders one)
+    // (a call that may meet a gain ride — fwgpu_run.cpp note_ramps — takes the instantiation that renders one)
     if ((kinds & LB_SET0) && v.gain_rides) hipLaunchKernelGGL((k_level<0, false, true>), grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, 0u);
     else if (kinds & LB_SET0) hipLaunchKernelGGL(k_level<0>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, 0u);
-    // (a call that may meet a spatialiser move — fwgpu_run.cpp note_sp_moves — takes the instantiation that renders one)
+    // (a call that may meet a spatialiser move — fwgpu_run.cpp note_ramps — takes the instantiation that renders one)
     if ((kinds & LB_SET1) && v.sp_moves) hipLaunchKernelGGL((k_level<1, true>), grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, walkers);
     else if (kinds & LB_SET1) hipLaunchKernelGGL(k_level<1>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, walkers);
     if (kinds & LB_SET2) hipLaunchKernelGGL(k_level<2>, grid, dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K, bpw, 0u);
@@ -208,8 +208,8 @@ int launch_voice_control(hipStream_t s, const FusedView& fv, int K, uint32_t cmd
     static const int occ = [] { const char* e = getenv("FWGPU_CTL_OCC"); return e ? atoi(e) : 0; }();  // experiments: 1 / 3 = force a build
     const bool small = occ ? occ == 3 : beside_render;
     const int wpb = beside_render ? 1 : 4;
-    // (a call that may meet a spatialiser move — fwgpu_run.cpp note_sp_moves — takes the instantiations that follow one)
-    // (... a gain ride — note_gain_rides — the ride builds, which have the move compiled in too)
+    // (a call that may meet a spatialiser move — fwgpu_run.cpp note_ramps — takes the instantiations that follow one)
+    // (... a gain ride — the ride builds, which have the move compiled in too)
     if (fv.gain_rides && small) hipLaunchKernelGGL(k_voice_control_small_ride, dim3((fv.n_voices + wpb - 1) / wpb), dim3(WAVE * wpb), 0, s, fv, K, cmd_block0);
     else if (fv.gain_rides) hipLaunchKernelGGL(k_voice_control_ride, dim3((fv.n_voices + wpb - 1) / wpb), dim3(WAVE * wpb), 0, s, fv, K, cmd_block0);
     else if (fv.sp_moves && small) hipLaunchKernelGGL(k_voice_control_small_spm, dim3((fv.n_voices + wpb - 1) / wpb), dim3(WAVE * wpb), 0, s, fv, K, cmd_block0);

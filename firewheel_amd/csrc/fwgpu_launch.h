@@ -45,12 +45,12 @@ struct DevView {
     // blocks: two waves never meet in a slot).  meter_K = 0: nothing is recorded (fwgpu_node_process).
     uint64_t meter_blk0 = 0;
     uint32_t meter_K = 0;
-    // 1: this call may meet a biquad coefficient sweep (fwgpu_run.cpp note_bq_sweeps) — launch_level starts no batch walkers: k_level<1>
+    // 1: this call may meet a biquad coefficient sweep (fwgpu_run.cpp note_ramps) — launch_level starts no batch walkers: k_level<1>
     // and k_bus_iir each decide on the device who renders a bus filter, the first moves the sweep's state, and they must decide alike
     int no_walkers = 0;
-    // 1: this call may meet a spatialiser move (fwgpu_run.cpp note_sp_moves) — launch_level renders set 1 with k_level<1, true>
+    // 1: this call may meet a spatialiser move (fwgpu_run.cpp note_ramps) — launch_level renders set 1 with k_level<1, true>
     int sp_moves = 0;
-    // 1: this call may meet a gain ride of a volume / pan node (fwgpu_run.cpp note_gain_rides) — launch_level renders set 0 with
+    // 1: this call may meet a gain ride of a volume / pan node (fwgpu_run.cpp note_ramps) — launch_level renders set 0 with
     // k_level<0, false, true>; fwgpu_node_process sets it for these two kinds (k_single_node<false, true>)
     int gain_rides = 0;
 };
@@ -99,11 +99,11 @@ struct FusedView {
     int has_prog;           // some voice's program is not 0 (or its source is a resampler): k_leaf_sum<true>
     int has_rs;             // some voice's source is a resampler: the program instantiation stages windows + filter bank in LDS
     int has_sp;             // some voice ends in a spatialiser stage: k_leaf_sum_sp
-    int sp_moves = 0;       // this call may meet a spatialiser move (fwgpu_run.cpp note_sp_moves): launch_voice_control takes the instantiations
+    int sp_moves = 0;       // this call may meet a spatialiser move (fwgpu_run.cpp note_ramps): launch_voice_control takes the instantiations
                             // that follow one; a block inside a move is flagged in its VoiceBlk::pad and the leaf kernel reads its delays
                             // from the last two ramp rows
     int sp_hist_in_render;  // control-ahead mode + spatialiser stages: k_sp_hist_copy makes the history copy, not k_voice_control
-    int gain_rides = 0;     // this call may meet a gain ride (fwgpu_run.cpp note_gain_rides): launch_voice_control takes the ride builds; a
+    int gain_rides = 0;     // this call may meet a gain ride (fwgpu_run.cpp note_ramps): launch_voice_control takes the ride builds; a
                             // stage in a ride gets its per-frame gains in its ramp rows, which every render kernel reads as it reads a ramp
                             // (in what was padding: every other field keeps its offset)
     const int* ctl_order;   // k_voice_control: wave w works voice ctl_order[w] (nullptr: w) — voices with messages first

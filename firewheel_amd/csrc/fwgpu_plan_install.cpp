@@ -1323,15 +1323,10 @@ void adopt_image(fwgpu_ctx* c, PlanImage* n, bool on_audio_thread) {
     (void)lazy_flush(c);       // blocks rendered from the OLD plan's LazyRecs reach node state before the voices are renumbered
     (void)join_streams(c);  // control-ahead mode: the control stream's work so far is ordered before the swap
     c->ahead_seq = 0;
-    // spatialiser moves (fwgpu_ctx.h sp_move_parked_n): a spatialiser may leave the plan here with its move in flight, and one that
-    // left earlier may come back here with its move where it stood — at most its N frames from now
-    if (c->frames_done < c->sp_move_until && c->sp_move_max_n > c->sp_move_parked_n) c->sp_move_parked_n = c->sp_move_max_n;
-    if (c->sp_move_parked_n && c->sp_move_until != ~0ull && c->frames_done + c->sp_move_parked_n > c->sp_move_until)
-        c->sp_move_until = c->frames_done + c->sp_move_parked_n;
-    // gain rides (fwgpu_ctx.h gain_ride_parked_n): the same for a volume / pan node that leaves or returns in mid-ride
-    if (c->frames_done < c->gain_ride_until && c->gain_ride_max_n > c->gain_ride_parked_n) c->gain_ride_parked_n = c->gain_ride_max_n;
-    if (c->gain_ride_parked_n && c->gain_ride_until != ~0ull && c->frames_done + c->gain_ride_parked_n > c->gain_ride_until)
-        c->gain_ride_until = c->frames_done + c->gain_ride_parked_n;
+    // a spatialiser or a volume / pan node may leave the plan here in mid-ramp, or come back in it (fwgpu_ctx.h RampBook::park).  Moves
+    // and rides only: the sweep book is not parked
+    c->moves.park(c->frames_done);
+    c->gain_rides.park(c->frames_done);
     // 1. larger persistent arrays: old contents copied over on the stream, then the pointers change hands
     if (n->grow_states.p) {
         if (c->d_states.p && c->states_cap)

@@ -32,6 +32,10 @@ int fail(fwgpu_ctx* c, int code, const char* msg) {
     set_error(c, msg, nullptr);
     return code;
 }
+int fail(fwgpu_ctx* c, int code, const char* who, const char* what) {
+    set_error(c, who, what);
+    return code;
+}
 int hipfail(fwgpu_ctx* c, hipError_t e, const char* what) {
     set_error(c, what, hipGetErrorString(e));
     return FWGPU_ERR_DEVICE;
@@ -238,11 +242,11 @@ void retire_cmds_node(fwgpu_ctx* c, int slot) {
         if (m.state == slot) {
             if (m.block == 0) {  // applied by this call
                 note_set_sample(c, m);
-                // (a sweep started by ONE node's process call moves only with that node's calls: the frame count of the process calls
-                //  says nothing about it, so from here on every process call of this ctx counts as one that may meet a sweep)
-                if (m.type == CMD_BQ_SWEEP) c->bq_sweep_until = ~0ull;
-                if (m.type == CMD_SP_MOVE) c->sp_move_until = ~0ull;  // (the same for a spatialiser move)
-                if (m.type == CMD_GAIN_RIDE && gr_cmd_frames(m) != 0u) c->gain_ride_until = ~0ull;  // (and for a gain ride)
+                // (RampBook::pin: the ramp this starts moves with this node's calls alone.  Sweeps and moves always pin; a ride step,
+                //  0 frames, is over once applied and pins nothing)
+                if (m.type == CMD_BQ_SWEEP) c->sweeps.pin();
+                if (m.type == CMD_SP_MOVE) c->moves.pin();
+                if (m.type == CMD_GAIN_RIDE && gr_cmd_frames(m) != 0u) c->gain_rides.pin();
                 continue;
             }
             Cmd k = m;
@@ -329,8 +333,8 @@ static void fill_fused_view(fwgpu_ctx* c, FusedView& fv) {
     fv.has_prog = c->fused_prog ? 1 : 0;
     fv.has_rs = c->fused_rs ? 1 : 0;
     fv.has_sp = c->fused_sp ? 1 : 0;
-    fv.sp_moves = c->sp_move_live ? 1 : 0;
-    fv.gain_rides = c->gain_ride_live ? 1 : 0;
+    fv.sp_moves = c->moves.live ? 1 : 0;
+    fv.gain_rides = c->gain_rides.live ? 1 : 0;
     fv.rt_parent_leaf = fv.rt_parent_up = fv.rt_kids = nullptr;
     fv.rt_tree_sync = nullptr;
     fv.rt_root = -1;
@@ -421,40 +425,29 @@ static int run_host_level(fwgpu_ctx* c, const DevView& v, const std::vector<fwgp
     return 0;
 }
 
-// biquad sweeps: raise bq_sweep_until over the sweep messages on the list (kept ones included: their block counts from this call's
-// first frame now) and say whether this call may meet a sweep
-static void note_bq_sweeps(fwgpu_ctx* c) {
-    for (const Cmd& m : c->cmds)
-        if (m.type == CMD_BQ_SWEEP) {
-            const uint64_t end = c->frames_done + (uint64_t)m.block * c->mbf + (uint64_t)bq_cmd_frames(m);
-            if (end > c->bq_sweep_until) c->bq_sweep_until = end;
-        }
-    c->bq_sweep_live = c->frames_done < c->bq_sweep_until;
-}
-// spatialiser moves, the same way: a move that a set_position cuts short leaves the bound standing, which costs kernels, not bits
-static void note_sp_moves(fwgpu_ctx* c) {
-    for (const Cmd& m : c->cmds)
-        if (m.type == CMD_SP_MOVE) {
-            const uint64_t end = c->frames_done + (uint64_t)m.block * c->mbf + (uint64_t)sp_cmd_frames(m);
-            if (end > c->sp_move_until) c->sp_move_until = end;
-            if (sp_cmd_frames(m) > c->sp_move_max_n) c->sp_move_max_n = sp_cmd_frames(m);
-        }
-    c->sp_move_live = c->frames_done < c->sp_move_until;
-    if (!c->sp_move_live) c->sp_move_max_n = 0;
-}
-// gain rides of volume / pan nodes, the same way: a ride that a param 0 cuts short leaves the bound standing, which costs kernels, not
-// bits.  (A step, frames == 0, is a message too: the ride builds are the ones that apply it, for the call that holds it)
-static void note_gain_rides(fwgpu_ctx* c) {
-    bool step = false;
-    for (const Cmd& m : c->cmds)
+// the ramp books: raise each bound over its messages on the list (kept ones included: their block counts from this call's first
+// frame now) and say whether this call may meet a ramp of each kind.  (A ride step, frames == 0, is a message too: the ride builds are
+// the ones that apply it, so it opens the ride book for the call that holds it — and for that call alone)
+static void note_ramps(fwgpu_ctx* c) {
+    bool ride_step = false;
+    for (const Cmd& m : c->cmds) {
+        const uint64_t at = c->frames_done + (uint64_t)m.block * c->mbf;
+        if (m.type == CMD_BQ_SWEEP) c->sweeps.note(at + bq_cmd_frames(m), bq_cmd_frames(m));
+        if (m.type == CMD_SP_MOVE) c->moves.note(at + sp_cmd_frames(m), sp_cmd_frames(m));
         if (m.type == CMD_GAIN_RIDE) {
-            const uint64_t end = c->frames_done + (uint64_t)m.block * c->mbf + (uint64_t)gr_cmd_frames(m);
-            if (end > c->gain_ride_until) c->gain_ride_until = end;
-            if (gr_cmd_frames(m) > c->gain_ride_max_n) c->gain_ride_max_n = gr_cmd_frames(m);
-            if (gr_cmd_frames(m) == 0u) step = true;
+            c->gain_rides.note(at + gr_cmd_frames(m), gr_cmd_frames(m));
+            if (gr_cmd_frames(m) == 0u) ride_step = true;
         }
-    c->gain_ride_live = step || c->frames_done < c->gain_ride_until;
-    if (!c->gain_ride_live) c->gain_ride_max_n = 0;
+    }
+    c->sweeps.settle(c->frames_done, false);
+    c->moves.settle(c->frames_done, false);
+    c->gain_rides.settle(c->frames_done, ride_step);
+}
+// the ramp flags of a view that launch_level reads: no batch walkers in a call that may meet a sweep, the move and ride instantiations
+static void ramp_flags(const fwgpu_ctx* c, DevView& v) {
+    v.no_walkers = c->sweeps.live ? 1 : 0;
+    v.sp_moves = c->moves.live ? 1 : 0;
+    v.gain_rides = c->gain_rides.live ? 1 : 0;
 }
 // K blocks of `frames` frames through the level-batched executor (schedule.rs:289-344 as one launch per level for
 // all K blocks: each block has its own pool slice, a stateful node walks its K blocks in order inside one wave)
@@ -465,9 +458,7 @@ int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const
     DevView v = generic_view(c, frames);
     v.meter_blk0 = c->blocks_done;  // level meters record this batch's blocks
     v.meter_K = (uint32_t)K;
-    v.no_walkers = c->bq_sweep_live ? 1 : 0;
-    v.sp_moves = c->sp_move_live ? 1 : 0;
-    v.gain_rides = c->gain_ride_live ? 1 : 0;
+    ramp_flags(c, v);
     // which gain-like stateful nodes cannot change during this batch (their blocks then run in parallel): decided once,
     // before the first level
     if (K > 1 && c->d_frozen.ensure_n("d_frozen", (size_t)c->plan.nodes.size()) == hipSuccess &&
@@ -502,7 +493,7 @@ int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const
         LCHK(c, launch_voice_control(c->stream, fv, K, cmd_block));
         timer_end(c, e1);
         timer_begin(c, 0, &e0, &e1);
-        if (c->hybrid_fx) LCHK(c, launch_chain(c->stream, fv, K, cmd_block, c->chain_nq | (c->bq_sweep_live ? 16 : 0)));
+        if (c->hybrid_fx) LCHK(c, launch_chain(c->stream, fv, K, cmd_block, c->chain_nq | (c->sweeps.live ? 16 : 0)));
         else LCHK(c, launch_leaf_sum(c->stream, fv, K));
         timer_end(c, e1);
     } else {
@@ -645,17 +636,41 @@ int rt_block_relaunch(fwgpu_ctx* c, float* d_out, unsigned long long seq) {
     return 0;
 }
 
+// a view of nodes that read and write the fused plan's buses (the mixers above the leaves, the master chain): no message list, no frozen
+// table; the master chain adds its own on top
+static DevView bus_view(fwgpu_ctx* c, const FusedView& fv, const DevBuf& nodes, const DevBuf& in, const DevBuf& out) {
+    DevView v;
+    v.nodes = nodes.as<NodeDesc>();
+    v.in_buf = in.as<int>();
+    v.out_buf = out.as<int>();
+    v.states = c->d_states.as<NodeState>();
+    v.samples = c->d_samples.as<SampleDesc>();
+    v.ext = c->d_ext.as<float>();
+    v.rs_table = c->d_rs_table.as<float>();
+    v.pool = fv.bus;
+    v.flags = fv.bus_flags;
+    v.pool_blk_stride = fv.bus_blk_stride;
+    v.flags_blk_stride = fv.bus_flags_blk_stride;
+    v.stride = c->stride;
+    v.frames = (int)c->mbf;
+    v.cmds = nullptr;
+    v.n_cmds = 0;
+    v.frozen = nullptr;
+    v.frozen_playhead = nullptr;
+    return v;
+}
+
 int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int n_out_ch) {
     FusedView fv;
     fill_fused_view(c, fv);
     // realtime edge: one block, tree = leaves + root, stereo stream -> the whole callback is ONE launch (k_rt_block)
     // (a call that may meet a gain ride takes the launch sequence below: k_rt_block and k_rt_persist keep the control code they had;
     //  a resident kernel owns the voice state between two steady callbacks, so it ends first)
-    if (c->gain_ride_live && c->rtp.launched) {
+    if (c->gain_rides.live && c->rtp.launched) {
         const int rc = rt_persist_stop(c);
         if (rc) return rc;
     }
-    if (K == 1 && c->rt_one_launch && !c->gain_ride_live && !c->lazy_this_call && !c->fused_sp &&!c->out_sil && !c->ahead_this_call && !c->fused_fx && !c->timing && c->n_tail == 0 && c->up_root_node >= 0 && n_out_ch == 2 &&
+    if (K == 1 && c->rt_one_launch && !c->gain_rides.live && !c->lazy_this_call && !c->fused_sp &&!c->out_sil && !c->ahead_this_call && !c->fused_fx && !c->timing && c->n_tail == 0 && c->up_root_node >= 0 && n_out_ch == 2 &&
         c->rt_tree_leaves > 0 && c->rt_tree_leaves == c->n_leaves && c->d_rt_sync.p) {
         DevView v;
         rt_root_view(c, fv, v);
@@ -699,14 +714,13 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
             if (rc) return rc;
         }
         c->rt_path[1]++;
+        std::chrono::steady_clock::time_point t0;
+        if (c->host_prof) t0 = std::chrono::steady_clock::now();
+        LCHK(c, launch_rt_block(c->stream, fv, v, c->root_args, d_out, cmd_block0, c->d_rt_sync.as<unsigned>(), flag, c->rt_signal_seq));
         if (c->host_prof) {
-            const auto t0 = std::chrono::steady_clock::now();
-            LCHK(c, launch_rt_block(c->stream, fv, v, c->root_args, d_out, cmd_block0, c->d_rt_sync.as<unsigned>(), flag, c->rt_signal_seq));
             c->hp_launch_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
             c->hp_launches++;
-            return 0;
         }
-        LCHK(c, launch_rt_block(c->stream, fv, v, c->root_args, d_out, cmd_block0, c->d_rt_sync.as<unsigned>(), flag, c->rt_signal_seq));
         return 0;
     }
     if (K == 1) c->rt_path[2]++;
@@ -767,30 +781,13 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
     }
     timer_begin(c, 0, &e0, &e1);
     if (fv.sp_hist_in_render) LCHK(c, launch_sp_hist_copy(c->stream, fv));
-    if (c->fused_fx) LCHK(c, launch_chain(c->stream, fv, K, cmd_block0, c->chain_nq | (c->bq_sweep_live ? 16 : 0)));
+    if (c->fused_fx) LCHK(c, launch_chain(c->stream, fv, K, cmd_block0, c->chain_nq | (c->sweeps.live ? 16 : 0)));
     else if (lazy && !c->fused_rs) LCHK(c, launch_leaf_sum_lazy(c->stream, fv, K));
     else LCHK(c, launch_leaf_sum(c->stream, fv, K));
     timer_end(c, e1);
     timer_begin(c, 2, &e0, &e1);
     if (!c->up_level_cnt.empty()) {
-        DevView v;
-        v.nodes = c->d_up_nodes.as<NodeDesc>();
-        v.in_buf = c->d_up_in.as<int>();
-        v.out_buf = c->d_up_out.as<int>();
-        v.states = c->d_states.as<NodeState>();
-        v.samples = c->d_samples.as<SampleDesc>();
-        v.ext = c->d_ext.as<float>();
-        v.rs_table = c->d_rs_table.as<float>();
-        v.pool = fv.bus;
-        v.flags = fv.bus_flags;
-        v.pool_blk_stride = fv.bus_blk_stride;
-        v.flags_blk_stride = fv.bus_flags_blk_stride;
-        v.stride = c->stride;
-        v.frames = (int)c->mbf;
-        v.cmds = nullptr;
-        v.n_cmds = 0;
-        v.frozen = nullptr;
-        v.frozen_playhead = nullptr;
+        const DevView v = bus_view(c, fv, c->d_up_nodes, c->d_up_in, c->d_up_out);  // (no message, no meter, no ramp reaches a SumNode)
         // the root SumNode is fused with read_graph_outputs + interleave_stereo when the stream is stereo
         const bool fuse_root = c->up_root_node >= 0 && n_out_ch == 2;
         const size_t n_levels = c->up_level_cnt.size() - (fuse_root ? 1 : 0);
@@ -810,29 +807,12 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
         }
     }
     if (c->n_tail) {  // master chain on the mix bus: the generic node kernel, K-batched, one launch per node
-        DevView v;
-        v.nodes = c->d_tail_nodes.as<NodeDesc>();
-        v.in_buf = c->d_tail_in.as<int>();
-        v.out_buf = c->d_tail_out.as<int>();
-        v.states = c->d_states.as<NodeState>();
-        v.samples = c->d_samples.as<SampleDesc>();
-        v.ext = c->d_ext.as<float>();
-        v.rs_table = c->d_rs_table.as<float>();
-        v.pool = fv.bus;
-        v.flags = fv.bus_flags;
-        v.pool_blk_stride = fv.bus_blk_stride;
-        v.flags_blk_stride = fv.bus_flags_blk_stride;
-        v.stride = c->stride;
-        v.frames = (int)c->mbf;
+        DevView v = bus_view(c, fv, c->d_tail_nodes, c->d_tail_in, c->d_tail_out);  // (frozen_playhead stays null: no sampler can sit in a master chain)
         v.cmds = fv.cmds;
         v.n_cmds = fv.n_cmds;
-        v.frozen = nullptr;
-        v.frozen_playhead = nullptr;  // (no sampler can sit in a master chain)
         v.meter_blk0 = c->blocks_done;  // a master meter: one more launch_level below, its K blocks in parallel
         v.meter_K = (uint32_t)K;
-        v.no_walkers = c->bq_sweep_live ? 1 : 0;
-        v.sp_moves = c->sp_move_live ? 1 : 0;
-        v.gain_rides = c->gain_ride_live ? 1 : 0;
+        ramp_flags(c, v);
         if (K > 1) {
             LCHK(c, launch_frozen_scan(c->stream, v, c->n_tail, cmd_block0, K, c->d_tail_frozen.as<uint8_t>(),
                                        c->d_tail_frozen.as<unsigned long long>()));
@@ -888,9 +868,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     // kernel of the call before it cost that kernel 7-15 us of co-residency and the step a ~10 us cross-stream event.
     c->frames_ctl.store(c->frames_done + frames, std::memory_order_release);
     drain_ring(c);
-    note_bq_sweeps(c);
-    note_sp_moves(c);
-    note_gain_rides(c);
+    note_ramps(c);
     const bool hot = c->ctl_ahead_mode == 1 || !c->cmds.empty() || !c->hot_prev.empty();
     // (SPEC streaming sources: no ahead mode while a sampler holds a stream.  The control kernel of call N + 1 would move C beside or
     //  before the render of call N, whose publication — a copy of the live NodeStates behind that render — could then hand the writer a
@@ -906,7 +884,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     c->lazy_this_call = false;
     // (one-block callbacks belong to the realtime kernels, which run their own control)
     if (c->lazy_on && can_fuse && c->lazy_capable && !ahead && !(stable_out && frames == mbf) && !c->rt_use_graph && frames % mbf == 0 && c->cmds.empty() &&
-        c->hot_prev.empty() && !c->bq_sweep_live && !c->sp_move_live && !c->gain_ride_live &&  // (a plan with a sweep, a move or a ride in flight runs its control kernel)
+        c->hot_prev.empty() && !c->ramp_live() &&  // (a plan with a sweep, a move or a ride in flight runs its control kernel)
         c->lazy_valid && c->lazy_epoch == c->epoch && c->h_lazy_pub) {
         const unsigned long long seq = __atomic_load_n(&c->h_lazy_pub[1], __ATOMIC_ACQUIRE);
         const unsigned long long horizon = __atomic_load_n(&c->h_lazy_pub[0], __ATOMIC_RELAXED);
@@ -933,7 +911,7 @@ static int run_blocks_impl(fwgpu_ctx* c, uint64_t frames, const float* d_in, int
     // steady realtime call: no message on the device, one fused batch, the same output block as last time — every
     // kernel argument repeats (block counters and playheads live in device state), so the launch sequence is replayed
     // from a hipGraph instead of being re-issued kernel by kernel
-    if (stable_out && c->rt_use_graph && c->meters.empty() && can_fuse && !c->timing && c->n_cmds_dev == 0 && !c->bq_sweep_live && !c->sp_move_live && !c->gain_ride_live && frames % mbf == 0 &&
+    if (stable_out && c->rt_use_graph && c->meters.empty() && can_fuse && !c->timing && c->n_cmds_dev == 0 && !c->ramp_live() && frames % mbf == 0 &&
         frames / mbf <= (c->fused_fx ? std::min<uint32_t>(c->kmax, CH_FAST_KMAX) : c->kmax)) {
         const uint32_t K = (uint32_t)(frames / mbf);
         fwgpu_ctx::RtGraph& g = c->rt_graph;

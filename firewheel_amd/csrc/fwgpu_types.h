@@ -24,6 +24,7 @@ enum : int {
 #else
 #define FW_TYPES_HD  // (the test harnesses compile the host translation units with plain g++)
 #endif
+#define FW_TYPES_HD_INLINE FW_TYPES_HD inline __attribute__((always_inline))
 // Raw bits in a field of another type — how integers travel in NodeState's float slots and in a message's doubles (the Cmd makers
 // and readers below).  A pair of floats in a double: `lo` in bits 0..31, `hi` in bits 32..63.
 FW_TYPES_HD constexpr uint32_t fw_bits_of(float f) { return __builtin_bit_cast(uint32_t, f); }
@@ -245,6 +246,20 @@ FW_TYPES_HD inline bool comp_state_ok(const NodeState& s, int n_in, int n_out) {
 }
 FW_TYPES_HD inline uint32_t comp_ext_len(const NodeState& s) { return (uint32_t)COMP_TAB_PAD + (uint32_t)((s.loop_end + 1) / 2); }
 
+// A ramp: a value moved from a to b over N frames by one message.  The frame at position u in [0, 1) is a + (d * u),
+// d = b - a (callers hoist it), each a separately rounded f32 operation (-ffp-contract=off).  The clamp: a + d can round one ulp past
+// b, and a curve that overshoots may put u outside [0, 1] — the value stays inside [min(a, b), max(a, b)].  Where u comes from is
+// each feature's own: (k + j) / N for a fade, a sweep (one division for its five coefficients) and a move, the curve's y for a ride.
+FW_TYPES_HD_INLINE float fw_ramp_mix(float a, float b, float d, float u) {
+    const float v = a + (d * u);
+    const float lo = a < b ? a : b, hi = a < b ? b : a;
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+// A 32.32 number moved from `from` to `to` over N frames: the signed increment per frame, truncated toward zero — N steps of it stay
+// between the two ends, and the ramp's last frame is followed by exactly `to`.  Wrapping u64 arithmetic; the signed inc travels as
+// its two's-complement bits.  N != 0
+FW_TYPES_HD_INLINE uint64_t fw_glide_inc(uint64_t from, uint64_t to, uint32_t N) { return (uint64_t)((int64_t)(to - from) / (int64_t)N); }
+
 // K_RESAMPLER ratio glide (SPEC): ONE statement for the node kernels, the control kernel and the leaf kernel.  All in
 // wrapping u64 arithmetic; a signed inc travels as its two's-complement bits.
 #define RS_GLIDE_FRAMES_MAX 16777216u
@@ -258,7 +273,7 @@ FW_TYPES_HD inline void rs_glide_start(NodeState& s, uint64_t S1, uint32_t N) {
         s.full_range = 0;
         return;
     }
-    const uint64_t inc = (uint64_t)((int64_t)(S1 - s.loop_start) / (int64_t)N);  // truncated toward zero
+    const uint64_t inc = fw_glide_inc(s.loop_start, S1, N);
     s.enabled = (int)(uint32_t)inc;
     s.ext_off = (uint32_t)(inc >> 32);
     s.full_range = (int)N;
@@ -313,7 +328,7 @@ FW_TYPES_HD inline int smp_env_then(const NodeState& s) { return (s.enabled >> 2
 FW_TYPES_HD inline bool smp_env_at_rest(const NodeState& s) { return smp_env_N(s) == 0u; }
 // the envelope as a block's render loop reads it: a snapshot taken BEFORE the block's advance, d = E1 - E0 computed once
 struct SmpEnv {
-    float E0, E1, d, lo, hi;
+    float E0, E1, d;
     uint32_t N, k;
 };
 FW_TYPES_HD inline SmpEnv smp_env_of(const NodeState& s) {
@@ -321,18 +336,15 @@ FW_TYPES_HD inline SmpEnv smp_env_of(const NodeState& s) {
     e.E0 = s.phasor;
     e.E1 = s.gain;
     e.d = e.E1 - e.E0;
-    e.lo = e.E0 < e.E1 ? e.E0 : e.E1;
-    e.hi = e.E0 < e.E1 ? e.E1 : e.E0;
     e.N = smp_env_N(s);
     e.k = (uint32_t)s.s1.status;
     return e;
 }
-// env(j): the value of the frame j frames ahead of the snapshot's position (the clamp: E0 + d can round one ulp past E1)
+// env(j): the value of the frame j frames ahead of the snapshot's position
 FW_TYPES_HD inline float smp_env_value(const SmpEnv& e, uint32_t j) {
     const uint32_t t = e.k + j;
     if (e.N == 0u || t >= e.N) return e.E1;
-    const float v = e.E0 + (e.d * ((float)t / (float)e.N));
-    return v < e.lo ? e.lo : (v > e.hi ? e.hi : v);
+    return fw_ramp_mix(e.E0, e.E1, e.d, (float)t / (float)e.N);
 }
 FW_TYPES_HD inline void smp_env_reset(NodeState& s) {  // the envelope is a transient: at rest at 1.0f, then = NONE
     s.gain = 1.0f;
@@ -531,15 +543,10 @@ FW_TYPES_HD inline void bq_sweep_put(NodeState& s, const BqSweep& w) {
 // the sweep's position j frames ahead, (float)(k + j) / (float)N — one division serves a frame's five coefficients; only for k + j < N
 FW_TYPES_HD inline float bq_sweep_pos(const BqSweep& w, uint32_t j) { return (float)(w.k + j) / (float)w.N; }
 // c_i(j): coefficient i (a compile-time index wherever a kernel calls this) of the frame j frames ahead; `rest` = the ext head's value
-// (the clamp: A + d can round one ulp past T)
 FW_TYPES_HD inline float bq_sweep_coef(const BqSweep& w, int i, uint32_t j, float rest) {
     if (w.N == 0u) return rest;
     if (w.k + j >= w.N) return w.T[i];
-    const float a = w.A[i], t = w.T[i];
-    const float d = t - a;
-    const float v = a + (d * bq_sweep_pos(w, j));
-    const float lo = a < t ? a : t, hi = a < t ? t : a;
-    return v < lo ? lo : (v > hi ? hi : v);
+    return fw_ramp_mix(w.A[i], w.T[i], w.T[i] - w.A[i], bq_sweep_pos(w, j));
 }
 // the message, applied at a block's first frame: N frames from where the coefficients stand (head: the ext slice's five) to T.
 // frames == 0 is a step: the caller writes T to the ext head (CMD_SET_COEFS does the same); so is frames > BQ_SWEEP_FRAMES_MAX, which
@@ -605,14 +612,11 @@ FW_TYPES_HD inline SpMove sp_move_of(const NodeState& s) {
     }
     return m;
 }
-// the gain of ear e, j frames ahead of the snapshot (the clamp: G0 + d can round one ulp past G1); behind the move, and at rest: G1
+// the gain of ear e, j frames ahead of the snapshot; behind the move, and at rest: G1
 FW_TYPES_HD inline float sp_move_gain(const SpMove& m, int e, uint32_t j) {
     const uint32_t t = m.k + j;
     if (t >= m.N) return m.G1[e];
-    const float a = m.G0[e], b = m.G1[e];
-    const float v = a + ((b - a) * ((float)t / (float)m.N));
-    const float lo = a < b ? a : b, hi = a < b ? b : a;
-    return v < lo ? lo : (v > hi ? hi : v);
+    return fw_ramp_mix(m.G0[e], m.G1[e], m.G1[e] - m.G0[e], (float)t / (float)m.N);
 }
 // the 32.32 delay of ear e, j frames ahead of the snapshot; behind the move exactly d1 << 32
 FW_TYPES_HD inline uint64_t sp_move_delay(const SpMove& m, int e, uint32_t j) {
@@ -657,8 +661,7 @@ FW_TYPES_HD inline void sp_move_start(NodeState& s, float G1l, float G1r, int d1
         s.full_range = 0;
         return;
     }
-    const uint64_t il = (uint64_t)((int64_t)(((uint64_t)tl << 32) - m.D[0]) / (int64_t)N);  // truncated toward zero
-    const uint64_t ir = (uint64_t)((int64_t)(((uint64_t)tr << 32) - m.D[1]) / (int64_t)N);
+    const uint64_t il = fw_glide_inc(m.D[0], (uint64_t)tl << 32, N), ir = fw_glide_inc(m.D[1], (uint64_t)tr << 32, N);
     s.phasor = G0l;
     s.phasor_inc = G0r;
     s.playhead = m.D[0];
@@ -695,7 +698,6 @@ FW_TYPES_HD inline void sp_move_advance(NodeState& s, uint32_t frames) {
 #define FW_TYPES_UNROLL
 #define FW_TYPES_ROLLED
 #endif
-#define FW_TYPES_HD_INLINE FW_TYPES_HD inline __attribute__((always_inline))
 struct XfCubic {
     float q, b, c;
 };
@@ -755,7 +757,7 @@ FW_TYPES_HD_INLINE GainRide gain_ride_of(const NodeState& s) {
     return r;
 }
 // ride_c(j) .. ride_c(j + W - 1), the gains of W consecutive frames from j frames ahead of the snapshot: behind the ride, and at rest,
-// G1; the clamp keeps an overshooting curve (and G0 + d rounding one ulp past G1) inside [min(G0, G1), max(G0, G1)]
+// G1; fw_ramp_mix's clamp keeps an overshooting curve inside [min(G0, G1), max(G0, G1)]
 template <int W>
 FW_TYPES_HD_INLINE void gain_ride_values(const GainRide& r, int c, uint32_t j, float (&g)[W]) {
     FW_TYPES_UNROLL
@@ -767,14 +769,9 @@ FW_TYPES_HD_INLINE void gain_ride_values(const GainRide& r, int c, uint32_t j, f
     FW_TYPES_UNROLL
     for (int e = 0; e < W; ++e) u[e] = (float)((uint32_t)t0 + (uint32_t)e) / fN;
     fw_curve_y<W>(r.shape, r.x1, r.y1, r.x2, r.y2, u, y);
-    const float a = r.G0[c], b = r.G1[c];
-    const float lo = a < b ? a : b, hi = a < b ? b : a;
     FW_TYPES_UNROLL
     for (int e = 0; e < W; ++e)
-        if (t0 + (uint64_t)e < (uint64_t)r.N) {  // (the ride may end among the W frames)
-            const float v = a + (r.d[c] * y[e]);
-            g[e] = v < lo ? lo : (v > hi ? hi : v);
-        }
+        if (t0 + (uint64_t)e < (uint64_t)r.N) g[e] = fw_ramp_mix(r.G0[c], r.G1[c], r.d[c], y[e]);  // (the ride may end among the W frames)
 }
 FW_TYPES_HD inline float gain_ride_value(const GainRide& r, int c, uint32_t j) {
     float g[1];

@@ -207,7 +207,7 @@ __device__ __forceinline__ void chain_sweep_recur(float* row, const ChSweep& z, 
 // SITES: some voice of the plan has a gain stage BETWEEN two filters or a hard clip (the instantiation with the five-site stage logic; the
 // other one knows "in front of the first filter" and "behind the last", multiplications only, and keeps its registers: the site tables cost
 // the one-biquad kernel 28 bytes of scratch per lane when they were unconditional)
-// SWEEP: the instantiation for a call that may meet a biquad coefficient sweep (the host knows: fwgpu_run.cpp note_bq_sweeps) — per-frame
+// SWEEP: the instantiation for a call that may meet a biquad coefficient sweep (the host knows: fwgpu_run.cpp note_ramps) — per-frame
 // coefficients in S1 / S1b (frame-parallel) and in S2 / S2b, the general loop only; the steady instantiations have none of it
 template <int NQ, bool BQ2, bool SITES, bool SWEEP = false>
 __global__ __launch_bounds__(CH_THREADS) void k_chain(FusedView fv, int K, uint32_t cmd_block0) {

@@ -196,8 +196,6 @@ __device__ __attribute__((noinline)) void env_rows(float* row0, float* row1, con
     e.E0 = E0;
     e.E1 = E1;
     e.d = E1 - E0;
-    e.lo = E0 < E1 ? E0 : E1;
-    e.hi = E0 < E1 ? E1 : E0;
     e.N = N;
     e.k = k;
     if (had_ramp) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");

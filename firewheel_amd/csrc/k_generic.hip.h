@@ -1149,7 +1149,7 @@ __device__ __forceinline__ bool biquad_walk_ok(const DevView& v, const NodeDesc&
     if (nd.kind != K_BIQUAD || nch < 1 || nch > 2 || K < 2 || (v.frames & 255)) return false;  // mono / stereo, whole 256-frame chunks
     // a coefficient sweep in flight goes block by block through node_process_wave (a sweep MESSAGE in the batch is a message: below).
     // (k_level<1> and k_bus_iir must decide alike, and the first changes this state: the host launches no walkers while a sweep may be
-    //  in flight — fwgpu_run.cpp bq_sweep_live — so this line guards, it does not dispatch)
+    //  in flight — fwgpu_ctx.h sweeps.live — so this line guards, it does not dispatch)
     if (!bq_sweep_at_rest(v.states[nd.state])) return false;
     if (v.n_cmds) {
         const int c = chain_cmd_lower_bound(v.cmds, v.n_cmds, nd.state, cmd_block0);

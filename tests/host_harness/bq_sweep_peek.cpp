@@ -3,11 +3,11 @@
 // the host, for the numpy model to be held against.
 #include "early_peek.h"
 
-// the host's count of frames and of the frame behind which no sweep is in flight (fwgpu_run.cpp note_bq_sweeps)
+// the host's count of frames and of the frame behind which no sweep is in flight (fwgpu_ctx.h RampBook, fwgpu_run.cpp note_ramps)
 extern "C" void bsp_sweep_book(const fwgpu_ctx* c, unsigned long long* out) {
     out[0] = c->frames_done;
-    out[1] = c->bq_sweep_until;
-    out[2] = c->bq_sweep_live ? 1ull : 0ull;
+    out[1] = c->sweeps.until;
+    out[2] = c->sweeps.live ? 1ull : 0ull;
 }
 
 // st = {A[5], T[5] (bits), N, k}; head = the five at the head of the ext slice (bits)

@@ -3,14 +3,14 @@
 // the host, for the numpy model to be held against.  A state is a caller-owned NodeState record (128 bytes).
 #include "early_peek.h"
 
-// the host's count of frames, the frame behind which no ride is in flight (fwgpu_run.cpp note_gain_rides), whether the call just
+// the host's count of frames, the frame behind which no ride is in flight (fwgpu_ctx.h RampBook, fwgpu_run.cpp note_ramps), whether the call just
 // rendered could meet one, and the two parked-node figures
 extern "C" void grp_ride_book(const fwgpu_ctx* c, unsigned long long* out) {
     out[0] = c->frames_done;
-    out[1] = c->gain_ride_until;
-    out[2] = c->gain_ride_live ? 1ull : 0ull;
-    out[3] = c->gain_ride_max_n;
-    out[4] = c->gain_ride_parked_n;
+    out[1] = c->gain_rides.until;
+    out[2] = c->gain_rides.live ? 1ull : 0ull;
+    out[3] = c->gain_rides.max_n;
+    out[4] = c->gain_rides.parked_n;
 }
 extern "C" unsigned grp_state_bytes() { return (unsigned)sizeof(fwgpu::NodeState); }
 static float grp_f(unsigned bits) {

@@ -3,11 +3,11 @@
 // the host, for the numpy model to be held against.  A state is a caller-owned NodeState record (128 bytes).
 #include "early_peek.h"
 
-// the host's count of frames and of the frame behind which no move is in flight (fwgpu_run.cpp note_sp_moves)
+// the host's count of frames and of the frame behind which no move is in flight (fwgpu_ctx.h RampBook, fwgpu_run.cpp note_ramps)
 extern "C" void spp_move_book(const fwgpu_ctx* c, unsigned long long* out) {
     out[0] = c->frames_done;
-    out[1] = c->sp_move_until;
-    out[2] = c->sp_move_live ? 1ull : 0ull;
+    out[1] = c->moves.until;
+    out[2] = c->moves.live ? 1ull : 0ull;
 }
 extern "C" unsigned spp_state_bytes() { return (unsigned)sizeof(fwgpu::NodeState); }
 static float spp_f(unsigned bits) {
