@@ -148,6 +148,8 @@ SIGNATURES = {
     "fwgpu_bus_exchange_wait_stats": (ci, [vp, C.POINTER(u64), u32, ci]),
     "fwgpu_synchronize": (ci, [vp]),
     "fwgpu_meter_read": (i64, [vp, i64, u64, u32, C.POINTER(MeterReading), C.POINTER(u64)]),
+    "fwgpu_spectrum_read": (i64, [vp, i64, u64, u32, fp, C.POINTER(u64)]),
+    "fwgpu_spectrum_layout": (ci, [vp, i64, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32]),
     "fwgpu_node_latency": (ci, [vp, i64, C.POINTER(u32)]),
     "fwgpu_graph_latency_report": (i64, [vp, C.POINTER(LatencySkew), u32]),
     "fwgpu_graph_output_latency": (ci, [vp, C.POINTER(u32)]),

@@ -1821,6 +1821,53 @@ int64_t fwgpu_meter_read(fwgpu_ctx* c, int64_t node, uint64_t first_block, uint3
     if (n) HIPC(c, hipStreamSynchronize(c->stream));
     return (int64_t)n;
 }
+// Spectrum meters (a K_METER created with two or more parameters): the same call for the node's second ring, out[(i * n_in + c) * B + b]
+int64_t fwgpu_spectrum_read(fwgpu_ctx* c, int64_t node, uint64_t first_block, uint32_t num_blocks, float* out, uint64_t* blocks_done) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    AudioCallScope audio;
+    use_device(c);
+    AudioGate gate(c);
+    const uint64_t done = c->blocks_done;
+    if (blocks_done) *blocks_done = done;
+    HIPC(c, hipStreamSynchronize(c->stream));
+    const PlanImage::Meter* m = nullptr;
+    if (c->have_plan)
+        for (const PlanImage::Meter& x : c->meters)
+            if (x.id == node && x.fft) m = &x;
+    if (!m) return fail(c, FWGPU_ERR_INVALID, "not a spectrum meter node of the installed plan");
+    if (num_blocks == 0) return 0;
+    if (!out) return fail(c, FWGPU_ERR_INVALID, "spectrum_read: null output with blocks requested");
+    if (first_block + (uint64_t)m->ring < done) return fail(c, FWGPU_ERR_INVALID, "spectrum_read: first_block is older than the ring retains");
+    if (first_block < m->first_block) return fail(c, FWGPU_ERR_INVALID, "spectrum_read: first_block is older than the meter's first plan");
+    const uint64_t exist = done > first_block ? done - first_block : 0;
+    const uint32_t n = (uint32_t)std::min<uint64_t>(num_blocks, exist);  // (<= ring: first_block + ring >= done)
+    const float* ring = c->d_ext.as<float>() + m->spec_off;
+    const size_t blk = (size_t)m->n_in * m->rec;  // floats of one block's records
+    const uint32_t s0 = (uint32_t)(first_block % m->ring);
+    const uint32_t n0 = std::min<uint32_t>(n, m->ring - s0);
+    if (n0) HIPC(c, hipMemcpyAsync(out, ring + (size_t)s0 * blk, (size_t)n0 * blk * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (n > n0) HIPC(c, hipMemcpyAsync(out + (size_t)n0 * blk, ring, (size_t)(n - n0) * blk * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (n) HIPC(c, hipStreamSynchronize(c->stream));
+    return (int64_t)n;
+}
+int fwgpu_spectrum_layout(fwgpu_ctx* c, int64_t node, uint32_t* fft_size, uint32_t* bands, uint32_t* edges, uint32_t edges_cap) {
+    NEED_CTX(c, FWGPU_ERR_INVALID);
+    AudioCallScope audio;
+    AudioGate gate(c);
+    const PlanImage::Meter* m = nullptr;
+    if (c->have_plan)
+        for (const PlanImage::Meter& x : c->meters)
+            if (x.id == node && x.fft) m = &x;
+    if (!m) return fail(c, FWGPU_ERR_INVALID, "not a spectrum meter node of the installed plan");
+    if (fft_size) *fft_size = m->fft;
+    if (bands) *bands = m->bands;
+    if (edges && edges_cap) {
+        std::vector<uint32_t> e((size_t)m->rec + 1);
+        spectrum_edges(m->fft, m->bands, e.data());
+        for (uint32_t b = 0; b < edges_cap && b <= m->rec; ++b) edges[b] = e[b];
+    }
+    return (int)m->rec;
+}
 
 int fwgpu_node_process(fwgpu_ctx* c, int64_t node, uint64_t frames, const float* const* inputs, uint32_t n_in,
                        float* const* outputs, uint32_t n_out, uint64_t in_mask, uint64_t* out_mask, double, uint32_t) {

@@ -136,6 +136,34 @@ void compressor_table(float ratio, float knee_db, float G[COMP_TAB_PAD]) {
         G[i] = (float)pow(10.0, gr / 20.0);
     }
 }
+// SPEC spectrum meter: the band edges e[0..B] over the bins of an N-point transform; bands == 0: every bin, DC included
+void spectrum_edges(uint32_t N, uint32_t bands, uint32_t* e) {
+    const int M = (int)(N / 2), B = (int)bands;
+    if (B == 0) {
+        for (int b = 0; b <= M + 1; ++b) e[b] = (uint32_t)b;
+        return;
+    }
+    e[0] = 1;
+    for (int b = 1; b < B; ++b) {
+        const int want = (int)floor(pow((double)M, (double)b / B) + 0.5), cap = M + 1 - (B - b);
+        const int lo = (int)e[b - 1] + 1, v = cap < want ? cap : want;
+        e[b] = (uint32_t)(lo > v ? lo : v);
+    }
+    e[B] = (uint32_t)(M + 1);
+}
+// ... and the slice's head (fwgpu_types.h spec_head_len floats): the periodic Hann window w[N], the twiddles wr[N/2] wi[N/2], the edges
+// as raw 32-bit words, zeros up to the head's length
+void spectrum_tables(const NodeState& s, float* head) {
+    const uint32_t N = (uint32_t)s.loop_start, B = (uint32_t)s.playing;
+    for (uint32_t i = 0; i < N; ++i) head[i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * i / N));
+    for (uint32_t k = 0; k < N / 2; ++k) {
+        head[N + k] = (float)cos(2.0 * M_PI * k / N);
+        head[N + N / 2 + k] = (float)(-sin(2.0 * M_PI * k / N));
+    }
+    std::vector<uint32_t> e(B + 1);
+    spectrum_edges(N, (uint32_t)s.full_range, e.data());
+    for (uint32_t b = 0; b < spec_head_len(s) - 2 * N; ++b) head[2 * N + b] = fw_float_of(b <= B ? e[b] : 0u);
+}
 uint32_t delay_frames(float secs, uint32_t sample_rate) {
     double d = round((double)secs * (double)sample_rate);
     if (!(d >= 1.0)) d = 1.0;
@@ -239,6 +267,18 @@ NodeState make_state(int kind, const float* params, int n_params, uint32_t sampl
             const float r = p(0, (float)METER_RING_DEFAULT);
             // anything else — NaN, a fraction, out of range — leaves 0 here, and the node fails activation at the next update
             s.loop_end = (r >= 1.0f && r <= (float)METER_RING_MAX && r == floorf(r)) ? (uint64_t)r : 0;
+            if (n_params >= 2) {  // SPEC spectrum meter (fwgpu_types.h spec_*): ring_blocks, fft_size, bands
+                const float n = p(1, 0.0f), b = p(2, (float)SPEC_BANDS_DEFAULT);
+                const bool pow2 = n == 256.0f || n == 512.0f || n == 1024.0f || n == 2048.0f || n == 4096.0f;
+                if (s.loop_end != 0 && pow2 && b >= 0.0f && b <= n / 2.0f && b == floorf(b)) {
+                    s.loop_start = (uint64_t)n;
+                    s.full_range = (int)b;
+                    s.playing = b == 0.0f ? (int)n / 2 + 1 : (int)b;
+                } else {  // (loop_start says whose message the refusal gets)
+                    s.loop_end = 0;
+                    s.loop_start = 1;
+                }
+            }
             break;
         }
         case K_LIMITER: {  // params: ceiling (linear, 0.001..1000, default 1.0), hold_frames (0..1920, default 128)

@@ -301,8 +301,16 @@ struct PlanImage {
         int64_t id = 0;
         uint32_t n_in = 0, ring = 0, ext_off = 0;
         uint64_t first_block = 0;
+        // a spectrum meter (fft != 0; fwgpu_spectrum_read / fwgpu_spectrum_layout): N, the `bands` parameter, the floats of one record
+        // and where the spectrum ring [ring][n_in][rec] lies in the ext pool
+        uint32_t fft = 0, bands = 0, rec = 0, spec_off = 0;
     };
     std::vector<Meter> meters;
+    bool has_spectra() const {
+        for (const Meter& m : meters)
+            if (m.fft) return true;
+        return false;
+    }
 
     // the steady realtime launch sequence of THIS plan kept as a hipGraph (FWGPU_RT_GRAPH=1)
     struct RtGraph {
@@ -661,6 +669,8 @@ Smoother make_smoother(float val, uint32_t sample_rate);
 void biquad_coefs(int type, float cutoff_hz, float q, uint32_t sample_rate, float co[5]);
 float compressor_knee_start(float threshold, float knee_db);               // T0 (SPEC compressor)
 void compressor_table(float ratio, float knee_db, float G[COMP_TAB_PAD]);  // G[0..COMP_TAB_N), zeros behind it
+void spectrum_edges(uint32_t N, uint32_t bands, uint32_t* e);  // e[0..B], B = bands or N/2 + 1 (SPEC spectrum meter)
+void spectrum_tables(const NodeState& s, float* head);          // window, twiddles, edges: spec_head_len(s) floats
 void resampler_table(float* h);
 uint64_t resampler_step(float ratio);
 void spatial_params(float x, float y, float z, uint32_t sample_rate, float* gl, float* gr, int* dl, int* dr);

@@ -7,6 +7,7 @@
 //   k_delay_comp.hip.h SPEC latency compensation: k_delay_comp — a pure delay of whole frames, a copy; every block of a batch in parallel
 //   k_ducker.hip.h   SPEC sidechain ducker: k_ducker — window counts over the key bus's gate bits, runs of blocks in parallel
 //   k_compressor.hip.h SPEC bus compressor: k_compressor — a table curve and window sums of the gain target, runs of blocks in parallel
+//   k_spectrum.hip.h SPEC spectrum meter: k_spectrum — a windowed FFT per (block, channel) of a meter in LDS, every block of a batch in parallel
 //   k_single.hip.h   k_single_node — one node of any kind on scratch buffers (behind the four above: it calls into each)
 //   k_control.hip.h  fused plans, control half: k_voice_control (per-voice per-block state machines, K blocks per launch)
 //   k_leaf.hip.h     fused voice-bank plan: k_leaf_sum (HBM-streaming source fetch + gain stages + ordered radix-P sum
@@ -42,6 +43,7 @@ __device__ __forceinline__ v4f splat(float x) { return (v4f){x, x, x, x}; }
 #include "k_delay_comp.hip.h"
 #include "k_ducker.hip.h"
 #include "k_compressor.hip.h"
+#include "k_spectrum.hip.h"
 #include "k_single.hip.h"
 #include "k_control.hip.h"
 #include "k_leaf.hip.h"
@@ -102,6 +104,13 @@ int launch_level(hipStream_t s, const DevView& v, const int* d_level_nodes, int 
         const int own_hist = K == 1 && pieces == 1 ? 1 : 0;
         hipLaunchKernelGGL(k_compressor, dim3(n_nodes, K * pieces), dim3(COMP_THREADS), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K, own_hist);
         if (!own_hist) hipLaunchKernelGGL(k_compressor_hist, dim3(n_nodes), dim3(COMP_THREADS), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K);
+    }
+    // a spectrum meter — behind k_level<0>, which renders the level meter it also is: a workgroup per (node, block, channel); behind it,
+    // unless the launch is one block, the workgroup per node that writes the window history back (stream order)
+    if ((kinds & LB_SET0) && v.spectra && v.meter_K) {
+        const int own_hist = K == 1 ? 1 : 0;
+        hipLaunchKernelGGL(k_spectrum, dim3(n_nodes, K, SPEC_CH_MAX), dim3(SPEC_THREADS), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K, own_hist);
+        if (!own_hist) hipLaunchKernelGGL(k_spectrum_hist, dim3(n_nodes), dim3(SPEC_THREADS), 0, s, v, d_level_nodes, n_nodes, (uint32_t)K);
     }
     if (walkers)
         hipLaunchKernelGGL(k_bus_iir, dim3((n_nodes + WPB - 1) / WPB), dim3(WAVE * WPB), 0, s, v, d_level_nodes, n_nodes, cmd_block0, (uint32_t)K);

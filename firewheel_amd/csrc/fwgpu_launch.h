@@ -27,6 +27,9 @@ struct DevView {
     int frames;  // frames in this block (<= max_block_frames)
     const Cmd* cmds;
     int n_cmds;
+    // 1: the installed plan holds a spectrum meter (SPEC) — launch_level runs k_spectrum behind a level with a set-0 node
+    // while meter_K != 0.  (In the padding behind n_cmds: every other field keeps its offset)
+    int spectra = 0;
     // per node of `nodes` (or nullptr): 1 = a gain-like stateful node whose control state cannot move during this
     // batch — k_level then runs its blocks in parallel (k_frozen_scan, launched once per batch before the levels)
     const uint8_t* frozen;

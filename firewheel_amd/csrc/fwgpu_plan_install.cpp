@@ -594,6 +594,8 @@ static int activate_nodes(ImageBuild& b) {
         size_t len = 0;
         std::vector<float> head;
         uint32_t head_pad = 0;  // floats at the slice's start that `head` fills whole, eight to a job: the zeroing job starts behind them
+        uint32_t head_off = 0;  // where a padded head starts in the slice (a spectrum meter's tables lie behind its level ring); with
+                                // head_off != 0 both it and head_pad are multiples of 64
         uint64_t fir_R = 0;     // a morph-capable FIR node: its ring length, for the place of its block records in the slice
         if (n.kind == K_BIQUAD) {
             len = 5 + 4 * (size_t)nch + BQ_SNAP_LEN;  // (behind the channels' state: a sweep as the chain plan's call found it)
@@ -605,8 +607,23 @@ static int activate_nodes(ImageBuild& b) {
             len = SP_HIST;
         } else if (n.kind == K_METER) {  // ring[R][n_in] of 16-byte records, zeroed like every slice
             if (n.init.loop_end < 1 || n.init.loop_end > METER_RING_MAX)
-                return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "MeterNode: ring_blocks must be a whole number in 1..65536");
+                return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED,
+                            spec_on(n.init) ? "MeterNode: ring_blocks must be a whole number in 1..65536, fft_size one of 256, 512, 1024, 2048, 4096, "
+                                              "bands a whole number in 0..fft_size/2"
+                                            : "MeterNode: ring_blocks must be a whole number in 1..65536");
             len = (size_t)n.init.loop_end * (size_t)n.n_in * (sizeof(MeterRec) / sizeof(float));
+            if (spec_on(n.init)) {  // SPEC spectrum meter: the level ring, then tables, history and the spectrum ring (fwgpu_types.h spec_*)
+                if (!spec_state_ok(n.init, (int)n.n_in, (int)n.n_out))
+                    return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED,
+                                "MeterNode: a spectrum meter has 1..8 inputs and a spectrum ring (ring_blocks x inputs x bands) of at most 2^24 floats");
+                len = spec_ext_len(n.init, (int)n.n_in);
+                head.resize(spec_head_len(n.init));
+                spectrum_tables(n.init, head.data());
+                head_off = spec_win_rel(n.init, (int)n.n_in);
+                head_pad = (uint32_t)head.size();
+                if (b.ext_jobs.size() + head.size() / 8 > 60000)  // (one job per eight floats, one row of k_adopt_init's grid per job)
+                    return fail(c, FWGPU_ERR_NODE_ACTIVATION_FAILED, "MeterNode: too many spectrum meters activated by one update");
+            }
         } else if (n.kind == K_LIMITER) {  // hist[n_in][HK], zeroed like every slice: zeros are the SPEC's x[n < 0]
             // (this and the next two: fwgpu_types.h X_state_ok / X_ext_len, which the device guards share.  The predicate asks more than
             //  the range of loop_end that marks a refused parameter; make_state fills nothing that range lets through and the predicate
@@ -688,15 +705,21 @@ static int activate_nodes(ImageBuild& b) {
                 if (!fir_morph_state_ok(si.st, (int)n.n_in, (int)n.n_out)) return fail(c, FWGPU_ERR_INVALID, "FirReverbNode: not a state the morph kernels render");
             }
             AdoptExtJobHost j{};
-            j.off = off + head_pad;
-            j.zero_len = b.ext_need == before ? (uint32_t)((len + 63) / 64 * 64) - head_pad : 0u;  // (a bumped slice is zero already)
+            j.off = off + head_off + head_pad;
+            j.zero_len = b.ext_need == before ? (uint32_t)((len + 63) / 64 * 64) - head_off - head_pad : 0u;  // (a bumped slice is zero already)
             j.n_head = head_pad ? 0u : (uint32_t)std::min<size_t>(head.size(), 8);
             for (uint32_t k = 0; k < j.n_head; ++k) j.head[k] = head[k];
             if (j.zero_len || j.n_head) b.ext_jobs.push_back(j);
+            if (head_off && b.ext_need == before) {  // the part of a recycled slice in front of the head
+                AdoptExtJobHost z{};
+                z.off = off;
+                z.zero_len = head_off;
+                b.ext_jobs.push_back(z);
+            }
             // a head longer than one job's eight floats (the compressor's table): jobs of their own, so that no two jobs write one float
             for (uint32_t h0 = 0; h0 < head_pad; h0 += 8) {
                 AdoptExtJobHost t{};
-                t.off = off + h0;
+                t.off = off + head_off + h0;
                 t.n_head = 8;
                 for (uint32_t k = 0; k < 8; ++k) t.head[k] = head[h0 + k];
                 b.ext_jobs.push_back(t);
@@ -1245,6 +1268,13 @@ static int size_generic_scratch(ImageBuild& b) {
         if (plan.nodes[i].kind == K_METER) {
             const NodeState st = b.node_init(plan.nodes[i].slot);
             P.meters.push_back({c->graph.id_of(plan.nodes[i].slot), (uint32_t)plan.nodes[i].n_in, (uint32_t)st.loop_end, st.ext_off, 0});
+            if (spec_on(st)) {
+                PlanImage::Meter& m = P.meters.back();
+                m.fft = (uint32_t)st.loop_start;
+                m.bands = (uint32_t)st.full_range;
+                m.rec = (uint32_t)st.playing;
+                m.spec_off = st.ext_off + spec_ring_rel(st, plan.nodes[i].n_in);
+            }
         }
     return 0;
 }

@@ -458,6 +458,7 @@ int run_generic_batch(fwgpu_ctx* c, int K, int frames, uint32_t cmd_block, const
     DevView v = generic_view(c, frames);
     v.meter_blk0 = c->blocks_done;  // level meters record this batch's blocks
     v.meter_K = (uint32_t)K;
+    v.spectra = c->has_spectra() ? 1 : 0;
     ramp_flags(c, v);
     // which gain-like stateful nodes cannot change during this batch (their blocks then run in parallel): decided once,
     // before the first level
@@ -812,6 +813,7 @@ int run_fused_batch(fwgpu_ctx* c, int K, uint32_t cmd_block0, float* d_out, int 
         v.n_cmds = fv.n_cmds;
         v.meter_blk0 = c->blocks_done;  // a master meter: one more launch_level below, its K blocks in parallel
         v.meter_K = (uint32_t)K;
+        v.spectra = c->has_spectra() ? 1 : 0;
         ramp_flags(c, v);
         if (K > 1) {
             LCHK(c, launch_frozen_scan(c->stream, v, c->n_tail, cmd_block0, K, c->d_tail_frozen.as<uint8_t>(),

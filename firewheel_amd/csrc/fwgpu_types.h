@@ -113,6 +113,15 @@ struct MeterRec {
 static_assert(sizeof(MeterRec) == 16, "MeterRec layout");
 #define METER_RING_DEFAULT 1024u
 #define METER_RING_MAX 65536u
+// K_METER, spectrum meter (SPEC): a meter created with two or more parameters also records, per (block, input channel),
+// the band powers of a Hann-windowed radix-2 FFT over the channel's last N frames.  N is a power of two in SPEC_FFT_MIN..SPEC_FFT_MAX,
+// `bands` 0 (every bin, DC included: N/2 + 1 values per record) or 1..N/2 (log-spaced bands over bins 1..N/2), at most SPEC_CH_MAX
+// channels, and the spectrum ring holds at most SPEC_RING_FLOATS_MAX floats (the largest plain meter ring).
+#define SPEC_FFT_MIN 256u
+#define SPEC_FFT_MAX 4096u
+#define SPEC_CH_MAX 8
+#define SPEC_BANDS_DEFAULT 32u
+#define SPEC_RING_FLOATS_MAX 16777216u
 #define RS_PHASES 32  // SPEC resampler: polyphase windowed-sinc table [RS_PHASES][RS_TAPS], 32.32 fixed-point position
 #define RS_TAPS 16
 // realtime edge, resident kernel (k_rt_persist): the mailbox in pinned, device-mapped host memory
@@ -194,7 +203,8 @@ struct NodeState {
     //        ride p0 / p1 and both smoothers rest at the targets G1_0 / G1_1 (a volume's p1 and s1 stay at 0, as make_state leaves
     //        them): the ride's end only clears these seven fields, back to make_state's zeros.  No other message reaches them; a
     //        node's state keeps its slot over a plan install.  The arithmetic is gain_ride_* below the struct
-    //   METER: ext = ring[R][n_in] of MeterRec (4 floats each), loop_end = R (0: the creation parameter was refused)
+    //   METER: ext = ring[R][n_in] of MeterRec (4 floats each), loop_end = R (0: the creation parameter was refused); a spectrum meter
+    //        also has loop_start = N, full_range = bands, playing = B and a longer slice: spec_state_ok / spec_ext_len below the struct
     //   LIMITER, DUCKER, DELAY_COMP, COMPRESSOR: loop_end = 0 marks a creation parameter that was refused; the valid states and the
     //        slice lengths are lim_/duck_/dcomp_/comp_state_ok and _ext_len below the struct
     //   LIMITER: p0 = ceiling C, loop_start = hold_frames H, loop_end = HK; ext = hist[n_in][HK]: the last HK input frames per channel,
@@ -245,6 +255,29 @@ FW_TYPES_HD inline bool comp_state_ok(const NodeState& s, int n_in, int n_out) {
            W == (A > R ? A : R) + (uint64_t)H && n_in == n_out && n_in >= 1 && n_in <= COMP_CH_MAX && s.p0 > 0.0f && s.p1 > 0.0f;
 }
 FW_TYPES_HD inline uint32_t comp_ext_len(const NodeState& s) { return (uint32_t)COMP_TAB_PAD + (uint32_t)((s.loop_end + 1) / 2); }
+// K_METER, spectrum meter: loop_end = R as for every meter, loop_start = N (0: a plain meter, whose state and slice are what they
+// were), full_range = the `bands` parameter, playing = B, the floats of one record (bands, or N/2 + 1 when bands == 0).  The slice, every
+// part at a multiple of 64 floats: the level ring a plain meter has (k_level and fwgpu_meter_read find it at ext_off, as ever), the window
+// w[N], the twiddles wr[N/2] wi[N/2], the edges e[B + 1] as 32-bit words, hist[n_in][N]: the last N input frames per channel, oldest
+// first (zeros at activation: the SPEC's x[n < 0]), and the spectrum ring [R][n_in][B].  The host uploads window, twiddles and edges
+// (fwgpu_control_math.cpp spectrum_tables) as the slice's `head`, spec_head_len floats from spec_win_rel on.
+FW_TYPES_HD inline bool spec_on(const NodeState& s) { return s.loop_start != 0; }
+FW_TYPES_HD inline bool spec_state_ok(const NodeState& s, int n_in, int n_out) {
+    const uint64_t R = s.loop_end, N = s.loop_start;
+    const uint32_t bands = (uint32_t)s.full_range, B = (uint32_t)s.playing;
+    return R >= 1 && R <= METER_RING_MAX && N >= SPEC_FFT_MIN && N <= SPEC_FFT_MAX && (N & (N - 1)) == 0 && s.full_range >= 0 && bands <= N / 2 &&
+           B == (bands ? bands : (uint32_t)N / 2 + 1) && n_in >= 1 && n_in <= SPEC_CH_MAX && (n_out == n_in || n_out == 0) &&
+           R * (uint64_t)n_in * B <= SPEC_RING_FLOATS_MAX;
+}
+FW_TYPES_HD inline uint32_t spec_win_rel(const NodeState& s, int n_in) { return ((uint32_t)s.loop_end * (uint32_t)n_in * 4u + 63u) / 64u * 64u; }
+FW_TYPES_HD inline uint32_t spec_tw_rel(const NodeState& s, int n_in) { return spec_win_rel(s, n_in) + (uint32_t)s.loop_start; }
+FW_TYPES_HD inline uint32_t spec_edges_rel(const NodeState& s, int n_in) { return spec_win_rel(s, n_in) + 2u * (uint32_t)s.loop_start; }
+FW_TYPES_HD inline uint32_t spec_head_len(const NodeState& s) { return 2u * (uint32_t)s.loop_start + ((uint32_t)s.playing + 1u + 63u) / 64u * 64u; }
+FW_TYPES_HD inline uint32_t spec_hist_rel(const NodeState& s, int n_in) { return spec_win_rel(s, n_in) + spec_head_len(s); }
+FW_TYPES_HD inline uint32_t spec_ring_rel(const NodeState& s, int n_in) { return spec_hist_rel(s, n_in) + (uint32_t)n_in * (uint32_t)s.loop_start; }
+FW_TYPES_HD inline uint32_t spec_ext_len(const NodeState& s, int n_in) {
+    return spec_ring_rel(s, n_in) + (uint32_t)s.loop_end * (uint32_t)n_in * (uint32_t)s.playing;
+}
 
 // A ramp: a value moved from a to b over N frames by one message.  The frame at position u in [0, 1) is a + (d * u),
 // d = b - a (callers hoist it), each a separately rounded f32 operation (-ffp-contract=off).  The clamp: a + d can round one ulp past

@@ -495,17 +495,50 @@ METER_DTYPE = np.dtype([("peak", np.float32), ("sum_squares", np.float32), ("ove
 class MeterNode(_Node):
     """SPEC node: level meter — per block and input channel the peak, the sum of squares and the number of
     samples over 1.0, measured on the device.  add_node(n, n, MeterNode()) passes the audio through, add_node(n, 0, ...) is a tap.
-    `ring_blocks` (1..65536) = how many blocks of readings the node retains for `read` / FirewheelGpuCtx.meter_read"""
+    `ring_blocks` (1..65536) = how many blocks of readings the node retains for `read` / FirewheelGpuCtx.meter_read.
+    With `fft_size` (256, 512, 1024, 2048 or 4096; at most 8 channels) the node is a spectrum meter as well: per block and input channel
+    the band powers of a Hann-windowed FFT over the channel's last fft_size frames, `bands` log-spaced bands over bins 1..fft_size/2
+    (0: every bin, DC included), read by `spectrum` / FirewheelGpuCtx.spectrum_read"""
     KIND = 16
 
-    def __init__(self, ring_blocks=1024):
+    def __init__(self, ring_blocks=1024, fft_size=None, bands=32):
         self.ring_blocks = ring_blocks
+        self.fft_size = fft_size
+        self.bands = bands
 
     def params(self):
-        return [float(self.ring_blocks)]
+        if self.fft_size is None:
+            return [float(self.ring_blocks)]
+        return [float(self.ring_blocks), float(self.fft_size), float(self.bands)]
 
     def read(self, first_block, num_blocks):
         return self.cx.meter_read(self.id, first_block, num_blocks)
+
+    def spectrum(self, first_block, num_blocks):
+        return self.cx.spectrum_read(self.id, first_block, num_blocks)
+
+    @staticmethod
+    def band_edges(fft_size, bands):
+        """the SPEC's edges e[0..B]: band b covers bins e[b] .. e[b+1] - 1 (bands == 0: B = fft_size/2 + 1, e[b] = b)"""
+        M = fft_size // 2
+        if bands == 0:
+            return np.arange(M + 2, dtype=np.uint32)
+        e = [1]
+        for b in range(1, bands):
+            e.append(max(e[-1] + 1, min(M + 1 - (bands - b), int(math.floor(math.pow(float(M), float(b) / bands) + 0.5)))))
+        return np.array(e + [M + 1], dtype=np.uint32)
+
+    @staticmethod
+    def band_hz(fft_size, bands, sample_rate):
+        """[B][2]: the centre frequencies of each band's first and last bin"""
+        e = MeterNode.band_edges(fft_size, bands).astype(np.float64)
+        return np.stack([e[:-1], e[1:] - 1.0], axis=1) * (float(sample_rate) / fft_size)
+
+    @staticmethod
+    def power_db(power):
+        """10 * log10(power), in f32 (0 -> -inf): 0 dB is a full-scale sine on a bin centre"""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (np.float32(10.0) * np.log10(np.asarray(power, dtype=np.float32))).astype(np.float32)
 
     @staticmethod
     def gain_to_db(amp):
@@ -1156,6 +1189,38 @@ class FirewheelGpuCtx(object):
         done = C.c_uint64(0)
         n = self.L.fwgpu_meter_read(self.c, node_id, first_block, num_blocks, buf.ctypes.data_as(C.POINTER(_lib.MeterReading)) if num_blocks and n_in else None,
                                     C.byref(done))
+        if n < 0:
+            e = FwgpuError(n, self.L.fwgpu_last_error(self.c).decode())
+            e.blocks_done = done.value
+            raise e
+        return buf[:n, :n_in], done.value
+
+    def spectrum_layout(self, node_id):
+        """fwgpu_spectrum_layout: (fft_size, bands, edges) of a spectrum meter of the installed plan — `bands` as created (0: every bin),
+        edges a uint32 array of B + 1 entries, B the floats of one record.  Raises FwgpuError (-20) for any other node"""
+        n, b = C.c_uint32(0), C.c_uint32(0)
+        B = self.L.fwgpu_spectrum_layout(self.c, node_id, C.byref(n), C.byref(b), None, 0)
+        if B < 0:
+            raise FwgpuError(B, self.L.fwgpu_last_error(self.c).decode())
+        edges = np.zeros(B + 1, dtype=np.uint32)
+        self._check(min(0, self.L.fwgpu_spectrum_layout(self.c, node_id, None, None, edges.ctypes.data_as(C.POINTER(C.c_uint32)), B + 1)))
+        return n.value, b.value, edges
+
+    def spectrum_read(self, node_id, first_block, num_blocks):
+        """fwgpu_spectrum_read: (powers, blocks_done) — powers is a float32 array [n][n_in][B] of the blocks [first_block, first_block
+        + n) that exist yet, with fwgpu_meter_read's rules and errors (a plain meter: -20)"""
+        node = self._nodes.get(node_id)
+        n_in = getattr(node, "_n_in", 0) if node is not None else 0
+        done = C.c_uint64(0)
+        B = self.L.fwgpu_spectrum_layout(self.c, node_id, None, None, None, 0)
+        if B < 0:
+            n = self.L.fwgpu_spectrum_read(self.c, node_id, first_block, 0, None, C.byref(done))  # (for the block count and the message)
+            e = FwgpuError(n if n < 0 else B, self.L.fwgpu_last_error(self.c).decode())
+            e.blocks_done = done.value
+            raise e
+        buf = np.zeros((max(num_blocks, 1), max(n_in, 1), B), dtype=np.float32)
+        n = self.L.fwgpu_spectrum_read(self.c, node_id, first_block, num_blocks, buf.ctypes.data_as(C.POINTER(C.c_float)) if num_blocks and n_in else None,
+                                       C.byref(done))
         if n < 0:
             e = FwgpuError(n, self.L.fwgpu_last_error(self.c).decode())
             e.blocks_done = done.value

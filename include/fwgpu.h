@@ -59,7 +59,8 @@ enum fwgpu_node_kind {
     FWGPU_RESAMPLER = 13,     /* SPEC polyphase resampling source (0 inputs)  params: sample id, ratio, loop, playing */
     FWGPU_SPATIAL = 14,       /* SPEC 3D spatialiser (1|2 in, 2 out)          params: x, y, z of the source */
     FWGPU_HOST_NODE = 15,     /* any other `dyn AudioNodeProcessor` (graph/processor.rs:243): runs on the HOST, see below */
-    FWGPU_METER = 16,         /* SPEC level meter     params: ring_blocks (1..65536, default 1024); see fwgpu_meter_read */
+    FWGPU_METER = 16,         /* SPEC level meter     params: ring_blocks (1..65536, default 1024); see fwgpu_meter_read.  With two or more
+                                 parameters a spectrum meter: ring_blocks, fft_size, bands; see fwgpu_spectrum_read */
     FWGPU_LIMITER = 17,       /* SPEC look-ahead limiter (n in, n out, n in 1..8)  params: ceiling (linear, 0.001..1000, default 1.0),
                                  hold_frames (0..1920, default 128); see FWGPU_LIMITER_LATENCY */
     FWGPU_DUCKER = 18,        /* SPEC sidechain ducker (n + k in, n out, n and k in 1..8)  params: threshold (linear, 1e-6..1000, default
@@ -539,6 +540,42 @@ typedef struct fwgpu_meter_reading {
  * without a stream wait is out of scope (it would need a pinned, device-mapped ring). */
 int64_t fwgpu_meter_read(fwgpu_ctx* ctx, int64_t node, uint64_t first_block, uint32_t num_blocks, fwgpu_meter_reading* out,
                          uint64_t* blocks_done);
+
+/* ---- spectrum meter (SPEC): WHERE in frequency the energy of a bus is — what a spectrum display, a beat or onset
+ * detector or an audio-reactive effect reads — measured on the device like the levels.  A FWGPU_METER created with two or more
+ * parameters, `ring_blocks, fft_size, bands`, is a spectrum meter; created with none or one it is the plain node above.  fft_size N is
+ * one of 256, 512, 1024, 2048, 4096; bands is a whole number in 0..N/2 (default 32 when only two parameters are given); n_in in 1..8,
+ * n_out == n_in or 0.  NaN, Inf, a fraction, another N, bands > N/2, n_in > 8 and ring_blocks * n_in * B > 2^24 floats (B: the floats
+ * of one record, below) fail activation at fwgpu_update.  The level records, the audio and the silence flags are exactly a plain
+ * meter's, fwgpu_meter_read included.  Besides them the node keeps one record of B floats per (block, input channel), block g in slot
+ * g % ring_blocks of a second ring with the rules of the first.  Per input channel, x[n] the frames since the node's activation (every
+ * frame of every block, full or short; x[n < 0] = +0.0; a block flagged silent counts as +0.0 and is not read), for block g with last
+ * frame n_g, all in f32, every operation rounded, no FMA:
+ *   window    v[i] = x[n_g - N + 1 + i] * w[i], i in 0..N-1, w[i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * i / N)) (periodic Hann, host, f64)
+ *   transform complex radix-2 decimation-in-time FFT of (v, 0); twiddles wr[k] = (float)cos(2.0 * M_PI * k / N), wi[k] =
+ *             (float)(-sin(2.0 * M_PI * k / N)), k < N/2 (host tables); input in bit-reversed order, re[i] = v[bitrev(i)], im[i] = +0.0;
+ *             stages h = 1, 2, 4, .., N/2: for every group of 2h consecutive elements and j < h, a = element j, b = element j + h,
+ *             k = j * (N / (2h)):  tr = (wr[k]*b.re) - (wi[k]*b.im), ti = (wr[k]*b.im) + (wi[k]*b.re),
+ *             a' = (a.re + tr, a.im + ti), b' = (a.re - tr, a.im - ti)
+ *   power     P[k] = ((re[k]*re[k]) + (im[k]*im[k])) * (16.0f / (N*N)), k in 0..N/2: a full-scale sine on a bin centre reads 1.0 at its
+ *             bin and 0.25 at each neighbour
+ *   bands     band b = ((P[e[b]] + P[e[b]+1]) + ...) + P[e[b+1]-1], one ascending chain of f32 adds.  bands == 0: B = N/2 + 1, e[b] = b
+ *             (every bin, DC included).  Otherwise B = bands, M = N/2, e[0] = 1, e[B] = M + 1 and for 0 < b < B
+ *             e[b] = max(e[b-1] + 1, min(M + 1 - (B - b), (int)floor(pow((double)M, (double)b / B) + 0.5))): strictly increasing
+ * The hop is the block: windows overlap when the block is shorter than N; when it is longer only its last N frames are seen.  Blocks
+ * run through fwgpu_node_process pass the audio, are not recorded and leave the window's history untouched.  No parameters after
+ * creation. */
+#define FWGPU_SPECTRUM_FFT_MIN 256
+#define FWGPU_SPECTRUM_FFT_MAX 4096
+#define FWGPU_SPECTRUM_CH_MAX 8
+#define FWGPU_SPECTRUM_BANDS_DEFAULT 32
+/* fwgpu_meter_read's contract and error cases for the spectrum records: out[(i * n_in + c) * B + b].  FWGPU_ERR_INVALID also for a plain
+ * meter. */
+int64_t fwgpu_spectrum_read(fwgpu_ctx* ctx, int64_t node, uint64_t first_block, uint32_t num_blocks, float* out, uint64_t* blocks_done);
+/* Audio-side call.  Returns B, the floats of one record of spectrum meter `node` of the installed plan (FWGPU_ERR_INVALID: not one);
+ * stores N and the `bands` parameter (when non-NULL) and up to edges_cap of the B + 1 edges: band b covers bins e[b] .. e[b+1] - 1,
+ * bin k is centred on k * sample_rate / N Hz. */
+int fwgpu_spectrum_layout(fwgpu_ctx* ctx, int64_t node, uint32_t* fft_size, uint32_t* bands, uint32_t* edges, uint32_t edges_cap);
 
 /* ---- look-ahead limiter (FWGPU_LIMITER; SPEC).  The remedy that goes with the meter's `over` count and, like it,
  * leaves the mix in HBM: a linked-channel brickwall limiter with a hold, written as FIR stages — a sliding minimum of the target gain and

@@ -32,6 +32,11 @@ pub const FWGPU_CROSSFADE_CH_MAX: u32 = 8;
 pub const FWGPU_COMPRESSOR_WIN_MAX: u32 = 32768;
 pub const FWGPU_COMPRESSOR_HOLD_MAX: u32 = 2048;
 pub const FWGPU_COMPRESSOR_CH_MAX: u32 = 8;
+/// the smallest and the largest fft_size of a spectrum meter (a FWGPU_METER with two or more parameters), its most channels and its default band count
+pub const FWGPU_SPECTRUM_FFT_MIN: u32 = 256;
+pub const FWGPU_SPECTRUM_FFT_MAX: u32 = 4096;
+pub const FWGPU_SPECTRUM_CH_MAX: u32 = 8;
+pub const FWGPU_SPECTRUM_BANDS_DEFAULT: u32 = 32;
 /// the longest glide of fwgpu_resampler_glide, in frames
 pub const FWGPU_RESAMPLER_GLIDE_FRAMES_MAX: u32 = 16777216;
 /// the longest ride of fwgpu_gain_ride, in frames
@@ -220,6 +225,8 @@ extern "C" {
     pub fn fwgpu_rccl_last_error() -> *const c_char;
     pub fn fwgpu_synchronize(ctx: *mut fwgpu_ctx) -> c_int;
     pub fn fwgpu_meter_read(ctx: *mut fwgpu_ctx, node: i64, first_block: u64, num_blocks: u32, out: *mut fwgpu_meter_reading, blocks_done: *mut u64) -> i64;
+    pub fn fwgpu_spectrum_read(ctx: *mut fwgpu_ctx, node: i64, first_block: u64, num_blocks: u32, out: *mut f32, blocks_done: *mut u64) -> i64;
+    pub fn fwgpu_spectrum_layout(ctx: *mut fwgpu_ctx, node: i64, fft_size: *mut u32, bands: *mut u32, edges: *mut u32, edges_cap: u32) -> c_int;
     pub fn fwgpu_node_latency(ctx: *mut fwgpu_ctx, node: i64, frames: *mut u32) -> c_int;
     pub fn fwgpu_graph_latency_report(ctx: *mut fwgpu_ctx, out: *mut fwgpu_latency_skew, cap: u32) -> i64;
     pub fn fwgpu_graph_output_latency(ctx: *mut fwgpu_ctx, frames: *mut u32) -> c_int;

@@ -709,6 +709,7 @@ impl AudioNode for GpuResamplerNode {
 pub struct GpuMeterNode {
     b: Binding,
     ring_blocks: u32,
+    spectrum: Option<(u32, u32)>,
     num_inputs: usize,
 }
 /// one record per (block, input channel)
@@ -716,7 +717,34 @@ pub type MeterReading = ffi::fwgpu_meter_reading;
 impl GpuMeterNode {
     /// `ring_blocks` (1..=65536): how many blocks of readings the node retains
     pub fn new(cx: &Arc<GpuContext>, ring_blocks: u32) -> Self {
-        Self { b: Binding::new(cx), ring_blocks, num_inputs: 0 }
+        Self { b: Binding::new(cx), ring_blocks, spectrum: None, num_inputs: 0 }
+    }
+    /// A spectrum meter as well (at most [`ffi::FWGPU_SPECTRUM_CH_MAX`] channels): per block and input channel the band powers of a
+    /// Hann-windowed FFT over the channel's last `fft_size` frames (256, 512, 1024, 2048 or 4096), `bands` log-spaced bands over bins
+    /// `1..=fft_size/2` (0: every bin, DC included).  A full-scale sine on a bin centre reads 1.0.
+    pub fn with_spectrum(cx: &Arc<GpuContext>, ring_blocks: u32, fft_size: u32, bands: u32) -> Self {
+        Self { b: Binding::new(cx), ring_blocks, spectrum: Some((fft_size, bands)), num_inputs: 0 }
+    }
+    /// The floats of one spectrum record and the band edges `e[0..=B]`: band `b` covers bins `e[b] .. e[b+1] - 1`, bin `k` is centred on
+    /// `k * sample_rate / fft_size` Hz.  Audio-side call.
+    pub fn spectrum_layout(&self) -> Result<(usize, Vec<u32>), GpuError> {
+        let node = self.b.node.unwrap_or(-1);
+        let cx = self.b.cx.as_ptr();
+        let bands = self.b.cx.check(unsafe { ffi::fwgpu_spectrum_layout(cx, node, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), 0) } as i64)? as usize;
+        let mut edges = vec![0u32; bands + 1];
+        self.b.cx.check(unsafe { ffi::fwgpu_spectrum_layout(cx, node, std::ptr::null_mut(), std::ptr::null_mut(), edges.as_mut_ptr(), edges.len() as u32) } as i64)?;
+        Ok((bands, edges))
+    }
+    /// The spectrum records of blocks `[first_block, first_block + n)`, `out[(i * num_inputs + c) * B + b]`, for the `n <= num_blocks`
+    /// of them that exist yet, `B` (the floats of one record) and the context's block count.  Audio-side call, as [`GpuMeterNode::read`].
+    pub fn spectrum(&self, first_block: u64, num_blocks: u32) -> Result<(Vec<f32>, usize, u64), GpuError> {
+        let node = self.b.node.unwrap_or(-1);
+        let (bands, _) = self.spectrum_layout()?;
+        let mut out = vec![0f32; num_blocks as usize * self.num_inputs.max(1) * bands];
+        let mut done: u64 = 0;
+        let n = self.b.cx.check(unsafe { ffi::fwgpu_spectrum_read(self.b.cx.as_ptr(), node, first_block, num_blocks, out.as_mut_ptr(), &mut done) })?;
+        out.truncate(n as usize * self.num_inputs * bands);
+        Ok((out, bands, done))
     }
     /// The records of blocks `[first_block, first_block + n)`, `out[i * num_inputs + c]`, for the `n <= num_blocks` of them that exist
     /// yet, and the context's block count.  Audio-side call: waits for the context's stream.
@@ -746,7 +774,10 @@ impl AudioNode for GpuMeterNode {
     }
     fn activate(&mut self, _sr: u32, _mbf: usize, num_inputs: usize, num_outputs: usize) -> Result<Box<dyn AudioNodeProcessor>, Box<dyn Error>> {
         self.num_inputs = num_inputs;
-        self.b.activate(ffi::FWGPU_METER, num_inputs, num_outputs, &[self.ring_blocks as f32])
+        match self.spectrum {
+            None => self.b.activate(ffi::FWGPU_METER, num_inputs, num_outputs, &[self.ring_blocks as f32]),
+            Some((n, bands)) => self.b.activate(ffi::FWGPU_METER, num_inputs, num_outputs, &[self.ring_blocks as f32, n as f32, bands as f32]),
+        }
     }
     fn deactivate(&mut self, _p: Option<Box<dyn AudioNodeProcessor>>) {
         self.b.deactivate()

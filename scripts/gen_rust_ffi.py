@@ -95,6 +95,9 @@ def generate():
     o.append("pub const FWGPU_COMPRESSOR_WIN_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_COMPRESSOR_WIN_MAX (\d+)", open(HDR).read()).group(1)))
     o.append("pub const FWGPU_COMPRESSOR_HOLD_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_COMPRESSOR_HOLD_MAX (\d+)", open(HDR).read()).group(1)))
     o.append("pub const FWGPU_COMPRESSOR_CH_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_COMPRESSOR_CH_MAX (\d+)", open(HDR).read()).group(1)))
+    o.append("/// the smallest and the largest fft_size of a spectrum meter (a FWGPU_METER with two or more parameters), its most channels and its default band count")
+    for name in ("FWGPU_SPECTRUM_FFT_MIN", "FWGPU_SPECTRUM_FFT_MAX", "FWGPU_SPECTRUM_CH_MAX", "FWGPU_SPECTRUM_BANDS_DEFAULT"):
+        o.append("pub const %s: u32 = %d;" % (name, int(re.search(r"#define %s (\d+)" % name, open(HDR).read()).group(1))))
     o.append("/// the longest glide of fwgpu_resampler_glide, in frames")
     o.append("pub const FWGPU_RESAMPLER_GLIDE_FRAMES_MAX: u32 = %d;" % int(re.search(r"#define FWGPU_RESAMPLER_GLIDE_FRAMES_MAX (\d+)", open(HDR).read()).group(1)))
     o.append("/// the longest ride of fwgpu_gain_ride, in frames")
